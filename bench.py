@@ -2,6 +2,7 @@
 """Benchmark of the scan-matching / map-update hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config2|ref2level|config5] [--particles P]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one lidar scan processed for every particle of the rank: search-field build
 from each particle's own map, pose-cube sweep with soft-max pose draw and confidence,
@@ -10,10 +11,15 @@ one RCCL all-gather of the normaliser).  All inputs of all steps (ranges, pose e
 uniforms) are resident in HBM before the timed region; nothing is copied or synchronised
 inside it.
 
+A plain run sets up, warms up, times ONE block of K steps, writes the last step's outputs if --dump-outputs is given, and
+prints the result line.  --full adds everything else this file measures: the CPU baseline, the probe steps and the event
+pairs behind the roofline block, --repeats blocks (default 5, the median reported), the variants (other workloads, inputs,
+particle counts, the closed loop, the drop-in caller) and, sharded, what the normaliser's collective adds per rank.
+
 Default workload = BASELINE.json configs[1] ("config2": 800x800 @ 0.1 m search field,
 36x41x41 pose cube, 180 beams) with the north-star's 64 particles per GPU.  Prints ONE JSON
 line (rank 0).  The K-step timed block (barrier + synchronize on both sides) is repeated
---repeats times; value / ms_per_step are the median block.
+--repeats times (plain run: once); value / ms_per_step are the median block.
 N > 1: one rank per GPU, particles sharded P per rank (weak scaling), value = whole-job
 particle-scans/s.  Under a launcher (torch.distributed.run sets WORLD_SIZE) the ranks are
 taken from the environment; `python bench.py --gpus N` on its own re-executes itself under
@@ -78,7 +84,7 @@ def source_sha256():
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 100; config3: scans of the log, default the whole log)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="config2", choices=sorted(WORKLOADS) + ["config3"],
                     help="config3: the CLOSED loop over the bundled Intel log (ParticleFilter.run, host decisions, growth, resampling; "
@@ -90,8 +96,8 @@ def parse():
                     "sweep, reference defaults, config-5 slice, config-3 closed loop)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target duration of each CPU baseline leg (two legs: one process, all cores)")
     ap.add_argument("--cpu-workers", type=int, default=0, help="processes of the all-cores CPU baseline (0: every host core)")
-    ap.add_argument("--repeats", type=int, default=5, help="the K-step timed block is run this many times; value / ms_per_step are the "
-                    "median block (every block is bracketed by barrier + synchronize)")
+    ap.add_argument("--repeats", type=int, default=None, help="the K-step timed block is run this many times; value / ms_per_step are the "
+                    "median block (every block is bracketed by barrier + synchronize); default 1, with --full 5")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of a multi-rank run "
                     "(nccl = RCCL over xGMI; gloo: dry mode, the 24-byte all-gather hops through host memory)")
     ap.add_argument("--share-gpu", action="store_true", help="dry mode: ranks beyond the visible GPUs share them (rank r -> GPU r %% count)")
@@ -99,6 +105,10 @@ def parse():
                     "particles per GPU up, SLAM2D_BENCH_GROUPS overrides; 1 = one stream)")
     ap.add_argument("--total-particles", type=int, default=None, help="STRONG scaling: this many particles over all ranks (e.g. 512 = "
                     "BASELINE config 4, 1024 with --workload config5 = config 5); default: --particles per rank (weak scaling)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: CPU baseline, roofline (probe steps, event "
+                    "pairs), --repeats blocks, variants, the sharded normaliser's cost per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "computed as DIR/<name>.npy (float32 / float64, at most 64 MB; maps of particles other than 0 as a seeded sample)")
     ap.add_argument("--spawn-check", action="store_true", help="launch plumbing only (no GPU work): every rank joins a gloo group, "
                     "rank 0 prints the rank count it saw")
     return ap.parse_args()
@@ -1131,7 +1141,7 @@ def normaliser_probe(workload, P, K, W, G, base_ms):
         env.update(env_extra)
         env["MASTER_PORT"] = str(_free_port())
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", workload, "--particles", str(P), "--steps", str(K),
-               "--warmup", str(W), "--repeats", "5", "--no-variants", "--no-cpu-baseline"]
+               "--warmup", str(W), "--repeats", "5", "--full", "--no-variants", "--no-cpu-baseline"]
         res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=150)
         lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
         if res.returncode != 0 or not lines:
@@ -1202,7 +1212,7 @@ def closed_loop_sharded(args, world, rank, device):
     dataio = importlib.import_module("slam-2d-lidar-scan_amd.dataio")
     par = par_mod()
     readings = dataio.read_npz(os.path.join(REPO, "tests", "golden", "intel_gfs.npz"))
-    K = min(args.steps, len(readings)) if args.steps != 100 else len(readings)        # (the default --steps means the whole log)
+    K = min(args.steps, len(readings)) if args.steps else len(readings)        # (without --steps: the whole log)
     readings = readings[:K]
     total = args.total_particles or (args.particles or 64) * world
     first, count = par.shard_range(total, world, rank)
@@ -1233,6 +1243,13 @@ def closed_loop_sharded(args, world, rank, device):
         return el, pf, res
     leg()                                                  # warm-up (allocator, first builds)
     el, pf, res = min((leg() for _ in range(3)), key=lambda r: r[0]) if os.environ.get("SLAM2D_BENCH_LEGS", "3") != "1" else leg()
+    if args.dump_outputs and rank == 0:         # the filter of the leg reported: its weights, the particles' last poses, its maps
+        torch.cuda.synchronize()
+        outs = {"weights": np.asarray(pf.weights, dtype=np.float64)}
+        if pf.trajectory:
+            outs["last_xy"] = np.asarray(pf.trajectory[-1], dtype=np.float64)
+        outs.update(map_outputs(pf.engine.maps))
+        write_outputs(args.dump_outputs, outs)
     if rank == 0:
         print(json.dumps({
             "metric": "scans/sec (180-beam) x particles, closed loop over the Intel log", "value": total * K / el, "unit": "particle-scans/s",
@@ -1245,6 +1262,73 @@ def closed_loop_sharded(args, world, rank, device):
                                       f"{pf.n_groups} particle group(s) per GPU on the event-free calls" + (" (sharded commit: gate + all-gather + publishing merge)" if pf.sharded else "")},
             "scans_per_sec": K / el, "resamples": len(res), "state_moving_resamples": pf.stats["state_moving_resamples"],
             "scans_redone": pf.stats["redo"], "filter_stats": dict(pf.stats), "final_map_of_particle_0": [pf.engine.maps[0].rows, pf.engine.maps[0].cols]}), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+MAP_SAMPLE_CELLS = 16384            # cells of every particle's map in map_sample.npy (the same seeded positions for every map)
+MAP0_WHOLE_CELLS = 4 << 20          # particle 0's map goes out whole up to this many cells, else as a seeded sample of this many
+
+
+def _sample_index(rows, cols, n, seed):
+    """Fixed cell positions (row-major flat indices, sorted) of a rows x cols map: the same for every run with this shape."""
+    return np.sort(np.random.RandomState(seed).choice(rows * cols, size=min(n, rows * cols), replace=False))
+
+
+def map_outputs(maps):
+    """The particles' count maps as the dump holds them: map_counts_sum [P, 2] (visited, total summed over each whole map),
+    map_sample [P, MAP_SAMPLE_CELLS, 2] (the same seeded cells of every map), map0_visited / map0_total (particle 0's whole
+    map, or a seeded sample of MAP0_WHOLE_CELLS cells of a larger one)."""
+    sums, sample, idx_of = [], [], {}
+    for m in maps:
+        m._materialise()
+        c = m.cells[:, :m.cols].to(torch.int64).reshape(-1)
+        vis, tot = (c >> 32, c & 0xFFFFFFFF) if m.wide else ((c >> 16) & 0xFFFF, c & 0xFFFF)
+        sums.append(torch.stack([vis.sum(), tot.sum()]))
+        key = (m.rows, m.cols)
+        if key not in idx_of:
+            idx_of[key] = torch.from_numpy(_sample_index(m.rows, m.cols, MAP_SAMPLE_CELLS, 1)).to(c.device)
+        idx = idx_of[key]
+        sample.append(torch.stack([vis[idx], tot[idx]], dim=1))
+    if len({tuple(t.shape) for t in sample}) != 1:          # (maps of different sizes: a few cells fewer in the smaller ones)
+        n = min(t.shape[0] for t in sample)
+        sample = [t[:n] for t in sample]
+    out = {"map_counts_sum": torch.stack(sums).cpu().numpy().astype(np.float64),
+           "map_sample": torch.stack(sample).cpu().numpy().astype(np.float32)}
+    v0, t0 = maps[0].download()
+    if v0.size > MAP0_WHOLE_CELLS:
+        idx = _sample_index(v0.shape[0], v0.shape[1], MAP0_WHOLE_CELLS, 0)
+        v0, t0 = v0.reshape(-1)[idx], t0.reshape(-1)[idx]
+    out["map0_visited"], out["map0_total"] = v0.astype(np.float32), t0.astype(np.float32)
+    return out
+
+
+def hot_path_outputs(hot):
+    """What the last step of the timed path left for its caller: every level's match records (float64 [P, 8], the fields of
+    Slam2dMatch in order: x, y, theta, confidence, log_confidence, best_score, pick, argmax), the weights, the log-weights,
+    the normaliser's statistics and the maps (map_outputs)."""
+    torch.cuda.synchronize()
+    out = {}
+    for which in ("coarse", "fine"):
+        if which == "fine" and hot.fine is None:
+            continue
+        m = hot.matches(which)
+        out[f"{which}_match"] = np.stack([m[f].astype(np.float64) for f in m.dtype.names], axis=1)
+    out["weights"] = hot.d_w.cpu().numpy().astype(np.float64)
+    out["log_weights"] = hot.d_logw.cpu().numpy().astype(np.float64)
+    out["weight_stats"] = hot.d_stats.cpu().numpy().astype(np.float64)
+    out.update(map_outputs(hot.maps()))
+    return out
+
+
+def write_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array (float32 / float64 only, at most DUMP_LIMIT_BYTES in all)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: the outputs hold {total} bytes, more than the {DUMP_LIMIT_BYTES} --dump-outputs allows")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def spawn_check(args, world, rank):
@@ -1278,16 +1362,20 @@ def main():
         sys.exit(spawn_check(args, world, rank))
     force_dist = os.environ.get("SLAM2D_FORCE_DIST") == "1"     # exercise the sharded code path on one GPU
     cfg = WORKLOADS.get(args.workload, WORKLOADS["ref2level"])
-    P, K, W, R = args.particles or WORKLOAD_PARTICLES.get(args.workload, 64), args.steps, args.warmup, max(1, args.repeats)
+    K = args.steps if args.steps is not None else 100
+    R = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
+    P, W = args.particles or WORKLOAD_PARTICLES.get(args.workload, 64), args.warmup
     if args.total_particles:
         if args.total_particles % world:
             raise SystemExit(f"bench.py: --total-particles {args.total_particles} is no multiple of the {world} ranks")
         P = args.total_particles // world
-    nprobe = min(8, K)
+    if K < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    nprobe = min(8, K) if args.full else 0
     closed = args.workload == "config3"
     scen = None if closed else Scenario(cfg, P, W + max(K, nprobe), seed=0, rank=rank)
     cpu = None
-    if not closed and not args.no_cpu_baseline and world == 1 and rank == 0:
+    if args.full and not closed and not args.no_cpu_baseline and world == 1 and rank == 0:
         cpu = cpu_baseline(cfg, scen, args.cpu_seconds, args.cpu_workers)      # before HIP is initialised: the pool forks
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no HIP device visible)")
@@ -1342,37 +1430,39 @@ def main():
     for s in range(W):
         hot.step(s)
     flags = hot.take_flags()        # synchronises; raises on any fault
-    # a few bracketed steps (outside the timed region: an event pair costs ~5 us of stream time) find the dominant kernel
-    E._lib.check(lib.slam2d_prof_enable(sum(1 << st for st in stages), 4 * 8 + 8), "prof_enable")
-    for s in range(W, W + nprobe):
-        hot.step(s)
-    hot.take_flags()
-    probe_ms = collect()
-    dom_stage = max(stages, key=lambda st: probe_ms.get(E._lib.STAGE_NAMES[st], {}).get("total_ms", 0.0))
-    launches_per_step_of = {k: v["launches"] / nprobe for k, v in probe_ms.items()}
-    # what an event pair adds to a bracketed launch: the same pair with nothing in between, recorded while the stream is busy
-    timer = lib.slam2d_timer_create()
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    pair = []
-    for i in range(12):
-        hot.step(W + i % nprobe)
-        lib.slam2d_timer_start(timer, stream)
-        lib.slam2d_timer_stop(timer, stream)
-        ms = C.c_float(0)
-        E._lib.check(lib.slam2d_timer_elapsed_ms(timer, C.byref(ms)), "timer")
-        pair.append(1e3 * ms.value)
-    lib.slam2d_timer_destroy(timer)
-    hot.take_flags()
-    overhead_us = statistics.median(pair)
-    # timed region: R blocks of K steps, each bracketed by barrier + synchronize; only the dominant kernel keeps an event pair,
-    # and only around every n-th of its launches (an event pair holds the stream for ~6 us on each side of the kernel; odd n: a
-    # stage with one launch per level alternates between the levels)
-    dom_lps = launches_per_step_of.get(E._lib.STAGE_NAMES[dom_stage], 1.0)
-    every = int(max(1, min(PROF_EVERY_MAX, (R * K * dom_lps) // 13)))       # (>= 13 timed launches: the driver's 5 x 20 steps bracket every 15th)
-    if every > 1 and every % 2 == 0:
-        every -= 1
-    E._lib.check(lib.slam2d_prof_every(every), "prof_every")
-    E._lib.check(lib.slam2d_prof_enable(1 << dom_stage, int(R * K * dom_lps) // every + 16), "prof_enable")
+    every = None
+    if args.full:
+        # a few bracketed steps (outside the timed region: an event pair costs ~5 us of stream time) find the dominant kernel
+        E._lib.check(lib.slam2d_prof_enable(sum(1 << st for st in stages), 4 * 8 + 8), "prof_enable")
+        for s in range(W, W + nprobe):
+            hot.step(s)
+        hot.take_flags()
+        probe_ms = collect()
+        dom_stage = max(stages, key=lambda st: probe_ms.get(E._lib.STAGE_NAMES[st], {}).get("total_ms", 0.0))
+        launches_per_step_of = {k: v["launches"] / nprobe for k, v in probe_ms.items()}
+        # what an event pair adds to a bracketed launch: the same pair with nothing in between, recorded while the stream is busy
+        timer = lib.slam2d_timer_create()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        pair = []
+        for i in range(12):
+            hot.step(W + i % nprobe)
+            lib.slam2d_timer_start(timer, stream)
+            lib.slam2d_timer_stop(timer, stream)
+            ms = C.c_float(0)
+            E._lib.check(lib.slam2d_timer_elapsed_ms(timer, C.byref(ms)), "timer")
+            pair.append(1e3 * ms.value)
+        lib.slam2d_timer_destroy(timer)
+        hot.take_flags()
+        overhead_us = statistics.median(pair)
+        # timed region: R blocks of K steps, each bracketed by barrier + synchronize; only the dominant kernel keeps an event pair,
+        # and only around every n-th of its launches (an event pair holds the stream for ~6 us on each side of the kernel; odd n: a
+        # stage with one launch per level alternates between the levels)
+        dom_lps = launches_per_step_of.get(E._lib.STAGE_NAMES[dom_stage], 1.0)
+        every = int(max(1, min(PROF_EVERY_MAX, (R * K * dom_lps) // 13)))       # (>= 13 timed launches: the driver's 5 x 20 steps bracket every 15th)
+        if every > 1 and every % 2 == 0:
+            every -= 1
+        E._lib.check(lib.slam2d_prof_every(every), "prof_every")
+        E._lib.check(lib.slam2d_prof_enable(1 << dom_stage, int(R * K * dom_lps) // every + 16), "prof_enable")
     blocks, mine, enq = [], [], []
     for _ in range(R):
         el, own = timed_run(hot, W, K)
@@ -1380,14 +1470,19 @@ def main():
         flags = flags | hot.take_flags()
         blocks.append(el)
         mine.append(own)
-    lib.slam2d_prof_disable()
-    E._lib.check(lib.slam2d_prof_every(1), "prof_every")
-    stage_ms = collect()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, hot_path_outputs(hot))
+    if args.full:
+        lib.slam2d_prof_disable()
+        E._lib.check(lib.slam2d_prof_every(1), "prof_every")
+        stage_ms = collect()
     elapsed = statistics.median(blocks)
     # N > 1: what the sharded normaliser (24-byte all-gather + merge launch) adds to a step on this rank
     per_rank, normaliser_added_us = None, None
     if dist.is_initialized():
         own_ms = 1e3 * statistics.median(mine) / K
+        added = float("nan")
+    if dist.is_initialized() and args.full:
         saved = hot.sharded
         hot.sharded = False                          # the same steps with every rank normalising on its own: no collective
         if isinstance(hot, HotPathGroups):
@@ -1399,14 +1494,16 @@ def main():
             hot.world, hot.total_particles = world, total_saved
             hot.parts_all = torch.zeros(3 * hot.G * world, dtype=torch.float64, device=device) if saved else hot.parts_local
         hot.take_flags()
-        rec = _ctl([own_ms, 1e3 * (statistics.median(mine) - local) / K], device)
+        added = 1e3 * (statistics.median(mine) - local) / K
+    if dist.is_initialized():
+        rec = _ctl([own_ms, added], device)
         got = [torch.zeros_like(rec) for _ in range(world)]
         dist.all_gather(got, rec)
         per_rank = [float(g[0]) for g in got]
-        normaliser_added_us = [float(g[1]) for g in got]
+        normaliser_added_us = [float(g[1]) for g in got] if args.full else None
 
-    variants = {}
-    if not args.no_variants and world == 1:          # (multi-GPU scaling runs: the headline only)
+    variants, rf_main = {}, None
+    if args.full and not args.no_variants and world == 1:          # (multi-GPU scaling runs: the headline only)
         def variant(bnb, prune, note):
             saved = [(lv, lv.c.bnb) for lv in hot.levels()]
             for lv, _ in saved:
@@ -1446,12 +1543,11 @@ def main():
             ds = dropin_serial(64, 53, device)
             if ds is not None:
                 variants["dropin_serial"] = ds
-    else:
+    elif args.full:
         rf_main = roofline_of(hot, scen, P, 1e3 * elapsed / K, stage_ms, launches_per_step_of, args.workload, overhead_us, probe_ms=probe_ms)
 
     if rank == 0:
         total_units = P * world * K
-        rf_main.setdefault("event_pairs", {})["every"] = every
         out = {
             "metric": f"scans/sec ({cfg['beams']}-beam) x particles at fixed search volume",
             "value": total_units / elapsed, "unit": "particle-scans/s",
@@ -1476,11 +1572,13 @@ def main():
             "timed_blocks": {"repeats": R, "steps_each": K, "ms_per_step_of_each": [round(1e3 * b / K, 5) for b in blocks], "reported": "median",
                              "host_enqueue_ms_per_step": round(1e3 * statistics.median(enq) / K, 5),
                              "host_issue": hot.E._lib.group_policy()},      # cores / local ranks -> worker threads or not (include/slam2d.h: slam2d_group_policy)
-            "roofline": rf_main,
-            "stages_probe": {k: {"avg_us": round(v["avg_us"], 2), "launches": v["launches"]} for k, v in probe_ms.items()},
-            "algorithmic_bytes_per_particle_scan": hot.algorithmic_bytes(scen),
             "fault_flags": int(np.bitwise_or.reduce(flags)) if len(flags) else 0,
         }
+        if args.full:
+            rf_main.setdefault("event_pairs", {})["every"] = every
+            out["roofline"] = rf_main
+            out["stages_probe"] = {k: {"avg_us": round(v["avg_us"], 2), "launches": v["launches"]} for k, v in probe_ms.items()}
+            out["algorithmic_bytes_per_particle_scan"] = hot.algorithmic_bytes(scen)
         if dist.is_initialized():
             out["ranks"] = {"backend": args.backend, "ranks_seen": ranks_seen, "gpus_visible": ngpu, "shared_gpu": bool(args.share_gpu and world > ngpu),
                             "ms_per_step_per_rank": per_rank, "normaliser_added_us_per_rank": normaliser_added_us}

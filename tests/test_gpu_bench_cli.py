@@ -1,6 +1,7 @@
 """bench.py end to end on the GPU box: the N-rank path in its one-GPU dry mode (`--gpus 2 --backend gloo --share-gpu`: two
 ranks, 64 particles each, both on cuda:0, the 24-byte all-gather through gloo) must report two ranks; the driver's short
-form must print one well-formed line with the roofline and CPU-baseline blocks."""
+form must print one well-formed line (with --full: the roofline and CPU-baseline blocks too), time exactly the steps asked for,
+and dump the same outputs from run to run."""
 import json
 import os
 import subprocess
@@ -26,10 +27,10 @@ def test_two_ranks_on_one_gpu_dry_mode():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    d = _bench(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "6", "--warmup", "3", "--repeats", "2", "--no-variants", "--no-cpu-baseline"])
+    d = _bench(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "6", "--warmup", "3", "--repeats", "2", "--full", "--no-variants", "--no-cpu-baseline"])
     assert d["n_gpus"] == 2 and d["ranks"]["ranks_seen"] == 2 and d["config"]["total_particles"] == 128
     assert len(d["ranks"]["ms_per_step_per_rank"]) == 2 and d["fault_flags"] == 0 and d["scaling"] == "weak"
-    one = _bench(["--gpus", "1", "--steps", "6", "--warmup", "3", "--repeats", "2", "--no-variants", "--no-cpu-baseline"])
+    one = _bench(["--gpus", "1", "--steps", "6", "--warmup", "3", "--repeats", "2", "--full", "--no-variants", "--no-cpu-baseline"])
     assert one["n_gpus"] == 1 and one["config"]["total_particles"] == 64 and "ranks" not in one
     # same per-rank work in both runs: the processed-bytes accounting of a step must agree
     a, b = d["roofline"]["whole_step"]["whole_array_bytes_per_particle_scan"], one["roofline"]["whole_step"]["whole_array_bytes_per_particle_scan"]
@@ -40,7 +41,7 @@ def test_driver_form_prints_the_contract_line():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    d = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-variants", "--cpu-seconds", "2"])
+    d = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-variants", "--cpu-seconds", "2"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                 "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -48,6 +49,35 @@ def test_driver_form_prints_the_contract_line():
     assert rf["bound"] == "hbm" and rf["peak"] == 8000.0 and 0 < rf["frac"] < 1 and rf["event_pairs"]["launches_timed"] >= 3
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12
     assert d["steps"] == 5 and d["timed_blocks"]["repeats"] == 5 and d["cpu_baseline"]["kind"] == "port"
+
+
+def test_plain_driver_form_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """The plain form (no --full): one block of exactly --steps steps, the headline fields and nothing that needs runs of its
+    own; --dump-outputs writes the last timed step's results (float32 / float64, at most 64 MB), the same in two runs."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _bench(["--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(out)])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+            assert key in d, key
+        for key in ("roofline", "cpu_baseline", "variants", "stages_probe"):
+            assert key not in d, key
+        assert d["steps"] == 7 and d["warmup"] == 3 and d["timed_blocks"]["repeats"] == 1 and d["fault_flags"] == 0
+        assert len(d["timed_blocks"]["ms_per_step_of_each"]) == 1 and abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        files = sorted(out.glob("*.npy"))
+        arrays = {f.stem: np.load(f) for f in files}
+        assert {"coarse_match", "weights", "log_weights", "map_counts_sum", "map_sample", "map0_visited", "map0_total"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        assert arrays["coarse_match"].shape == (64, 8) and arrays["weights"].shape == (64,)
+        assert abs(arrays["weights"].sum() - 1.0) < 1e-9 and arrays["map_counts_sum"].shape == (64, 2)
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
 
 
 def test_closed_loop_workload_sharded_dry_mode():

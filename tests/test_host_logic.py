@@ -195,13 +195,15 @@ def test_text_log_ingest(tmp_path):
     assert dataio.text_log_to_npz(str(clf), str(tmp_path / "a.npz")) == 2
     back = dataio.read_npz(str(tmp_path / "a.npz"))
     assert list(back[1]["range"]) == [4.5, 5.75] and back[1]["x"] == 1.0
-    ref_raw, ref_json = "/root/reference/DataSet/RawData/csail.corrected.gfs", "/root/reference/DataSet/PreprocessedData/csail_gfs"
-    if os.path.exists(ref_raw) and os.path.exists(ref_json):          # the reference's own conversion, when it is around
-        got, _ = dataio.read_text_log(ref_raw)
-        want = dataio.read_json(ref_json)
-        assert len(got) == len(want)
-        for a, b in zip(got, want):
-            assert (a["x"], a["y"], a["theta"]) == (b["x"], b["y"], b["theta"]) and list(a["range"]) == list(b["range"])
+    # the reference's own conversion (DataPreprocess/preprocess_gfs.py) of the head of its CSAIL log
+    z = load_golden("csail_gfs_excerpt.npz")
+    (tmp_path / "csail.gfs").write_bytes(z["gfs"].tobytes())
+    (tmp_path / "csail_gfs").write_bytes(z["processed_json"].tobytes())
+    got, _ = dataio.read_text_log(str(tmp_path / "csail.gfs"))
+    want = dataio.read_json(str(tmp_path / "csail_gfs"))
+    assert len(got) == len(want) == 24
+    for a, b in zip(got, want):
+        assert (a["x"], a["y"], a["theta"]) == (b["x"], b["y"], b["theta"]) and list(a["range"]) == list(b["range"])
 
 
 def test_text_log_order_and_duplicates_follow_the_reference(tmp_path):

@@ -1,4 +1,4 @@
-for G in 2 3 6; do python bench.py --particles 66 --groups $G --steps 60 --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+for G in 2 3 6; do python bench.py --full --particles 66 --groups $G --steps 60 --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -3,7 +3,7 @@ cp slam-2d-lidar-scan_amd/libslam2d_hip.so /tmp/orig.so
 for LIB in "$@"; do
   cp $LIB slam-2d-lidar-scan_amd/libslam2d_hip.so
   for WL in config2 ref2level; do
-    python bench.py --workload $WL --steps 30 --warmup 5 --no-cpu-baseline 2>&1 | python -c "
+    python bench.py --full --workload $WL --steps 30 --warmup 5 --no-cpu-baseline 2>&1 | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -5,7 +5,7 @@ for LIB in "$@"; do
   ENVS=""; [ "$LIB" != "-" ] && ENVS="SLAM2D_LIB=$PWD/$LIB"
   for WL in ${AB_WL:-config2 ref2level config5}; do
     for PP in ${AB_P:-0}; do PARG=""; [ "$PP" != "0" ] && PARG="--particles $PP"
-    env $ENVS python bench.py --workload $WL $PARG --steps ${AB_STEPS:-60} --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+    env $ENVS python bench.py --full --workload $WL $PARG --steps ${AB_STEPS:-60} --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -6,7 +6,7 @@
 #   bench      python bench.py (default command) and the driver's short form
 #   clock      in-kernel phase stamps (debug build; LAST: it rebuilds the library)
 #   pmc        HBM / SQ / TCP counter passes of the three workloads -> gpurun_out/pmc3/<wl>/<pass>
-#   multi      bench.py --gpus 2 on one GPU (gloo dry mode)
+#   multi      bench.py --full --gpus 2 on one GPU (gloo dry mode)
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $ROOT/gpurun_out
@@ -24,7 +24,7 @@ kstat)
   for WL in ${KSTAT_WL:-config2 ref2level config5}; do
     OUT=$ROOT/gpurun_out/kstat_$WL${KSTAT_TAG:-}; rm -rf $OUT
     ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o k -- \
-        python $ROOT/bench.py --workload $WL --steps 40 --warmup 5 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
+        python $ROOT/bench.py --full --workload $WL --steps 40 --warmup 5 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
     echo "kstat $WL rc=$?"
     python - <<PY
 import csv, glob
@@ -54,7 +54,7 @@ pmc)
       N=${PASS%%:*}; C=${PASS#*:}
       OUT=$ROOT/gpurun_out/pmc3/$WL/$N; rm -rf $OUT; mkdir -p $OUT
       ( cd /tmp && timeout 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT -o pmc -- \
-          python $ROOT/bench.py --workload $WL --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
+          python $ROOT/bench.py --full --workload $WL --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
       echo "pmc $WL $N rc=$?"
     done
   done
@@ -68,7 +68,7 @@ ab)
   for WL in ${AB_WL:-config2}; do
     for SET in "${SETS[@]}"; do
       ENVS=$(echo "$SET" | tr ',' ' '); [ "$SET" = "-" ] && ENVS=""
-      env $ENVS python bench.py --workload $WL --steps ${AB_STEPS:-60} --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+      env $ENVS python bench.py --full --workload $WL --steps ${AB_STEPS:-60} --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):
@@ -82,7 +82,7 @@ fetch)
     N=${PASS%%:*}; C=${PASS#*:}
     OUT=$ROOT/gpurun_out/pmc4${FETCH_TAG:-}/config2/$N; rm -rf $OUT; mkdir -p $OUT
     ( cd /tmp && env ${FETCH_ENV:-} timeout 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT -o pmc -- \
-        python $ROOT/bench.py --workload config2 --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
+        python $ROOT/bench.py --full --workload config2 --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
     echo "fetch${FETCH_TAG:-} $N rc=$?"
     python - <<PY
 import csv, glob, collections

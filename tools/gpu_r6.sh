@@ -4,7 +4,7 @@
 #   newtests    only the tests named in $NEWTESTS (a -k expression)
 #   kstatp      rocprofv3 --kernel-trace --stats of `bench.py --workload $WL --particles $P` for P in $PS -> gpurun_out/kstat_<wl>_p<P>
 #   pmcp        HBM / SQ / TCP counter passes of the same commands -> gpurun_out/pmc6/<wl>_p<P>/<pass>
-#   psweep      bench.py --particles P (no variants) for P in $PS: ms per step, us per particle-scan, stage probes
+#   psweep      bench.py --full --particles P (no variants) for P in $PS: ms per step, us per particle-scan, stage probes
 #   bench       python bench.py (default command) and the driver's short form
 #   ab          A/B of environment switches (AB="A=1,B=2;-"), AB_WL workloads, AB_P particles
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
@@ -26,7 +26,7 @@ kstatp)
   for P in $PS; do
     OUT=$ROOT/gpurun_out/kstat_${WL}_p$P${KSTAT_TAG:-}; rm -rf $OUT
     ( cd /tmp && env ${KSTAT_ENV:-} timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o k -- \
-        python $ROOT/bench.py --workload $WL --particles $P --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
+        python $ROOT/bench.py --full --workload $WL --particles $P --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
     echo "kstat $WL p$P rc=$?"
     python - <<PY
 import csv, glob
@@ -47,13 +47,13 @@ pmcp)
       N=${PASS%%:*}; C=${PASS#*:}
       OUT=$ROOT/gpurun_out/pmc6/${WL}_p$P/$N; rm -rf $OUT; mkdir -p $OUT
       ( cd /tmp && env ${PMC_ENV:-} timeout 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT -o pmc -- \
-          python $ROOT/bench.py --workload $WL --particles $P --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
+          python $ROOT/bench.py --full --workload $WL --particles $P --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
       echo "pmc $WL p$P $N rc=$?"
     done
   done ;;
 psweep)
   for P in $PS; do
-    env ${SWEEP_ENV:-} python bench.py --workload $WL --particles $P --steps ${AB_STEPS:-60} --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+    env ${SWEEP_ENV:-} python bench.py --full --workload $WL --particles $P --steps ${AB_STEPS:-60} --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):
@@ -71,7 +71,7 @@ ab)
     for P in ${AB_P:-256}; do
       for SET in "${SETS[@]}"; do
         ENVS=$(echo "$SET" | tr ',' ' '); [ "$SET" = "-" ] && ENVS=""
-        env $ENVS python bench.py --workload $W --particles $P --steps ${AB_STEPS:-60} --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+        env $ENVS python bench.py --full --workload $W --particles $P --steps ${AB_STEPS:-60} --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

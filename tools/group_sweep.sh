@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT
 for P in 128 256 512; do for G in 1 2 4; do
-python bench.py --particles $P --groups $G --steps 60 --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+python bench.py --full --particles $P --groups $G --steps 60 --warmup 8 --repeats 3 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

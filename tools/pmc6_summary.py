@@ -116,7 +116,7 @@ def write_profiles(tag, rnd):
     for f in g.glob(os.path.join(ROOT, f"gpurun_out/pmc6/{tag}/fetch/**/pmc_kernel_trace.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
             alone[short(r["Kernel_Name"])].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-    head = (f"rocprofv3 --pmc <one pass per line of tools/gpu_r6.sh pmcp> --kernel-trace -- python bench.py --workload {wl} --particles {p} --steps 12 --warmup 6 --repeats 1 "
+    head = (f"rocprofv3 --pmc <one pass per line of tools/gpu_r6.sh pmcp> --kernel-trace -- python bench.py --full --workload {wl} --particles {p} --steps 12 --warmup 6 --repeats 1 "
             f"--no-cpu-baseline --no-variants\nper-launch means after the warm-up launches; slam2d.hip sha256 {sha}\n"
             f"a launch serves one particle group = {int(p) // 2} particles (bench.py runs {p} particles per GPU in two groups on two streams)\n")
     lines = [head, "HBM traffic per launch (FETCH_SIZE / WRITE_SIZE are KB counters; gfx950: HBM bytes = 2 * FETCH_SIZE + WRITE_SIZE, MI355X_MICROARCH.md)",

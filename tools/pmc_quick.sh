@@ -14,11 +14,11 @@ for P in ${PS:-512}; do
     case " ${PASSES:-fetch write tcc sq sq2 tcp lds} " in *" $N "*) ;; *) continue ;; esac
     OUT=$ROOT/gpurun_out/pmc6/${WL}_p$P${TAG:-}/$N; rm -rf $OUT; mkdir -p $OUT
     ( cd /tmp && env ${ENVS:-} timeout 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT -o pmc -- \
-        python $ROOT/bench.py --workload $WL --particles $P --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
+        python $ROOT/bench.py --full --workload $WL --particles $P --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
     echo "pmc $WL p$P $N rc=$?"
   done
   OUT=$ROOT/gpurun_out/kstat_${WL}_p$P${TAG:-}; rm -rf $OUT
   ( cd /tmp && env ${ENVS:-} timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o k -- \
-      python $ROOT/bench.py --workload $WL --particles $P --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
+      python $ROOT/bench.py --full --workload $WL --particles $P --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-variants > $OUT.log 2>&1 )
   cd $ROOT && python tools/pmc6_summary.py ${WL}_p$P${TAG:-} --alone
 done

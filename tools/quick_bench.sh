@@ -3,7 +3,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 mkdir -p gpurun_out
 timeout 1200 python -m pytest tests -m gpu -q --maxfail=20 -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1; echo pytest rc=$?; tail -n 12 gpurun_out/pytest_gpu.log | cut -c1-300
 for WL in "${@:-config2}"; do
-python bench.py --workload $WL --steps 60 --warmup 8 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+python bench.py --full --workload $WL --steps 60 --warmup 8 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

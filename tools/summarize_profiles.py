@@ -2,7 +2,7 @@
 """Turn the rocprofv3 outputs of tools/gpu_r4.sh (stages `kstat` and `pmc`) under gpurun_out/ into the small summaries
 committed under profiles/:
 
-  profiles/<round>_<workload>_kernel_stats.csv   rocprofv3 --kernel-trace --stats of `python bench.py --workload <wl>`
+  profiles/<round>_<workload>_kernel_stats.csv   rocprofv3 --kernel-trace --stats of `python bench.py --full --workload <wl>`
   profiles/<round>_pmc_<workload>.txt            per-launch HBM traffic of every kernel (FETCH_SIZE / WRITE_SIZE passes)
   profiles/<round>_counters_<workload>.txt       SQ / TCP counters per launch
   profiles/traffic.json                          what bench.py's roofline block reads: per-launch HBM bytes per kernel,
@@ -122,7 +122,7 @@ for wl in ("config2", "ref2level", "config5"):
     except Exception as exc:
         print("no kernel-stats durations for", wl, repr(exc))
     step_total = sum(v["hbm_bytes_corrected"] * v["launches_per_step"] for kk, v in entries.items() if kk.startswith(wl + ":") and v["in_step"])
-    head = (f"rocprofv3 --pmc {{FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum}} --kernel-trace -- python bench.py --workload {wl} --steps 12 --warmup 6 "
+    head = (f"rocprofv3 --pmc {{FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum}} --kernel-trace -- python bench.py --full --workload {wl} --steps 12 --warmup 6 "
             "--repeats 1 --no-cpu-baseline --no-variants\nper-launch means after the warm-up launches; FETCH/WRITE_SIZE are KB counters (x1024 here); "
             f"slam2d.hip sha256 {sha[:16]}\nlaunches/step is relative to k_grid_update (one launch per scan and particle group: bench.py steps its particles in "
             f"groups on separate streams, so a 64-particle scan is four launch sequences of 16 -- config 5: two of 64)\n"
@@ -131,7 +131,7 @@ for wl in ("config2", "ref2level", "config5"):
     print(head + "\n".join(lines))
     if extra:
         open(f"profiles/{ROUND}_counters_{wl}.txt", "w").write(
-            f"rocprofv3 --pmc <SQ_* | TCP_*> --kernel-trace -- python bench.py --workload {wl} --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants\n"
+            f"rocprofv3 --pmc <SQ_* | TCP_*> --kernel-trace -- python bench.py --full --workload {wl} --steps 12 --warmup 6 --repeats 1 --no-cpu-baseline --no-variants\n"
             "per-launch means after the warm-up launches (raw counter values)\n" + "\n".join(extra) + "\n")
         print("\n".join(extra))
 
