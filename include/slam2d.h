@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define SLAM2D_ABI_VERSION 17
+#define SLAM2D_ABI_VERSION 18
 #define SLAM2D_SPOKE_BAND 16         /* radial band width of the beam-major spoke table, in cells */
 
 /* library error codes (negative; positive values are hipError_t) */
@@ -258,6 +258,18 @@ typedef struct {
     int32_t argmax;          /* flat cube index of the maximum (lowest index on ties) */
 } Slam2dMatch;
 
+
+/* ABI 18: where a beam of a batch of scans writes (slam2d_map_scans), planned by the host as the reference's per-beam growth
+ * (Utils/OccupancyGrid.py:144-152) replays: the beam's indices are taken against (lim_x0, lim_y0), the limits after the
+ * earlier beams' and scans' growth and before the beam's own; they wrap (a negative index + cols / rows, as Python) against
+ * the shape right after the beam's own growth; every low-side growth later in the batch moves them by (ac, ar). */
+typedef struct {
+    double  lim_x0, lim_y0;  /* mapXLim[0], mapYLim[0] when the beam's indices are computed (:144-145) */
+    int32_t dc, dr;          /* low-side shift of the beam's own growth (bookkeeping; the kernel does not read it) */
+    int32_t ac, ar;          /* sum of the low-side shifts of every LATER growth of the batch */
+    int32_t cols, rows;      /* map shape right after the beam's own growth */
+} Slam2dBeamPlan;
+
 /* ------------------------------------------------------------------------- */
 
 int slam2d_abi_version(void);
@@ -359,6 +371,31 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
 int slam2d_grid_update(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t P,
                        const double* d_pose, int32_t pose_stride, const double* d_ranges,
                        const int32_t* d_beam_shift, uint32_t* d_flags, void* stream);
+
+/* ABI 18: the exact fp64 extent of the occupied points of every (scan, beam) of S scans (Utils/OccupancyGrid.py:142-147:
+ * x + xAtSpokeDir[occupiedIdx], y + yAtSpokeDir[occupiedIdx]), the only thing checkMapToExpand (:108-118) asks of them:
+ *   d_pose[s*pose_stride + 0..2] = (x, y, theta), d_ranges [S][beams]
+ *   d_out [S][beams][4] = (min x, max x, min y, max y); +inf, -inf, +inf, -inf for a beam without occupied cells. */
+int slam2d_occ_extent(const Slam2dLidar* lidar, int32_t S, const double* d_pose, int32_t pose_stride, const double* d_ranges,
+                      double* d_out, void* stream);
+
+/* ABI 18: updateOccupancyGrid (Utils/OccupancyGrid.py:127-152) for S scans at given poses into ONE map, in one launch, with the
+ * reference's semantics exactly -- also where slam2d_grid_update's plain read-modify-write is not: a pose on a half cell (two
+ * adjacent window columns or rows round to one map index), a window step that is not the map unit, stale indices that wrap.
+ *   d_map:     one map descriptor (device), already grown to the batch's final extent (the host replays the growth from
+ *              slam2d_occ_extent and allocates once)
+ *   d_plan:    [S][beams] Slam2dBeamPlan
+ *   d_lut_bin: [W][W] uint16 spoke bin of every window cell, d_lut_r: [W][W] its radius (spokesGrid, :32-45)
+ * A fancy-index statement -- one beam's empty cells (total += 1), its occupied cells (visited += 2, total += 2) -- adds to
+ * every map element it names ONCE however many of its cells name it; statements, beams and scans add up (integer atomics: the
+ * result does not depend on timing).  Per scan a map element receives at most 3 (1 + 2) from each beam that reaches it; when the
+ * scan's window lies inside the map (no growth, no wrap) at most four window cells reach one element, so at most 8.  A narrow
+ * map raises SLAM2D_F_COUNT_OVERFLOW if a `total` passed 16 bits (the host promotes before that can happen); a cell outside
+ * the map (the reference: IndexError) raises SLAM2D_F_UPDATE_OUTSIDE_MAP and is skipped.  d_flags[0] receives the bits.
+ * occ_bits is NOT maintained: call slam2d_map_refresh_bits afterwards. */
+int slam2d_map_scans(const Slam2dLidar* lidar, const Slam2dMap* d_map, int32_t S, const double* d_pose, int32_t pose_stride,
+                     const double* d_ranges, const Slam2dBeamPlan* d_plan, const uint16_t* d_lut_bin, const double* d_lut_r,
+                     uint32_t* d_flags, void* stream);
 
 /* Particle.updateEstimatedPose for P particles (Algorithm/FastSlam.py:77-106): the pose prior of the
  * next scan from the previous matched poses and the raw odometry increment.

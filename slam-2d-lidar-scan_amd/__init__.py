@@ -9,7 +9,8 @@ with ``importlib.import_module("slam-2d-lidar-scan_amd")`` or through the
 
 ``OccupancyGrid`` / ``ScanMatcher`` keep the reference's class surface
 (Utils/OccupancyGrid.py, Utils/ScanMatcher_OGBased.py); ``ParticleFilter`` is the
-batched counterpart of Algorithm/FastSlam.py's.  All three need the HIP library
+batched counterpart of Algorithm/FastSlam.py's.  ``map_from_poses`` builds the map of a log at
+given poses (Utils/OccupancyGrid.py:main).  All of them need the HIP library
 (``libslam2d_hip.so``, built by ``__graft_entry__.build()``) and a GPU; there is no
 CPU fallback.
 """
@@ -28,6 +29,7 @@ _LAZY = {
     "SearchLevel": ("engine", "SearchLevel"),
     "LidarModel": ("engine", "LidarModel"),
     "MapState": ("engine", "MapState"),
+    "map_from_poses": ("mapping", "map_from_poses"),
 }
 
 

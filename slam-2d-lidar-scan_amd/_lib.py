@@ -43,7 +43,7 @@ MAX_BLUR_RADIUS = 16
 MAX_BEAMS = 2048
 SPOKE_BAND = 16
 SYNC_WORDS = 4
-ABI_VERSION = 17
+ABI_VERSION = 18
 MATCH_PRUNE_BY_PRIOR = 1
 MATCH_PRIOR_READY = 2
 PRUNE_MARGIN = 40.0
@@ -136,7 +136,13 @@ class Slam2dScan(C.Structure):
                 ("next_raw_turn", C.c_double), ("next_has_turn", C.c_int32)]
 
 
-STRUCTS = {"Slam2dGroup": Slam2dGroup, "Slam2dScan": Slam2dScan, "Slam2dMap": Slam2dMap, "Slam2dLidar": Slam2dLidar, "Slam2dFrame": Slam2dFrame,
+class Slam2dBeamPlan(C.Structure):
+    """Where one beam of a batch of scans writes (include/slam2d.h, slam2d_map_scans)."""
+    _fields_ = [("lim_x0", C.c_double), ("lim_y0", C.c_double), ("dc", C.c_int32), ("dr", C.c_int32),
+                ("ac", C.c_int32), ("ar", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32)]
+
+
+STRUCTS = {"Slam2dBeamPlan": Slam2dBeamPlan, "Slam2dGroup": Slam2dGroup, "Slam2dScan": Slam2dScan, "Slam2dMap": Slam2dMap, "Slam2dLidar": Slam2dLidar, "Slam2dFrame": Slam2dFrame,
            "Slam2dLevel": Slam2dLevel, "Slam2dMatch": Slam2dMatch, "Slam2dPartial": Slam2dPartial}
 
 # name -> (restype, argtypes); every symbol include/slam2d.h declares
@@ -151,6 +157,8 @@ SIGNATURES = {
     "slam2d_match": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), _vp, C.c_int32, _vp, C.c_int32, _vp,
                                C.c_double, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "slam2d_grid_update": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "slam2d_occ_extent": (C.c_int, [C.POINTER(Slam2dLidar), C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    "slam2d_map_scans": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "slam2d_prior": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int32, C.c_double, _vp, C.c_int32, _vp, _vp, _vp]),
     "slam2d_post_match": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "slam2d_weights_normalize": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),

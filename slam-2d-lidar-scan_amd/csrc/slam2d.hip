@@ -3872,6 +3872,150 @@ __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar
     if (f) atomicOr(&flags[p], f);
 }
 
+// ---- mapping from known poses (Utils/OccupancyGrid.py:main: updateOccupancyGrid per scan at given poses) ----
+// Both kernels take S scans x B beams, one wave per (scan, beam), MAPS_BEAMS adjacent beams of one scan per block, and walk
+// the beam's spoke cells by radial band as k_grid_update does.
+#define MAPS_BEAMS 4
+
+__device__ __forceinline__ int beam_spoke(const Slam2dLidar& lid, double th, int beam) {
+    const int S = lid.num_spokes;
+    int first = (lid.spoke_start + (int)rint(th / (2 * 3.141592653589793) * (double)S)) % S;     // :131,134
+    if (first < 0) first += S;
+    return (first + beam) % S;
+}
+
+// Exact fp64 extent of the occupied points x + xAtSpokeDir[occ], y + yAtSpokeDir[occ] of every (scan, beam) (:142-147):
+// out[(s * B + b) * 4 + 0..3] = (min x, max x, min y, max y), +inf / -inf for a beam without occupied cells.  checkMapToExpand
+// (:108-118) only asks any(x < lim) and its kin, so these four numbers replay a beam's growth exactly.
+__global__ __launch_bounds__(64 * MAPS_BEAMS) void k_occ_extent(Slam2dLidar lid, int S, int groups, const double* __restrict__ pose,
+                                                               int pstride, const double* __restrict__ ranges, double* __restrict__ out) {
+    const int s = blockIdx.x / groups, beam = (blockIdx.x % groups) * MAPS_BEAMS + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (s >= S || beam >= lid.beams) return;
+    const double px = pose[(size_t)s * pstride], py = pose[(size_t)s * pstride + 1], th = pose[(size_t)s * pstride + 2];
+    const double rg = ranges[(size_t)s * lid.beams + beam];
+    const double lo = rg - lid.wall_half, hi = rg + lid.wall_half;
+    const int nb = lid.num_bands;
+    const int* __restrict__ bp = lid.spoke_band + (size_t)beam_spoke(lid, th, beam) * (nb + 1);
+    double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    const int qlo = lo > 0.0 ? (int)fmin(floor(lo / lid.unit), 2.0e9) : 0;
+    const int qhi = hi > 0.0 ? (int)fmin(floor(hi / lid.unit), 2.0e9) : -1;
+    if (qhi >= 0) {
+        const int b0 = min(qlo / SLAM2D_SPOKE_BAND, nb), b1 = min(qhi / SLAM2D_SPOKE_BAND + 1, nb);
+        for (int k = bp[b0] + lane; k < bp[max(b0, b1)]; k += 64) {
+            const double r = lid.spoke_r[k];
+            if (!(r > lo && r < hi)) continue;                                     // :142-143
+            const uint32_t c = lid.spoke_cells[k];
+            const double x = px + lid.lut_xs[c & 0xffffu], y = py + lid.lut_xs[c >> 16];
+            x0 = fmin(x0, x); x1 = fmax(x1, x); y0 = fmin(y0, y); y1 = fmax(y1, y);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        x0 = fmin(x0, __shfl_xor(x0, o)); x1 = fmax(x1, __shfl_xor(x1, o));
+        y0 = fmin(y0, __shfl_xor(y0, o)); y1 = fmax(y1, __shfl_xor(y1, o));
+    }
+    if (lane == 0) {
+        double* o = out + ((size_t)s * lid.beams + beam) * 4;
+        o[0] = x0; o[1] = x1; o[2] = y0; o[3] = y1;
+    }
+}
+
+// convertRealXYToMapIdx of one window coordinate (:104-105) against the limit in force when the beam's indices are taken;
+// INT_MIN: not representable (a cell that far off is outside the map in any case)
+__device__ __forceinline__ int stale_idx(double p, double xs, double lim0, double unit) {
+    const double t = ((p + xs) - lim0) / unit;
+    return fabs(t) < 1e9 ? (int)rint(t) : INT_MIN;
+}
+
+// The window columns j' of one row-or-column axis whose stale index is v: the neighbours of j for v == a (its own index), and
+// the columns about (v - a) * unit / step further on for the wrapped alias v == a + n.  The index is non-decreasing in j and
+// the window step is in [unit, 2 unit), so no value is taken by more than two columns.  Writes (column, wrapped) pairs.
+__device__ __forceinline__ int axis_partners(const Slam2dLidar& lid, double p, double lim0, int j, int a, int n, int* col, int* wrapped) {
+    const int W = lid.lut_w;
+    int k = 0;
+    col[k] = j; wrapped[k++] = a < 0;
+    if (j > 0 && stale_idx(p, lid.lut_xs[j - 1], lim0, lid.unit) == a) { col[k] = j - 1; wrapped[k++] = a < 0; }
+    if (j + 1 < W && stale_idx(p, lid.lut_xs[j + 1], lim0, lid.unit) == a) { col[k] = j + 1; wrapped[k++] = a < 0; }
+    if (a < 0) {
+        // Python's wrap: a negative index a names element a + n; a cell of the same statement whose index IS a + n writes there too
+        const double step = (lid.lut_xs[W - 1] - lid.lut_xs[0]) / (double)(W - 1);
+        const int jc = j + (int)floor((double)n * lid.unit / step);
+        for (int t = jc - 1; t <= jc + 2; ++t)
+            if (t >= 0 && t < W && k < 6 && stale_idx(p, lid.lut_xs[t], lim0, lid.unit) == a + n) { col[k] = t; wrapped[k++] = 0; }
+    }
+    return k;
+}
+
+// updateOccupancyGrid (:127-152) for S scans at given poses into ONE map, the reference's semantics exactly:
+//  - indices are taken against the limits in force for that beam (plan[s][b].lim_*: after the earlier beams' and scans' growth,
+//    before the beam's own), wrap Python-style against the shape right after the beam's growth (cols, rows) and move with every
+//    later low-side growth of the batch (ac, ar) -- the map is already grown to the batch's final extent;
+//  - one fancy-index statement (a beam's empty cells; its occupied cells) adds to each element it names ONCE, however many of its
+//    cells name it: two adjacent window columns (rows) share an index when a pose sits on a half cell, or -- after a wrap --
+//    an index a < 0 and a + cols name one element.  Of the cells of a statement that name one element, the one first in the order
+//    (number of wrapped axes, window row, window column) writes; the others find it among their partners and stay silent;
+//  - statements add up: integer atomics, so the counts do not depend on the order in which the waves run.
+// The occupancy bits are NOT maintained (slam2d_map_refresh_bits afterwards).
+__global__ __launch_bounds__(64 * MAPS_BEAMS) void k_map_scans(Slam2dLidar lid, const Slam2dMap* __restrict__ map, int S, int groups,
+                                                              const double* __restrict__ pose, int pstride,
+                                                              const double* __restrict__ ranges, const Slam2dBeamPlan* __restrict__ plan,
+                                                              const uint16_t* __restrict__ lut_bin, const double* __restrict__ lut_r,
+                                                              uint32_t* flags) {
+    const int s = blockIdx.x / groups, beam = (blockIdx.x % groups) * MAPS_BEAMS + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (s >= S || beam >= lid.beams) return;
+    const Slam2dMap m = *map;
+    const Slam2dBeamPlan pl = plan[(size_t)s * lid.beams + beam];
+    const double px = pose[(size_t)s * pstride], py = pose[(size_t)s * pstride + 1], th = pose[(size_t)s * pstride + 2];
+    const double rg = ranges[(size_t)s * lid.beams + beam];
+    const double lo = rg - lid.wall_half, hi = rg + lid.wall_half;
+    const bool returned = rg < lid.max_range;
+    const int W = lid.lut_w, nb = lid.num_bands, spoke = beam_spoke(lid, th, beam);
+    const int* __restrict__ bp = lid.spoke_band + (size_t)spoke * (nb + 1);
+    const int qlo = lo > 0.0 ? (int)fmin(floor(lo / lid.unit), 2.0e9) : 0;
+    const int qhi = hi > 0.0 ? (int)fmin(floor(hi / lid.unit), 2.0e9) : -1;
+    if (qhi < 0) return;
+    const int b0 = returned ? 0 : min(qlo / SLAM2D_SPOKE_BAND, nb), b1 = min(qhi / SLAM2D_SPOKE_BAND + 1, nb);
+    const int kend = bp[max(b0, b1)];
+    uint32_t f = 0;
+    for (int k = bp[b0] + lane; k < kend; k += 64) {
+        const double r = lid.spoke_r[k];
+        const int cls = (returned && r < lo) ? 1 : (r > lo && r < hi) ? 2 : 0;       // :138-143
+        if (!cls) continue;
+        const uint32_t c = lid.spoke_cells[k];
+        const int j = (int)(c & 0xffffu), i = (int)(c >> 16);
+        const int ax = stale_idx(px, lid.lut_xs[j], pl.lim_x0, lid.unit), ay = stale_idx(py, lid.lut_xs[i], pl.lim_y0, lid.unit);
+        const int ex = ax < 0 && ax != INT_MIN ? ax + pl.cols : ax, ey = ay < 0 && ay != INT_MIN ? ay + pl.rows : ay;
+        if (ex < 0 || ex >= pl.cols || ey < 0 || ey >= pl.rows ||              // (the reference: IndexError)
+            ex + pl.ac >= m.cols || ey + pl.ar >= m.rows) { f |= SLAM2D_F_UPDATE_OUTSIDE_MAP; continue; }
+        int cj[6], wj[6], ci[6], wi[6];
+        const int ncj = axis_partners(lid, px, pl.lim_x0, j, ax, pl.cols, cj, wj);
+        const int nci = axis_partners(lid, py, pl.lim_y0, i, ay, pl.rows, ci, wi);
+        bool silent = false;
+        if (ncj > 1 || nci > 1) {
+            const int mine = wj[0] + wi[0];
+            for (int u = 0; u < nci && !silent; ++u)
+                for (int v = 0; v < ncj && !silent; ++v) {
+                    const int ii = ci[u], jj = cj[v], theirs = wi[u] + wj[v];
+                    if (!(theirs < mine || (theirs == mine && (ii < i || (ii == i && jj < j))))) continue;
+                    const size_t q = (size_t)ii * W + jj;
+                    if (lut_bin[q] != spoke) continue;
+                    const double rq = lut_r[q];
+                    silent = cls == 1 ? rq < lo : (rq > lo && rq < hi);
+                }
+        }
+        if (silent) continue;
+        const size_t at = (size_t)(ey + pl.ar) * m.pitch + (size_t)(ex + pl.ac);
+        if (m.wide) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(m.cells) + at, cls == 1 ? 1ull : 0x0000000200000002ull);
+        } else {
+            const uint32_t inc = cls == 1 ? 1u : 0x00020002u;
+            const uint32_t old = atomicAdd(m.cells + at, inc);
+            if ((old & 0xffffu) + (inc & 0xffffu) > 0xffffu) f |= SLAM2D_F_COUNT_OVERFLOW;   // (the host promotes before this can happen)
+        }
+    }
+    if (f) atomicOr(flags, f);
+}
+
 // Sharded normaliser, merge half: every rank folds the gathered [world][3] partials in rank order
 // (so the result does not depend on the network's reduction order), normalises its own particles
 // and evaluates sum (w - 1/N)^2 = sum w^2 - 1/N over ALL N particles (Algorithm/FastSlam.py:32-35).
@@ -4076,6 +4220,7 @@ int slam2d_sizeof(const char* name) {
     if (!strcmp(name, "Slam2dPartial")) return (int)sizeof(Slam2dPartial);
     if (!strcmp(name, "Slam2dGroup")) return (int)sizeof(Slam2dGroup);
     if (!strcmp(name, "Slam2dScan")) return (int)sizeof(Slam2dScan);
+    if (!strcmp(name, "Slam2dBeamPlan")) return (int)sizeof(Slam2dBeamPlan);
     return -1;
 }
 
@@ -4484,6 +4629,34 @@ int slam2d_grid_update(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_
                        int32_t pose_stride, const double* d_ranges, const int32_t* d_beam_shift, uint32_t* d_flags,
                        void* stream) {
     return launch_update(lidar, d_maps, P, d_pose, pose_stride, d_ranges, d_beam_shift, d_flags, WeightsJob{}, stream);
+}
+
+int slam2d_occ_extent(const Slam2dLidar* lidar, int32_t S, const double* d_pose, int32_t pose_stride, const double* d_ranges,
+                      double* d_out, void* stream) {
+    if (!lidar || !d_pose || !d_ranges || !d_out || S <= 0 || pose_stride < 3) return SLAM2D_E_BADARG;
+    if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_TOOLARGE;
+    if (!lidar->spoke_band || !lidar->spoke_cells || !lidar->spoke_r || !lidar->lut_xs || lidar->num_bands < 1 || lidar->lut_w > 65535)
+        return SLAM2D_E_BADARG;
+    const int groups = cdiv(lidar->beams, MAPS_BEAMS);
+    if ((long long)S * groups > 0x7fffffffll) return SLAM2D_E_TOOLARGE;
+    k_occ_extent<<<S * groups, 64 * MAPS_BEAMS, 0, (hipStream_t)stream>>>(*lidar, S, groups, d_pose, pose_stride, d_ranges, d_out);
+    return launch_status();
+}
+
+int slam2d_map_scans(const Slam2dLidar* lidar, const Slam2dMap* d_map, int32_t S, const double* d_pose, int32_t pose_stride,
+                     const double* d_ranges, const Slam2dBeamPlan* d_plan, const uint16_t* d_lut_bin, const double* d_lut_r,
+                     uint32_t* d_flags, void* stream) {
+    if (!lidar || !d_map || !d_pose || !d_ranges || !d_plan || !d_lut_bin || !d_lut_r || !d_flags || S <= 0 || pose_stride < 3)
+        return SLAM2D_E_BADARG;
+    if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_TOOLARGE;
+    if (!lidar->spoke_band || !lidar->spoke_cells || !lidar->spoke_r || !lidar->lut_xs || lidar->num_bands < 1 || lidar->lut_w > 65535 ||
+        lidar->lut_w < 2)
+        return SLAM2D_E_BADARG;
+    const int groups = cdiv(lidar->beams, MAPS_BEAMS);
+    if ((long long)S * groups > 0x7fffffffll) return SLAM2D_E_TOOLARGE;
+    k_map_scans<<<S * groups, 64 * MAPS_BEAMS, 0, (hipStream_t)stream>>>(*lidar, d_map, S, groups, d_pose, pose_stride, d_ranges, d_plan, d_lut_bin,
+                                                        d_lut_r, d_flags);
+    return launch_status();
 }
 
 int slam2d_grid_update_weights(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t P, const double* d_pose,

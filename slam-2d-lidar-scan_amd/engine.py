@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Slam2dFrame, Slam2dLevel, Slam2dLidar, Slam2dMap, Slam2dMatch, Slam2dPartial, check
+from ._lib import Slam2dBeamPlan, Slam2dFrame, Slam2dLevel, Slam2dLidar, Slam2dMap, Slam2dMatch, Slam2dPartial, check
 
 MATCH_DOUBLES = C.sizeof(Slam2dMatch) // 8      # stride of a Slam2dMatch array viewed as double*
 _MATCH_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("theta", "f8"), ("confidence", "f8"),
@@ -25,7 +25,10 @@ _MATCH_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("theta", "f8"), ("confidence
 _FRAME_DTYPE = np.dtype([("xlo", "f8"), ("ylo", "f8"), ("xhi", "f8"), ("yhi", "f8"), ("cx", "f8"), ("cy", "f8"),
                          ("field_min", "f8"), ("fh", "i4"), ("fw", "i4"), ("mx0", "i4"), ("mx1", "i4"),
                          ("my0", "i4"), ("my1", "i4"), ("redo", "i4"), ("min_known", "i4"), ("field_max", "f8")])
+PLAN_DTYPE = np.dtype([("lim_x0", "f8"), ("lim_y0", "f8"), ("dc", "i4"), ("dr", "i4"), ("ac", "i4"), ("ar", "i4"),
+                       ("cols", "i4"), ("rows", "i4")])                  # Slam2dBeamPlan
 assert _MATCH_DTYPE.itemsize == C.sizeof(Slam2dMatch) and _FRAME_DTYPE.itemsize == C.sizeof(Slam2dFrame)
+assert PLAN_DTYPE.itemsize == C.sizeof(Slam2dBeamPlan)
 
 
 def require_gpu(device):
@@ -318,6 +321,88 @@ class LidarModel:
         rec[:, 2] = np.concatenate((np.cumsum(rec[::-1, 0])[::-1][1:], [0]))
         rec[:, 3] = np.concatenate((np.cumsum(rec[::-1, 1])[::-1][1:], [0]))
         return rec
+
+    # -- batched counterpart of grow_for_update: many scans at given poses into one map (slam2d_map_scans) --
+    def occ_extents_host(self, poses, ranges):
+        """NumPy twin of slam2d_occ_extent (tests): [S, beams, 4] = (min x, max x, min y, max y) of each beam's occupied
+        points x + xAtSpokeDir[occ], y + yAtSpokeDir[occ] (:142-147), +-inf where a beam has none."""
+        W, xs = self.width, self.xs
+        out = np.empty((len(poses), self.beams, 4))
+        out[:] = (np.inf, -np.inf, np.inf, -np.inf)
+        for s, ((x, y, theta), rng) in enumerate(zip(poses, ranges)):
+            for i, c, _, occ in self.beam_cells(theta, np.asarray(rng, dtype=np.float64)):
+                if occ.any():
+                    px, py = x + xs[c[occ] % W], y + xs[c[occ] // W]
+                    out[s, i] = (px.min(), px.max(), py.min(), py.max())
+        return out
+
+    def window_inside(self, m, x, y):
+        """The scan's +-R window lies inside map ``m``: none of its cells can make the map grow or index outside it."""
+        R = self.max_range
+        return not (x - R < m.lim_x[0] or x + R > m.lim_x[1] or y - R < m.lim_y[0] or y + R > m.lim_y[1])
+
+    def plan_scans(self, m, poses, extents):
+        """The reference's per-beam growth (:144-147) replayed over a batch of scans on MapState ``m`` (grown on the host
+        with deferred_growth, materialised once), from the occupied extents of every beam (slam2d_occ_extent; None: every
+        window lies inside the map).  Returns (plan [S, beams] PLAN_DTYPE for slam2d_map_scans, inside [S] bool: the scan's
+        window lay inside the map when it came, planes [S] int: distinct write mappings of the scan).  A scan whose window
+        lies inside the map cannot grow it and skips the per-beam loop, and so do the beams of any scan before the first
+        one whose occupied points leave the map."""
+        S, B, unit = len(poses), self.beams, self.unit
+        plan = np.zeros((S, B), dtype=PLAN_DTYPE)
+        inside = np.zeros(S, dtype=bool)
+        planes = np.ones(S, dtype=np.int64)
+        with m.deferred_growth():
+            for s in range(S):
+                x, y = float(poses[s][0]), float(poses[s][1])
+                if self.window_inside(m, x, y):
+                    inside[s] = True
+                    p = plan[s]
+                    p["lim_x0"], p["lim_y0"], p["cols"], p["rows"] = m.lim_x[0], m.lim_y[0], m.cols, m.rows
+                    continue
+                if extents is None:
+                    raise ValueError("plan_scans: a window leaves the map and no extents were given")
+                e = extents[s]
+                rec = plan[s]
+                # beams before the first one whose occupied points leave the map cannot grow it (+-inf: no occupied cell)
+                leave = np.flatnonzero((e[:, 0] < m.lim_x[0]) | (e[:, 1] > m.lim_x[1]) | (e[:, 2] < m.lim_y[0]) | (e[:, 3] > m.lim_y[1]))
+                if leave.size == 0:
+                    rec["lim_x0"], rec["lim_y0"], rec["cols"], rec["rows"] = m.lim_x[0], m.lim_y[0], m.cols, m.rows
+                    continue
+                b0 = int(leave[0])
+                rec[:b0]["lim_x0"], rec[:b0]["lim_y0"], rec[:b0]["cols"], rec[:b0]["rows"] = m.lim_x[0], m.lim_y[0], m.cols, m.rows
+                for b in range(b0, B):
+                    lx, ly = m.lim_x[0], m.lim_y[0]
+                    dc = dr = 0
+                    if e[b, 0] < lx or e[b, 1] > m.lim_x[1] or e[b, 2] < ly or e[b, 3] > m.lim_y[1]:   # checkAndExapndOG (:147)
+                        before = len(m.growth_log)
+                        dc, dr = m.ensure_contains(e[b, 0:2], e[b, 2:4], unit)
+                        planes[s] += 2 * (len(m.growth_log) != before)      # (its own mapping + the one after it)
+                    rec[b] = (lx, ly, dc, dr, 0, 0, m.cols, m.rows)
+        flat = plan.reshape(-1)
+        for own, later in (("dc", "ac"), ("dr", "ar")):
+            v = flat[own].astype(np.int64)
+            tail = np.cumsum(v[::-1])[::-1]                  # shifts of this beam and every later one
+            flat[later] = tail - v
+        return plan, inside, planes
+
+    def scan_count_bound(self, inside, planes):
+        """Upper bound of what one scan of slam2d_map_scans adds to one map element's `total`: every statement adds at most
+        once per element (1 empty, 2 occupied, at most 3 per beam).  One write mapping (window column -> element) reaches an
+        element from at most 2 stale values per axis (a, a - cols: the wrap) of at most 2 window columns each (the window
+        step lies in [unit, 2 unit)): 16 cells, 2 each; with the window inside the map there is no wrap: 4 cells, 8.  A scan
+        that grows the map has at most two more mappings per growing beam (the beam's own: old limits, new shape; the
+        beams after it), and never more than 3 per beam."""
+        B = self.beams
+        return np.where(inside, 8, np.minimum(3 * B, 32 * np.asarray(planes)))
+
+    def lut_images(self, device):
+        """Spoke bin (uint16, as int16) and radius of every window cell on ``device`` (the statement membership test of
+        slam2d_map_scans), built once per device."""
+        key = "img:" + str(device)
+        if key not in self._dev:
+            self._dev[key] = (_dev(self.bin.view(np.int16), device), _dev(self.r, device))
+        return self._dev[key]
 
     def on(self, device):
         """Device copies + the C struct (kept alive with the tensors)."""

@@ -7,14 +7,17 @@ it unchanged.  ``occupancyGridVisited`` / ``occupancyGridTotal`` are properties 
 download the counts as float64 NumPy arrays (the reference stores float64 arrays).
 """
 import copy
+import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
-from .engine import MATCH_DOUBLES, LidarModel, MapState, ParticleEngine, pinned_stream, require_gpu
+from .engine import MATCH_DOUBLES, LidarModel, MapState, ParticleEngine, _ptr, _stream as engine_stream, pinned_stream, require_gpu
 
 DEFAULT_DEVICE = "cuda:0"
+MAP_SCANS_CHUNK = 1024      # scans per slam2d_map_scans launch in update_many
+HALF_CELL_TOL = 1e-6        # a pose this close to a half cell goes through slam2d_map_scans
 
 
 class OccupancyGrid:
@@ -118,11 +121,26 @@ class OccupancyGrid:
             self.version += 1
         return shifts
 
+    def _needs_exact(self, x, y):
+        """Where k_grid_update's one-writer-per-cell premise fails: a pose within HALF_CELL_TOL of a half cell on either axis
+        (two adjacent window columns / rows round to one map index), or a window step that is not the map unit."""
+        unit = self.unitGridSize
+        if self.lidar.xs_step() != unit:
+            return True
+        for v in ((x - self.map.lim_x[0]) / unit, (y - self.map.lim_y[0]) / unit):
+            if abs(abs(v - np.floor(v)) - 0.5) < HALF_CELL_TOL:
+                return True
+        return False
+
     def updateOccupancyGrid(self, reading, dTheta=0, update=True):
         x, y, theta = reading['x'], reading['y'], reading['theta'] + dTheta
         rng = np.asarray(reading['range'], dtype=np.float64)
         if not update:
             return self._update_points(x, y, theta, rng)
+        if self._needs_exact(x, y):
+            self._last_match = None
+            self._map_scans(np.array([[x, y, theta]], dtype=np.float64), rng[None, :])
+            return
         R = self.lidarMaxRange
         m = self.map
         shifts = None
@@ -155,6 +173,57 @@ class OccupancyGrid:
             io["ev"].record()
             eng.grid_update(io["d"][0:3], 3, io["d"][3:], None)
         self._update_pending = True
+
+    def update_many(self, readings):
+        """``for r in readings: self.updateOccupancyGrid(r)`` -- counts, mapXLim / mapYLim, map.growth_log and faults -- in
+        one slam2d_map_scans launch per MAP_SCANS_CHUNK scans (+ one slam2d_occ_extent launch per chunk whose windows leave
+        the map).  Synchronous: raises on a fault the update flagged."""
+        readings = list(readings)
+        if not readings:
+            return
+        B = self.numSamplesPerRev
+        poses = np.array([[r['x'], r['y'], r['theta']] for r in readings], dtype=np.float64).reshape(-1, 3)
+        ranges = np.array([np.asarray(r['range'], dtype=np.float64) for r in readings]).reshape(len(readings), -1)
+        if ranges.shape[1] != B:
+            raise ValueError(f"every reading needs {B} ranges")
+        self._last_match = None
+        for a in range(0, len(readings), MAP_SCANS_CHUNK):
+            self._map_scans(poses[a:a + MAP_SCANS_CHUNK], ranges[a:a + MAP_SCANS_CHUNK])
+
+    def _map_scans(self, poses, ranges):
+        """S scans into this grid with the reference's exact semantics (slam2d_map_scans), growth included."""
+        self.flush()                                                # (an earlier update's fault is raised first)
+        eng = self.engine()
+        m, lid, S = self.map, self.lidar, len(poses)
+        io = eng.to_device(np.concatenate((poses.reshape(-1), ranges.reshape(-1))))
+        d_pose, d_rng = io[:3 * S], io[3 * S:]
+        extents = None
+        if not all(lid.window_inside(m, float(x), float(y)) for x, y in poses[:, :2]):
+            d_ext = torch.empty((S, lid.beams, 4), dtype=torch.float64, device=self.device)
+            with pinned_stream():
+                _lib.check(_lib.lib().slam2d_occ_extent(C.byref(eng.lidar_c), S, _ptr(d_pose), 3, _ptr(d_rng), _ptr(d_ext),
+                                                        engine_stream()), "slam2d_occ_extent")
+            extents = d_ext.cpu().numpy()
+        before = len(m.growth_log)
+        plan, inside, planes = lid.plan_scans(m, poses, extents)
+        if len(m.growth_log) != before:
+            self.version += 1
+        eng.sync_bounds()
+        bound = int(lid.scan_count_bound(inside, planes).sum())
+        if not m.wide and m.count_bound + bound > _lib.COUNT_LIMIT:
+            m.promote()                                             # (a 16-bit total must never carry into visited)
+        eng = self.engine()
+        eng.refresh_bits()                                          # (fresh descriptors after a growth or a promotion)
+        bins, radii = lid.lut_images(self.device)
+        d_plan = torch.from_numpy(plan.reshape(-1).view(np.uint8)).to(self.device)
+        with pinned_stream():
+            _lib.check(_lib.lib().slam2d_map_scans(C.byref(eng.lidar_c), _ptr(eng.d_maps), S, _ptr(d_pose), 3, _ptr(d_rng),
+                                                   _ptr(d_plan), _ptr(bins), _ptr(radii), _ptr(eng.flags), engine_stream()),
+                       "slam2d_map_scans")
+        m.count_bound += bound
+        m.bits_valid = False
+        eng.refresh_bits()
+        eng.take_flags()                                            # (synchronises: the uploads outlive the kernels)
 
     def _update_io(self, eng, beams):
         io = getattr(eng, "_update_io", None)
