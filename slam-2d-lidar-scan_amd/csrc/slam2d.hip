@@ -933,14 +933,14 @@ __global__ __launch_bounds__(TRIAGE_THREADS) void k_tile_triage(Slam2dLevel lv, 
     for (int b = wave; b < nfill; b += TRIAGE_THREADS / 64) fill_tile(lv, p, fill_s[b], lane, c);
 }
 
-// Blur of the work list: gridDim.x one-wave blocks per particle walk that particle's active tiles.
+// Blur of the work list: bpp one-wave blocks per particle walk that particle's active tiles.
 #ifndef BLUR_MIN_WAVES
 #define BLUR_MIN_WAVES 1
 #endif
-// bpp > 0 (round 4): a 1-D grid in which block b runs on XCD b % 8 and all blocks of particle p on XCD p % 8, like the sweep's
+// The grid is 1-D (round 4): block b runs on XCD b % 8 and all blocks of particle p on XCD p % 8, like the sweep's
 // and the update's -- x-adjacent tiles share the 128-byte lines of their occupancy halo (8 tiles wide), and with the blocks of a
 // particle dealt round the XCDs by blockIdx.x every XCD's L2 fetched its own copy of those lines (round 3: 34 MB of HBM
-// traffic per 32-particle launch for 6.9 MB processed, L2 hit rate 56 %).  bpp == 0: the (blocks, P) grid of rounds 1-3.
+// traffic per 32-particle launch for 6.9 MB processed, L2 hit rate 56 % with the (blocks, P) grid of rounds 1-3).
 // tail != 0 (round 4: levels without bounds, where that was all k_blur_check_redo was launched for): the minimum check of a frame
 // WITHOUT a free tile -- rare: then every tile was listed and blurred against the analytic floor -- is done by the last of the
 // particle's blur blocks to finish (arrival counter lv.sync[p][1]; plain stores + agent release before the ticket, agent acquire
@@ -964,17 +964,14 @@ __device__ __forceinline__ void blur_check_tail(const Slam2dLevel& lv, BlurLds<R
 template <int RAD>
 __global__ __launch_bounds__(BLUR_THREADS, BLUR_MIN_WAVES) void k_blur_clamp(Slam2dLevel lv, int P, int bpp, uint32_t* flags, int tail) {
     __shared__ BlurLds<RAD> sm;
-    int p = blockIdx.y, first = blockIdx.x, stride = gridDim.x;
-    if (bpp > 0) {
-        const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-        p = (slot / bpp) * 8 + xcd; first = slot % bpp; stride = bpp;
-        if (p >= P) return;
-    }
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int p = (slot / bpp) * 8 + xcd, first = slot % bpp;
+    if (p >= P) return;
     const int n = lv.tilecount[2 * p];
     if (first >= n) return;
     const Slam2dFrame fr = lv.frames[p];
     const int* list = lv.tilelist + (size_t)p * 2 * lv.tmax * lv.tmax;
-    for (int b = first; b < n; b += stride) {
+    for (int b = first; b < n; b += bpp) {
         const int t = list[b];
         blur_tile<RAD>(lv, sm, p, fr, t / lv.tmax, t % lv.tmax, 0, false);
     }
@@ -984,7 +981,7 @@ __global__ __launch_bounds__(BLUR_THREADS, BLUR_MIN_WAVES) void k_blur_clamp(Sla
         unsigned ticket = 0u;
         if (threadIdx.x == 0) ticket = __hip_atomic_fetch_add(&lv.sync[p * SLAM2D_SYNC_WORDS + 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
-        if (ticket != (unsigned)(min(n, stride) - 1)) return;                   // (blocks of this particle that had a tile)
+        if (ticket != (unsigned)(min(n, bpp) - 1)) return;                   // (blocks of this particle that had a tile)
         if (threadIdx.x == 0) __hip_atomic_store(&lv.sync[p * SLAM2D_SYNC_WORDS + 1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         blur_check_tail<RAD>(lv, sm, p, fr, flags);
@@ -994,6 +991,7 @@ __global__ __launch_bounds__(BLUR_THREADS, BLUR_MIN_WAVES) void k_blur_clamp(Sla
 #ifndef GMIN2_ROWWISE
 #define GMIN2_ROWWISE 1
 #endif
+#define GMIN2_BLOCKS 16              // blocks per particle of k_blur_check_redo where it derives gmin2
 // gmin2 (branch and bound): element [Y][X] = min(gmin[Y..Y+1][X..X+1]) >> 12.  Blocks beyond the buffer are clamped
 // (duplicates only).
 __device__ __forceinline__ void gmin2_entry(const Slam2dLevel& lv, const uint32_t* __restrict__ G, uint32_t* __restrict__ G2,
@@ -1334,29 +1332,24 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
     int* cnt_s = ep_lds + 2 * hsize;
     for (int i = tid; i < hsize; i += NT) { hkey[i] = INT_MAX; hown[i] = INT_MAX; }
     // tile marking scratch: the patch of a beam covers tiles [tx0, tx0 + n + cx] x [ty0, ty0 + n + cy] with cx, cy in {0, 1}
-    // (n = (lead + span) / 16), so a beam sets ONE bit -- its corner tile, in the bitmap of its class (cy, cx) -- and the
+    // (n = 2 ncell / 16), so a beam sets ONE bit -- its corner tile, in the bitmap of its class (cy, cx) -- and the
     // block dilates the four bitmaps afterwards (rows padded to whole words).  Walking the tile rows per beam was half of
     // this kernel's time at 1081 beams.
     const int nneed = (lv.tmax * lv.tmax + 31) >> 5;
     const int wp = (lv.tmax + 31) >> 5;                    // words per tile row
-    const bool lds_mark = mark != 0;                       // (tmax^2 <= 28000, check_field_args: the scratch is <= 28 KB)
     uint32_t* corner_s = reinterpret_cast<uint32_t*>(ep_lds + 2 * hsize + 32);       // [2 cy][2 cx][tmax][wp]
     uint32_t* hd_s = corner_s + 4 * lv.tmax * wp;                                   // [2 cy][tmax][wp] after the horizontal pass
     uint32_t* lin_s = hd_s + 2 * lv.tmax * wp;                                      // [nneed] the block's bitmap (bit = ty * tmax + tx)
     uint32_t* const need_g = mark ? need_slice(lv, p, grp, nneed) : nullptr;
-    if (lds_mark) for (int i = tid; i < 6 * lv.tmax * wp + nneed; i += NT) corner_s[i] = 0u;
-    // branch and bound: gmin2 summarises the aligned 8x8 blocks around the 4x4 windows of the pose tiles, which
-    // reach from 3 cells before the patch to 4 * ceil(nx / 4) + 3 cells after its corner
-    // (two-level bounds: 8x8-pose tiles, 3x3 blocks: up to 8 * ceil(nx / 8) + 3)
-    // mark == 2 (round 4): only the cells the POSES read, (2 ncell + 1)^2 at the patch, as without bounds.  A block minimum taken
+    if (mark) for (int i = tid; i < 6 * lv.tmax * wp + nneed; i += NT) corner_s[i] = 0u;   // (tmax^2 <= 28000, check_field_args: <= 28 KB)
+    // Branch and bound: gmin2 summarises the aligned 8x8 blocks around the 4x4 windows of the pose tiles, which reach from 3 cells
+    // before the patch to 4 * ceil(nx / 4) + 3 cells after its corner (two-level bounds: up to 8 * ceil(nx / 8) + 3).  Still only
+    // the cells the POSES read are marked (round 4), (2 ncell + 1)^2 at the patch, as without bounds.  A block minimum taken
     // partly over cells of tiles that were not rebuilt is a minimum over MORE values than the poses can read: never larger than
     // the true one, so the bound it enters stays an upper bound of the scores -- only looser where a pose tile hangs over the
     // window's edge -- and whatever is scored exactly reads needed cells only.
-    const bool wide_need = lv.bnb && mark != 2;
-    const int lead = wide_need ? 3 : 0;
-    const int span = !wide_need ? 2 * lv.ncell : lv.bnb == 2 ? 8 * ((2 * lv.ncell + 8) >> 3) + 3 : 4 * ((2 * lv.ncell + 4) >> 2) + 3;
-    const int ntl = (lead + span) >> BLUR_SHIFT;
     const int nc = lv.ncell;
+    const int span = 2 * nc, ntl = span >> BLUR_SHIFT;
     const int per = NT == 256 ? (B + 255) / 256 : 1;       // beams per thread (5 at 1081 beams -- rounding the beams up to a power of
     //                                                        two first made it 8: three fully masked passes through every loop below,
     //                                                        a third of the kernel's vector instructions), interleaved: beam = q * NT + tid, so that a
@@ -1426,17 +1419,13 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
         atomicMin(&hown[h], q * NT + tid);
         if (mark) {                                        // tiles of the (2 nc + 1)^2 patch at (x0, y0)
             const int y0 = key[q] >> 16, x0 = key[q] & 0xFFFF;
-            // (a patch clipped by the field's low edge keeps its full extent: at most one tile row / column too many)
-            const int xa = max(x0 - lead, 0), ya = max(y0 - lead, 0);
-            if (lds_mark) {
-                const int tx0 = xa >> BLUR_SHIFT, ty0 = ya >> BLUR_SHIFT;
-                const int cx = (((xa & (BLUR_TILE - 1)) + lead + span) >> BLUR_SHIFT) - ntl;
-                const int cy = (((ya & (BLUR_TILE - 1)) + lead + span) >> BLUR_SHIFT) - ntl;
-                uint32_t* w = corner_s + ((cy * 2 + cx) * lv.tmax + ty0) * wp + (tx0 >> 5);
-                const uint32_t m = 1u << (tx0 & 31);
-                // neighbouring beams share the corner tile: a plain read first, the atomic only for a new bit
-                if (!(*w & m)) atomicOr(w, m);
-            }
+            const int tx0 = x0 >> BLUR_SHIFT, ty0 = y0 >> BLUR_SHIFT;
+            const int cx = (((x0 & (BLUR_TILE - 1)) + span) >> BLUR_SHIFT) - ntl;
+            const int cy = (((y0 & (BLUR_TILE - 1)) + span) >> BLUR_SHIFT) - ntl;
+            uint32_t* w = corner_s + ((cy * 2 + cx) * lv.tmax + ty0) * wp + (tx0 >> 5);
+            const uint32_t m = 1u << (tx0 & 31);
+            // neighbouring beams share the corner tile: a plain read first, the atomic only for a new bit
+            if (!(*w & m)) atomicOr(w, m);
         }
     }
     __syncthreads();
@@ -1494,7 +1483,7 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
     }
   }
     if (bad) atomicOr(&flags[p], SLAM2D_F_ENDPOINT_OUTSIDE);
-    if (!lds_mark) return;                                 // (block-uniform)
+    if (!mark) return;                                     // (block-uniform)
     __syncthreads();                                       // the corner bits of the block's angles are all set
     {
         const int nitem = lv.tmax * wp;
@@ -1536,7 +1525,8 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
 // K1c  pose-cube sweep                              (Utils/ScanMatcher_OGBased.py:116-132)
 //      score[theta][dy][dx] = sum_k field[cy_k + dy][cx_k + dx] + rv + thetaWeight
 //
-//      One BLOCK scores 64*RQ slots of 4 consecutive dx of one (particle, theta): lanes run along the
+//      One BLOCK scores 64 slots of 4 consecutive dx of one (particle, theta), one slot per lane (two to four
+//      slots per lane measured slower in round 1, config 2: 132-134 us against 124 us): lanes run along the
 //      flattened (dy, dx/4) plane, so every gather of a wave is a few contiguous row segments of the
 //      fixed-point uint32 field; its 4 waves split the unique-cell list.  The list is wave-uniform: it is
 //      read with scalar loads and the field through a buffer resource as (per-lane constant VGPR offset) +
@@ -1594,9 +1584,9 @@ __device__ __forceinline__ Best wave_best_ordered(const Best me) {
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // A "slot" is 4 consecutive dx of one dy row (the last slot of a row is partly padding); one lane
-// scores RQ slots, i.e. each gather is one 16-byte buffer load -- a quarter of the vector-memory
+// scores one slot, i.e. each gather is one 16-byte buffer load -- a quarter of the vector-memory
 // instructions of a dword-per-lane sweep for the same bytes.
-// One BLOCK = 64*RQ slots of one (particle, theta); its 4 waves score the SAME slots against
+// One BLOCK = 64 slots of one (particle, theta); its 4 waves score the SAME slots against
 // interleaved quarters of the cell list (wave s takes cells s, s+4, ...), so four waves stream through
 // the same field rows at the same time -- one L1 working set per block (measured 124 -> 117 us; the
 // gathers run at L1 delivery rate, bypassing L1 costs 1.6x) -- and their exact integer partial sums
@@ -1608,6 +1598,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #ifndef SWEEP_DEPTH
 #define SWEEP_DEPTH 8
 #endif
+#define SWEEP_DEEP_MAX_BLOCKS 64     // blocks per particle up to which the launch is about one round of blocks (latency-bound): the deep loop
 // arg-max, confidence and matched pose of particle p from the sweep's partials (k_select<0> without the soft-max draw: the very
 // expressions and summation order), by ONE wave -- the sweep's last-arriving block of the particle (k_sweep, sel_out).  The
 // partials were published with write-through stores by other blocks: they are read past this CU's L1.
@@ -1659,17 +1650,17 @@ __device__ __forceinline__ void select_argmax_from_partials(const Slam2dLevel& l
     }
 }
 
-template <int RQ, int mode, bool SKIP>
-// (RQ = 1, whole cube, no skip test: 8 waves per SIMD -- 64 VGPRs instead of 66 -- hold the reference's fine level, 30 blocks per
+template <int mode, bool SKIP>
+// (whole cube, no skip test: 8 waves per SIMD -- 64 VGPRs instead of 66 -- hold the reference's fine level, 30 blocks per
 // particle x 64 particles = 1 920 blocks of 4 waves, in ONE round of blocks instead of a full one and a sliver)
-__global__ __launch_bounds__(256, (RQ == 1 && mode == 0 && !SKIP) ? 8 : 1) void k_sweep(Slam2dLevel lv, int P, int chunks, int bpp, const double* __restrict__ sel_est = nullptr,
+__global__ __launch_bounds__(256, (mode == 0 && !SKIP) ? 8 : 1) void k_sweep(Slam2dLevel lv, int P, int chunks, int bpp, const double* __restrict__ sel_est = nullptr,
                                                int sel_estride = 0, Slam2dMatch* sel_out = nullptr, int deep = 0) {
-    // mode 0: the whole cube.  mode 1 (RQ = 1): only the slots of the prior's ring (lv.ring).  mode 2: the
+    // mode 0: the whole cube.  mode 1: only the slots of the prior's ring (lv.ring).  mode 2: the
     // whole cube, for the particles the ring pass could not settle (lv.prune_state[p] != 0) -- see write_priors.
-    // SKIP (RQ = 1): a wave-load whose whole patch (its 6-7 pose rows x all dx, at the cell) lies in tiles that
+    // SKIP: a wave-load whose whole patch (its 6-7 pose rows x all dx, at the cell) lies in tiles that
     // hold the free-space constant is not issued; the constant is added once per skipped cell at the end
     // (integer sums: exact).  ~29 % of the loads at config 2.
-    __shared__ unsigned long long part_s[3][WAVE * RQ * 4];
+    __shared__ unsigned long long part_s[3][WAVE * 4];
     __shared__ unsigned long long free_s[64];
     const int b = blockIdx.x;
     const int xcd = b & 7, slot = b >> 3;
@@ -1704,21 +1695,14 @@ __global__ __launch_bounds__(256, (RQ == 1 && mode == 0 && !SKIP) ? 8 : 1) void 
     const int dbg0 = lv.fine ? 44 : 32;
     auto sweep_chunk = [&](const int ch) {
     DBG_CLOCK(dbg0, p == 0 && it == 0 && ch == 0);
-    const int u0 = ch * (WAVE * RQ) + lane;
-    int off[RQ], q0[RQ], nv[RQ];          // byte offset, first pose index, valid poses (0..4) of each slot
-    unsigned lo[RQ][4], hi[RQ][4];        // exact 64-bit integer sums as 32-bit halves
-#pragma unroll
-    for (int r = 0; r < RQ; ++r) {
-        int u = u0 + r * WAVE;
-        if (mode == 1) u = u < nring ? lv.ring[1 + u] : nslot;
-        const int uu = u < nslot ? u : 0;
-        const int iy = uu / nq, dx = (uu - iy * nq) * 4;
-        off[r] = (iy * lv.fpitch + dx) * 4;
-        q0[r] = iy * nx + dx;
-        nv[r] = u < nslot ? min(4, nx - dx) : 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { lo[r][e] = 0u; hi[r][e] = 0u; }
-    }
+    int u = ch * WAVE + lane;             // the lane's slot
+    if (mode == 1) u = u < nring ? lv.ring[1 + u] : nslot;
+    const int uu = u < nslot ? u : 0;
+    const int iy = uu / nq, dx = (uu - iy * nq) * 4;
+    const int off = (iy * lv.fpitch + dx) * 4;            // byte offset, first pose index, valid poses (0..4) of the slot
+    const int q0 = iy * nx + dx;
+    const int nv = u < nslot ? min(4, nx - dx) : 0;
+    unsigned lo[4] = {0u, 0u, 0u, 0u}, hi[4] = {0u, 0u, 0u, 0u};      // exact 64-bit integer sums as 32-bit halves
     unsigned nfree = 0u;
     if constexpr (SKIP) {
         // This wave's cells (k = wave, wave + 4, ...) 64 at a time, one per lane; the loop then pops cells off a
@@ -1758,18 +1742,18 @@ __global__ __launch_bounds__(256, (RQ == 1 && mode == 0 && !SKIP) ? 8 : 1) void 
                 }
                 u32x4 v[SWEEP_DEPTH];
 #pragma unroll
-                for (int i = 0; i < SWEEP_DEPTH; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[0], c[i], 0);
+                for (int i = 0; i < SWEEP_DEPTH; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, c[i], 0);
 #pragma unroll
                 for (int i = 0; i < SWEEP_DEPTH; ++i)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const unsigned s2 = lo[0][e] + v[i][e];
-                        hi[0][e] += s2 < v[i][e] ? 1u : 0u;
-                        lo[0][e] = s2;
+                        const unsigned s2 = lo[e] + v[i][e];
+                        hi[e] += s2 < v[i][e] ? 1u : 0u;
+                        lo[e] = s2;
                     }
             }
         }
-    } else if (RQ == 1 && deep) {
+    } else if (deep) {
         // Round 4: a level whose launch is ONE round of blocks (the reference's 11 x 11 fine cube: 30 blocks per particle) is
         // bound by the latency of this loop, not by the gathers' throughput -- with two loads in flight a wave's ~40 cells were
         // ~20 round trips.  The wave's cells come in one vector load (a lane each), v_readlane hands them to the loop as scalar
@@ -1784,14 +1768,14 @@ __global__ __launch_bounds__(256, (RQ == 1 && mode == 0 && !SKIP) ? 8 : 1) void 
                 for (int i = 0; i < SWEEP_DEPTH; ++i) c[i] = __builtin_amdgcn_readlane(boff, min(j0 + i, WAVE - 1));
                 u32x4 v[SWEEP_DEPTH];
 #pragma unroll
-                for (int i = 0; i < SWEEP_DEPTH; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[0], j0 + i < n ? c[i] : 0x7ffffff0, 0);
+                for (int i = 0; i < SWEEP_DEPTH; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, j0 + i < n ? c[i] : 0x7ffffff0, 0);
 #pragma unroll
                 for (int i = 0; i < SWEEP_DEPTH; ++i)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const unsigned s2 = lo[0][e] + v[i][e];
-                        hi[0][e] += s2 < v[i][e] ? 1u : 0u;
-                        lo[0][e] = s2;
+                        const unsigned s2 = lo[e] + v[i][e];
+                        hi[e] += s2 < v[i][e] ? 1u : 0u;
+                        lo[e] = s2;
                     }
             }
         }
@@ -1799,87 +1783,70 @@ __global__ __launch_bounds__(256, (RQ == 1 && mode == 0 && !SKIP) ? 8 : 1) void 
 #pragma unroll 2
     for (int k = wave; k < K; k += 4) {
         const int cell = cl[k] * 4;
-        u32x4 v[RQ];
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, cell, 0);
 #pragma unroll
-        for (int r = 0; r < RQ; ++r) v[r] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[r], cell, 0);
-#pragma unroll
-        for (int r = 0; r < RQ; ++r)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned s = lo[r][e] + v[r][e];
-                hi[r][e] += s < v[r][e] ? 1u : 0u;
-                lo[r][e] = s;
-            }
+        for (int e = 0; e < 4; ++e) {
+            const unsigned s = lo[e] + v[e];
+            hi[e] += s < v[e] ? 1u : 0u;
+            lo[e] = s;
+        }
     }
     }
     if constexpr (SKIP) {                                  // the skipped cells: each adds the free-space cost
         const double fv = lv.floor_value;
         const unsigned long long add = (unsigned long long)nfree * (fv > 0.5 * fv ? 0u : (uint32_t)rint(-fv * lv.cost_scale));
 #pragma unroll
-        for (int r = 0; r < RQ; ++r)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned long long t = (((unsigned long long)hi[r][e] << 32) | lo[r][e]) + add;
-                hi[r][e] = (unsigned)(t >> 32); lo[r][e] = (unsigned)t;
-            }
+        for (int e = 0; e < 4; ++e) {
+            const unsigned long long t = (((unsigned long long)hi[e] << 32) | lo[e]) + add;
+            hi[e] = (unsigned)(t >> 32); lo[e] = (unsigned)t;
+        }
     }
     DBG_CLOCK(dbg0 + 1, p == 0 && it == 0 && ch == 0);
     if (wave > 0) {
 #pragma unroll
-        for (int r = 0; r < RQ; ++r)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) part_s[wave - 1][(r * 4 + e) * WAVE + lane] = ((unsigned long long)hi[r][e] << 32) | lo[r][e];
+        for (int e = 0; e < 4; ++e) part_s[wave - 1][e * WAVE + lane] = ((unsigned long long)hi[e] << 32) | lo[e];
     }
     __syncthreads();
     DBG_CLOCK(dbg0 + 2, p == 0 && it == 0 && ch == 0);
     if (wave > 0) return;
     {
 #pragma unroll
-    for (int r = 0; r < RQ; ++r)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int ix = (r * 4 + e) * WAVE + lane;
-            const unsigned long long tot = (((unsigned long long)hi[r][e] << 32) | lo[r][e]) + part_s[0][ix] + part_s[1][ix] + part_s[2][ix];
-            hi[r][e] = (unsigned)(tot >> 32); lo[r][e] = (unsigned)tot;
-        }
+    for (int e = 0; e < 4; ++e) {
+        const int ix = e * WAVE + lane;
+        const unsigned long long tot = (((unsigned long long)hi[e] << 32) | lo[e]) + part_s[0][ix] + part_s[1][ix] + part_s[2][ix];
+        hi[e] = (unsigned)(tot >> 32); lo[e] = (unsigned)tot;
+    }
     const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
     double* __restrict__ out = lv.cube + ((size_t)p * lv.ntheta + it) * npose;
     const double inv = 1.0 / lv.cost_scale;
-    double sc[RQ][4], prv[RQ][4], ptw[RQ][4];
+    double sc[4], prv[4], ptw[4];
     Best me{-INFINITY, INT_MAX, 0};
     // both prior planes of the lane's poses in one batch of loads (one round trip, not eight)
 #pragma unroll
-    for (int r = 0; r < RQ; ++r)
+    for (int e = 0; e < 4; ++e) {
+        const int q = min(q0 + e, npose - 1);
+        prv[e] = pr[q];
+        ptw[e] = pr[npose + q];
+    }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int q = min(q0[r] + e, npose - 1);
-            prv[r][e] = pr[q];
-            ptw[r][e] = pr[npose + q];
+    for (int e = 0; e < 4; ++e) {
+        sc[e] = -INFINITY;
+        if (e < nv) {
+            const int q = q0 + e;
+            const unsigned long long acc = ((unsigned long long)hi[e] << 32) | lo[e];
+            const double sum = -((double)acc * inv);                               // sum of probSP values
+            sc[e] = (sum + prv[e]) + ptw[e];                                       // :131
+            out[q] = sc[e];
+            Best cand{sc[e], it * npose + q, isnan(sc[e]) ? 1 : 0};
+            if (better(cand, me)) me = cand;
         }
-#pragma unroll
-    for (int r = 0; r < RQ; ++r)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            sc[r][e] = -INFINITY;
-            if (e < nv[r]) {
-                const int q = q0[r] + e;
-                const unsigned long long acc = ((unsigned long long)hi[r][e] << 32) | lo[r][e];
-                const double sum = -((double)acc * inv);                           // sum of probSP values
-                sc[r][e] = (sum + prv[r][e]) + ptw[r][e];                          // :131
-                out[q] = sc[r][e];
-                Best cand{sc[r][e], it * npose + q, isnan(sc[r][e]) ? 1 : 0};
-                if (better(cand, me)) me = cand;
-            }
-        }
+    }
     // per-wave reduction for k_select: max / argmax / sum exp(score - max)
-    if constexpr (RQ == 1) me = wave_best_ordered(me);     // lane = one slot: indices ascend with the lane
-    else me = wave_best(me);
+    me = wave_best_ordered(me);                            // lane = one slot: indices ascend with the lane
     double ex = 0.0;
 #pragma unroll
-    for (int r = 0; r < RQ; ++r)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (e < nv[r]) ex += exp(sc[r][e] - me.v);
+    for (int e = 0; e < 4; ++e)
+        if (e < nv) ex += exp(sc[e] - me.v);
     ex = wave_sum(ex);
     if (lane == 0) {
         Slam2dPartial pt;
@@ -2112,7 +2079,7 @@ __global__ __launch_bounds__(64 * ASEED_WAVES) void k_aseed(Slam2dLevel lv, int 
 //      one wave per particle, working on the per-wave partials of the sweep
 // ------------------------------------------------------------------------------------
 template <int mode>
-__global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, int RQ, const double* __restrict__ est,
+__global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const double* __restrict__ est,
                                                int estride, const double* __restrict__ uniform, Slam2dMatch* out) {
     // mode as in k_sweep.  In mode 1 only the first ceil(ring length / 64) chunks of every theta hold
     // partials; the partial of (theta it, chunk ch) sits at it * chunks + ch in every mode.
@@ -2195,9 +2162,9 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, int R
             }
             pick = __builtin_amdgcn_readlane(found, l2);
         } else {
-        // inside chunk wsel: it covers slots [ch*64*RQ, ...) = a contiguous pose range [qlo, qhi);
+        // inside chunk wsel: it covers slots [ch*64, ...) = a contiguous pose range [qlo, qhi);
         // lane l owns a contiguous run of `per2` poses of it
-        const int s0c = min(nslot, ch * WAVE * RQ), s1c = min(nslot, (ch + 1) * WAVE * RQ);
+        const int s0c = min(nslot, ch * WAVE), s1c = min(nslot, (ch + 1) * WAVE);
         const int qlo = (s0c / nq) * nx + min(nx, 4 * (s0c % nq));
         const int qhi = (s1c / nq) * nx + min(nx, 4 * (s1c % nq));
         const int per2 = (qhi - qlo + WAVE - 1) / WAVE;
@@ -2274,6 +2241,11 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 // row group holds the row's 4 sums over ALL the cells this wave walked (reduced over the 16 slices).
 #define EXACT_DEPTH 8
 #define SLAM2D_BEAM_TABLE_MIN 512   // beams from which k_frame_axis (with its per-particle beam-endpoint table) is worth its launch
+// ... and particles per launch from which it is (round 6): the merged launch makes every angle block evaluate the cos / sin of
+// all beams and every scatter block the frame; when the launch fills the machine that work costs more than the two launches
+// it saves (config 2: k_endpoints 57 -> 27 + 26 us at 128 particles per launch, the step 0.309 -> 0.305 ms; at 256 per launch
+// 0.580 -> 0.561; at 16 per launch the two launches cost 0.113 -> 0.123)
+#define SLAM2D_FRAME_KERNEL_MIN_P 128
 // byte offsets of the first NPRE cells of lane slice s (cells s, s + 16, ...), beyond-the-buffer where the list ends
 template <int NPRE>
 __device__ __forceinline__ void tile_prefetch(const int* __restrict__ cl, const int K, int (&pre)[NPRE]) {
@@ -4181,29 +4153,48 @@ __global__ void k_fill(uint32_t* cells, long long n, uint32_t value) {
 // ------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------
-template <int R>
 static void launch_sweep(const Slam2dLevel& lv, int P, int chunks, hipStream_t s, int mode = 0, const double* sel_est = nullptr,
                          int sel_estride = 0, Slam2dMatch* sel_out = nullptr) {
     const int bpp = lv.ntheta * cdiv(chunks, mode == 2 ? SWEEP_REST_CHUNKS : (mode == 0 ? SWEEP_MAIN_CHUNKS : 1));   // blocks per particle
     const unsigned grid = cdiv(P, 8) * 8 * bpp;
-    static const bool no_skip = [] { const char* e = getenv("SLAM2D_SWEEP_NOSKIP"); return e && atoi(e) == 1; }();
+    if (mode == 1) { k_sweep<1, false><<<grid, 256, 0, s>>>(lv, P, chunks, bpp); return; }
     // worth it for long cell lists (measured: 1081 beams -15 %, 180 beams +4 %: the vector prologue of the skip
     // loop costs more than 29 % fewer loads save when a wave has only ~43 cells)
-    const bool skip = R == 1 && sweep_skips(lv) && !no_skip;
-    if constexpr (R == 1) {
-        if (mode == 1) { k_sweep<1, 1, false><<<grid, 256, 0, s>>>(lv, P, chunks, bpp); return; }
-        if (skip) {
-            if (mode == 0) k_sweep<1, 0, true><<<grid, 256, 0, s>>>(lv, P, chunks, bpp, sel_est, sel_estride, sel_out);
-            else k_sweep<1, 2, true><<<grid, 256, 0, s>>>(lv, P, chunks, bpp);
-            return;
-        }
+    if (sweep_skips(lv)) {
+        if (mode == 0) k_sweep<0, true><<<grid, 256, 0, s>>>(lv, P, chunks, bpp, sel_est, sel_estride, sel_out);
+        else k_sweep<2, true><<<grid, 256, 0, s>>>(lv, P, chunks, bpp);
+        return;
     }
-    // deep (R == 1): SWEEP_DEPTH gathers in flight per wave; SLAM2D_SWEEP_DEEP = 0 never, 1 (default) where a particle has at most
-    // 64 blocks (the launch is about one round of blocks: latency-bound), 2 always
-    static const int deep_env = [] { const char* e = getenv("SLAM2D_SWEEP_DEEP"); return e ? atoi(e) : 1; }();
-    const int deep = R == 1 && (deep_env == 2 || (deep_env == 1 && bpp <= 64)) ? 1 : 0;
-    if (mode == 0) k_sweep<R, 0, false><<<grid, 256, 0, s>>>(lv, P, chunks, bpp, sel_est, sel_estride, sel_out, deep);
-    else if (mode == 2) k_sweep<R, 2, false><<<grid, 256, 0, s>>>(lv, P, chunks, bpp, nullptr, 0, nullptr, deep);
+    // deep: SWEEP_DEPTH gathers in flight per wave, where the launch is about one round of blocks
+    const int deep = bpp <= SWEEP_DEEP_MAX_BLOCKS ? 1 : 0;
+    if (mode == 0) k_sweep<0, false><<<grid, 256, 0, s>>>(lv, P, chunks, bpp, sel_est, sel_estride, sel_out, deep);
+    else k_sweep<2, false><<<grid, 256, 0, s>>>(lv, P, chunks, bpp, nullptr, 0, nullptr, deep);
+}
+
+// More dynamic LDS than the default limit for `kernel`: asked for once per device (`granted`: the kernel's own record; 160 KB
+// per CU on gfx950).  false: more than a CU has, or the device does not grant it -- the caller reports a clean error or falls
+// back instead of a failed launch.
+constexpr size_t DYN_LDS_MAX = 160 * 1024 - 512;
+static bool grant_dynamic_lds(const void* kernel, size_t (&granted)[64], size_t lds) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    size_t& allowed = granted[dev >= 0 && dev < 64 ? dev : 0];
+    if (allowed == 0) allowed = 64 * 1024;
+    if (lds <= allowed) return true;
+    if (lds > DYN_LDS_MAX || hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DYN_LDS_MAX) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    allowed = DYN_LDS_MAX;
+    return true;
+}
+// one instantiation of k_bound_lds: its LDS granted, then launched (false: not granted, nothing launched)
+template <int NSET, bool RLE>
+static bool launch_bound_lds_as(const Slam2dLevel& lv, int P, int bpp, int tpb, int nw, size_t lds, hipStream_t s) {
+    static size_t granted[64] = {};
+    if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_bound_lds<NSET, RLE>), granted, lds)) return false;
+    k_bound_lds<NSET, RLE><<<(unsigned)cdiv(P, 8) * 8 * bpp, WAVE * nw, lds, s>>>(lv, P, bpp, tpb);
+    return true;
 }
 
 extern "C" {
@@ -4286,36 +4277,19 @@ static int launch_field(const Slam2dLevel& lv, const Slam2dMap* d_maps, int P, u
     // Without bounds (no gmin2 to derive), without the sweep's free-tile masks and without the prior pruning (which reads the
     // field's maximum) k_blur_check_redo has ONE duty left: the minimum check of a frame without a free tile -- the blur's last
     // block does it (k_blur_clamp, tail).  One launch per level less: 2 x 6 us per scan at the reference's defaults.
-    // SLAM2D_FOLD_CHECK=0: the separate launch.
-    static const bool fold = [] { const char* e = getenv("SLAM2D_FOLD_CHECK"); return !e || atoi(e) != 0; }();
-    const bool folded = fold && lazy && !lv.bnb && !sweep_skips(lv) && !field_max_needed && lv.sync != nullptr;
+    const bool folded = lazy && !lv.bnb && !sweep_skips(lv) && !field_max_needed && lv.sync != nullptr;
     {
         const int kb = (lv.blur_radius + 7) >> FLAG_SHIFT;
         const int rw = (flag_pitch(lv) >> 4) + 1;
         const size_t lds = (size_t)((2 * ((((2 * lv.tmax + 2 * kb) * rw + 1) & ~1) + lv.tmax * (rw + 1)) + 15) & ~15) + ((ntile + 3) & ~3) + 4 * ((ntile + 31) / 32) + 2 * (size_t)ntile;
-        // more than the default dynamic LDS limit: ask once per device (160 KB per CU on gfx950); a device that does not grant it
-        // gets a clean error instead of a failed launch
-        static size_t lds_allowed[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        size_t& allowed = lds_allowed[dev >= 0 && dev < 64 ? dev : 0];
-        if (allowed == 0) allowed = 64 * 1024;
-        if (lds > allowed) {
-            const size_t want = 160 * 1024 - 512;
-            if (lds > want || hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_triage), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) != hipSuccess) {
-                (void)hipGetLastError();
-                return SLAM2D_E_TOOLARGE;
-            }
-            allowed = want;
-        }
+        static size_t granted[64] = {};
+        if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_tile_triage), granted, lds)) return SLAM2D_E_TOOLARGE;
         k_tile_triage<<<P, TRIAGE_THREADS, lds, s>>>(lv, lazy ? 1 : 0);
     }
     {
         StageScope prof(SLAM2D_STAGE_BLUR, s);
-        static const int blur_blocks = [] { const char* e = getenv("SLAM2D_BLUR_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : SLAM2D_BLUR_BLOCKS_PER_PARTICLE; }();
-        static const bool xcd_pin = [] { const char* e = getenv("SLAM2D_BLUR_XCD"); return !e || atoi(e) != 0; }();
-        const int bpp = xcd_pin ? min(ntile, blur_blocks) : 0;
-        const dim3 bgrid = xcd_pin ? dim3((unsigned)cdiv(P, 8) * 8 * bpp) : dim3(min(ntile, blur_blocks), P);
+        const int bpp = min(ntile, SLAM2D_BLUR_BLOCKS_PER_PARTICLE);
+        const unsigned bgrid = (unsigned)cdiv(P, 8) * 8 * bpp;
         const int tail = folded ? 1 : 0;
         switch (lv.blur_radius) {
             case 2: k_blur_clamp<2><<<bgrid, BLUR_THREADS, 0, s>>>(lv, P, bpp, d_flags, tail); break;
@@ -4325,11 +4299,8 @@ static int launch_field(const Slam2dLevel& lv, const Slam2dMap* d_maps, int P, u
         }
     }
     if (folded) return 0;                              // the minimum check rode in the blur's launch: nothing else to do at this level
-    // gmin2 only where a tile was written (SLAM2D_GMIN2_FULL=1: over the whole frame, as before round 3)
-    static const bool full = [] { const char* e = getenv("SLAM2D_GMIN2_FULL"); return e && atoi(e) == 1; }();
-    const int dirty = lazy && !full ? 1 : 0;
-    static const int dblocks = [] { const char* e = getenv("SLAM2D_GMIN2_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 16; }();
-    const dim3 cgrid(P, lv.bnb ? (dirty ? dblocks : 16) : 1);
+    const int dirty = lazy ? 1 : 0;                    // gmin2 only where a tile was written (the full build: over the whole frame)
+    const dim3 cgrid(P, lv.bnb ? GMIN2_BLOCKS : 1);
     switch (lv.blur_radius) {
         case 2: k_blur_check_redo<2><<<cgrid, 256, 0, s>>>(lv, d_flags, dirty); break;
         case 4: k_blur_check_redo<4><<<cgrid, 256, 0, s>>>(lv, d_flags, dirty); break;
@@ -4343,7 +4314,7 @@ static int launch_field(const Slam2dLevel& lv, const Slam2dMap* d_maps, int P, u
 static void launch_endpoints(const Slam2dLidar& lid, const Slam2dLevel& lv, int P, const double* d_est, int est_stride,
                              const double* d_ranges, double est_moving_dist, const double* d_psi_cs, uint32_t* d_flags,
                              bool mark, bool prune, hipStream_t s, bool beam_table = false,
-                             const Slam2dMap* own_frame_maps = nullptr, bool with_scatter = false) {
+                             const Slam2dMap* own_frame_maps = nullptr) {
     StageScope prof(SLAM2D_STAGE_ENDPOINTS, s);
     int n = 256;
     while (n < lid.beams) n <<= 1;
@@ -4353,104 +4324,75 @@ static void launch_endpoints(const Slam2dLidar& lid, const Slam2dLevel& lv, int 
     const int G = lv.ep_group > 0 ? lv.ep_group : 1;
     const int nt = lid.beams <= 192 ? 192 : 256;
     // round 4: only the tiles the poses read are marked, not the wider region the block minima of the bounds summarise (see
-    // k_endpoints, mark == 2: 13 % fewer needed tiles, 6 % fewer blurred ones at config 2, the same surviving pose tiles;
-    // SLAM2D_TIGHT_NEED=0 restores the wide marking)
-    static const int markv = [] { const char* e = getenv("SLAM2D_TIGHT_NEED"); return e && atoi(e) == 0 ? 1 : 2; }();
-    // with_scatter (needs own_frame_maps): the occupied-cell scatter as further blocks of this launch
+    // k_endpoints: 13 % fewer needed tiles, 6 % fewer blurred ones at config 2, the same surviving pose tiles)
+    // own_frame_maps: the frame's duties and the occupied-cell scatter as further blocks of this launch
+    const bool with_scatter = own_frame_maps != nullptr;
     const int sbx = with_scatter ? cdiv(cdiv(lv.wmax, 32) + 1, 64) : 0, sby = with_scatter ? cdiv(lv.wmax, (nt / 64) * SCATTER_ROLE_NR) : 0;
     if (with_scatter) ep_lds = ep_lds > (size_t)lv.wmax * sizeof(int32_t) ? ep_lds : (size_t)lv.wmax * sizeof(int32_t);
     const dim3 grid(cdiv(lv.ntheta, G) + (own_frame_maps ? 2 : 1) + sbx * sby, P);
     if (nt == 192)
         k_endpoints<192><<<grid, 192, ep_lds, s>>>(lid, lv, d_est, est_stride, d_ranges, d_flags, est_moving_dist, lv.fine ? nullptr : d_psi_cs,
-                                                   mark ? markv : 0, prune ? 1 : 0, beam_table && lv.beam_xy ? 1 : 0, own_frame_maps, sbx);
+                                                   mark ? 1 : 0, prune ? 1 : 0, beam_table && lv.beam_xy ? 1 : 0, own_frame_maps, sbx);
     else
         k_endpoints<256><<<grid, 256, ep_lds, s>>>(lid, lv, d_est, est_stride, d_ranges, d_flags, est_moving_dist, lv.fine ? nullptr : d_psi_cs,
-                                                   mark ? markv : 0, prune ? 1 : 0, beam_table && lv.beam_xy ? 1 : 0, own_frame_maps, sbx);
+                                                   mark ? 1 : 0, prune ? 1 : 0, beam_table && lv.beam_xy ? 1 : 0, own_frame_maps, sbx);
 }
 
 // cube sweep + selection
 // k_bound_lds where the level carries the byte image of the bounds (Slam2dLevel.gmin2b) and it fits the CU's LDS.
-// SLAM2D_BOUND_LDS=0: never.  A particle's angles are split over up to SLAM2D_BOUND_LDS_SPLIT blocks (each stages the image)
-// while the launch stays below SLAM2D_BOUND_LDS_BLOCKS blocks (128: measured at 16 / 64 / 128 / 256 particles per launch, four /
+// SLAM2D_BOUND_LDS=0: never.  A particle's angles are split over up to BOUND_LDS_MAX_SPLIT blocks (each stages the image)
+// while the launch stays below BOUND_LDS_BLOCKS blocks (128: measured at 16 / 64 / 128 / 256 particles per launch, four /
 // two / one / one block per particle): small launches need the CUs, large ones pay for every extra staging pass and barrier.
+#define BOUND_LDS_MAX_SPLIT 4
+#define BOUND_LDS_BLOCKS 128
+#define BOUND_LDS_BLOCKS_RLE 256     // long lists: an angle is 16 us of one wave (config 5's 64-particle launches, 139 angles, four blocks per particle)
 static bool launch_bound_lds(const Slam2dLevel& lv, int P, hipStream_t s) {
     static const int mode = [] { const char* e = getenv("SLAM2D_BOUND_LDS"); return e ? atoi(e) : -1; }();
-    static const int max_split = [] { const char* e = getenv("SLAM2D_BOUND_LDS_SPLIT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 4; }();
-    static const int want_blocks_env = [] { const char* e = getenv("SLAM2D_BOUND_LDS_BLOCKS"); return e ? atoi(e) : 0; }();
-    static const int rle_mode = [] { const char* e = getenv("SLAM2D_BOUND_LDS_RLE"); return e ? atoi(e) : -1; }();
     if (mode == 0 || !lv.gmin2b) return false;
     const int nx = 2 * lv.ncell + 1, nbt = (nx + 3) >> 2;
     const int nset = cdiv(nbt * nbt, WAVE);
     const int gp = lv.tmax << 2, lp = lv.g2b_pitch;
     if (nset > 4 || lv.kmax > 2048 || lp < gp || (lp & 15)) return false;
     const size_t image = ((size_t)gp * lp + 15) & ~(size_t)15;
-    const bool rle = (rle_mode < 0 ? lv.kmax >= SLAM2D_BEAM_TABLE_MIN : rle_mode != 0) && image + (size_t)nbt * lp < 65536;   // (16-bit offsets in the run words)
-    // (long lists: an angle is 16 us of one wave -- 256 blocks: config 5's 64-particle launches, 139 angles, four blocks per particle)
-    const int blocks = want_blocks_env > 0 ? want_blocks_env : (rle ? 256 : 128);
-    const int bpp = max(1, min(min(max_split, lv.ntheta), blocks / max(P, 1)));
+    // run-length lists from SLAM2D_BEAM_TABLE_MIN cells (16-bit offsets in the run words)
+    const bool rle = lv.kmax >= SLAM2D_BEAM_TABLE_MIN && image + (size_t)nbt * lp < 65536;
+    const int blocks = rle ? BOUND_LDS_BLOCKS_RLE : BOUND_LDS_BLOCKS;
+    const int bpp = max(1, min(min(BOUND_LDS_MAX_SPLIT, lv.ntheta), blocks / max(P, 1)));
     const int tpb = cdiv(lv.ntheta, bpp);                       // angles per block
     const int rounds = cdiv(tpb, 16), nw = cdiv(tpb, rounds);
     const size_t lds = image + (rle ? (size_t)nw * WAVE * sizeof(unsigned) : 0);
-    const size_t want = 160 * 1024 - 512;
-    if (lds > want) return false;
-    static size_t granted[64][8] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    size_t& allowed = granted[dev >= 0 && dev < 64 ? dev : 0][(nset - 1) * 2 + (rle ? 1 : 0)];
-    if (allowed == 0) allowed = 64 * 1024;
-    const void* fn[8] = {reinterpret_cast<const void*>(k_bound_lds<1, false>), reinterpret_cast<const void*>(k_bound_lds<1, true>),
-                         reinterpret_cast<const void*>(k_bound_lds<2, false>), reinterpret_cast<const void*>(k_bound_lds<2, true>),
-                         reinterpret_cast<const void*>(k_bound_lds<3, false>), reinterpret_cast<const void*>(k_bound_lds<3, true>),
-                         reinterpret_cast<const void*>(k_bound_lds<4, false>), reinterpret_cast<const void*>(k_bound_lds<4, true>)};
-    if (lds > allowed) {
-        if (hipFuncSetAttribute(fn[(nset - 1) * 2 + (rle ? 1 : 0)], hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        allowed = want;
-    }
-    const unsigned grid = (unsigned)cdiv(P, 8) * 8 * bpp;
     switch ((nset - 1) * 2 + (rle ? 1 : 0)) {
-        case 0: k_bound_lds<1, false><<<grid, WAVE * nw, lds, s>>>(lv, P, bpp, tpb); break;
-        case 1: k_bound_lds<1, true><<<grid, WAVE * nw, lds, s>>>(lv, P, bpp, tpb); break;
-        case 2: k_bound_lds<2, false><<<grid, WAVE * nw, lds, s>>>(lv, P, bpp, tpb); break;
-        case 3: k_bound_lds<2, true><<<grid, WAVE * nw, lds, s>>>(lv, P, bpp, tpb); break;
-        case 4: k_bound_lds<3, false><<<grid, WAVE * nw, lds, s>>>(lv, P, bpp, tpb); break;
-        case 5: k_bound_lds<3, true><<<grid, WAVE * nw, lds, s>>>(lv, P, bpp, tpb); break;
-        case 6: k_bound_lds<4, false><<<grid, WAVE * nw, lds, s>>>(lv, P, bpp, tpb); break;
-        default: k_bound_lds<4, true><<<grid, WAVE * nw, lds, s>>>(lv, P, bpp, tpb); break;
+        case 0: return launch_bound_lds_as<1, false>(lv, P, bpp, tpb, nw, lds, s);
+        case 1: return launch_bound_lds_as<1, true>(lv, P, bpp, tpb, nw, lds, s);
+        case 2: return launch_bound_lds_as<2, false>(lv, P, bpp, tpb, nw, lds, s);
+        case 3: return launch_bound_lds_as<2, true>(lv, P, bpp, tpb, nw, lds, s);
+        case 4: return launch_bound_lds_as<3, false>(lv, P, bpp, tpb, nw, lds, s);
+        case 5: return launch_bound_lds_as<3, true>(lv, P, bpp, tpb, nw, lds, s);
+        case 6: return launch_bound_lds_as<4, false>(lv, P, bpp, tpb, nw, lds, s);
+        default: return launch_bound_lds_as<4, true>(lv, P, bpp, tpb, nw, lds, s);
     }
-    return true;
 }
 
 static int launch_scores(const Slam2dLevel& lv, int P, const double* d_est, int est_stride, const double* d_uniform,
                          Slam2dMatch* d_out, hipStream_t s, int ring_chunks = 0) {
     const int nx = 2 * lv.ncell + 1;
     const int nslot = nx * ((nx + 3) / 4);            // slots of 4 consecutive dx
-    const int need = cdiv(nslot, WAVE);
-    int bestR = 1;        // slots per lane; measured on MI355X (config 2): 1 -> 124 us, 2..4 -> 132-134 us
-    if (const char* ov = getenv("SLAM2D_SWEEP_R")) {              // tuning knob
-        const int R = atoi(ov);
-        if (R >= 1 && R <= 4) bestR = R;
-    }
-    if (ring_chunks > 0) bestR = 1;
-    const int chunks = cdiv(need, bestR);
+    const int chunks = cdiv(nslot, WAVE);             // one slot per lane
     if (lv.ntheta * chunks > lv.npartial) return SLAM2D_E_BADARG;
     if (ring_chunks > 0) {
         // the prior's ring first (write_priors); the particles it does not settle are swept in full by the
         // second pair of launches, whose blocks return at once for everyone else
         {
             StageScope prof(SLAM2D_STAGE_SWEEP, s);
-            launch_sweep<1>(lv, P, min(ring_chunks, chunks), s, 1);
+            launch_sweep(lv, P, min(ring_chunks, chunks), s, 1);
         }
         {
             StageScope prof(SLAM2D_STAGE_SELECT, s);
-            k_select<1><<<P, WAVE, 0, s>>>(lv, min(ring_chunks, chunks), 1, d_est, est_stride, d_uniform, d_out);
+            k_select<1><<<P, WAVE, 0, s>>>(lv, min(ring_chunks, chunks), d_est, est_stride, d_uniform, d_out);
         }
     }
     const int mode = ring_chunks > 0 ? 2 : 0;
-    static const bool no_small = [] { const char* e = getenv("SLAM2D_SWEEP_NOSMALL"); return e && atoi(e) == 1; }();
-    if (mode == 0 && nslot <= 32 && chunks == 1 && !no_small) {           // small cube: one wave per (particle, theta) plane
+    if (mode == 0 && nslot <= 32) {           // small cube: one wave per (particle, theta) plane
         const unsigned grid = (unsigned)cdiv(P, 8) * 8 * lv.ntheta;
         const size_t lds = (size_t)WAVE * 4 * sizeof(unsigned long long) + (size_t)lv.kmax * sizeof(int);
         const int pruned = lv.bnb == 3 ? 1 : 0;
@@ -4464,28 +4406,21 @@ static int launch_scores(const Slam2dLevel& lv, int P, const double* d_est, int 
             k_sweep_small<<<grid, WAVE, lds, s>>>(lv, P, pruned);
         }
         StageScope prof(SLAM2D_STAGE_SELECT, s);
-        k_select<0><<<P, WAVE, 0, s>>>(lv, 1, 1, d_est, est_stride, d_uniform, d_out);
+        k_select<0><<<P, WAVE, 0, s>>>(lv, 1, d_est, est_stride, d_uniform, d_out);
         return 0;
     }
     // a level matched by arg-max (no soft-max draw: the fine level, matchMax) needs nothing of the cube for its selection: the
     // sweep's last block of every particle does it from the partials (k_sweep, sel_out) and k_select is not launched
-    // (SLAM2D_FUSE_SELECT=0: the separate launch)
-    static const bool fuse_sel = [] { const char* e = getenv("SLAM2D_FUSE_SELECT"); return !e || atoi(e) != 0; }();
-    const bool fused = fuse_sel && mode == 0 && d_uniform == nullptr && lv.sync != nullptr;
+    const bool fused = mode == 0 && d_uniform == nullptr && lv.sync != nullptr;
     {
         StageScope prof(SLAM2D_STAGE_SWEEP, s);
-        switch (bestR) {
-            case 1: launch_sweep<1>(lv, P, chunks, s, mode, fused ? d_est : nullptr, est_stride, fused ? d_out : nullptr); break;
-            case 2: launch_sweep<2>(lv, P, chunks, s, mode, fused ? d_est : nullptr, est_stride, fused ? d_out : nullptr); break;
-            case 3: launch_sweep<3>(lv, P, chunks, s, mode, fused ? d_est : nullptr, est_stride, fused ? d_out : nullptr); break;
-            default: launch_sweep<4>(lv, P, chunks, s, mode, fused ? d_est : nullptr, est_stride, fused ? d_out : nullptr); break;
-        }
+        launch_sweep(lv, P, chunks, s, mode, fused ? d_est : nullptr, est_stride, fused ? d_out : nullptr);
     }
     if (fused) return 0;
     {
         StageScope prof(SLAM2D_STAGE_SELECT, s);
-        if (mode == 0) k_select<0><<<P, WAVE, 0, s>>>(lv, chunks, bestR, d_est, est_stride, d_uniform, d_out);
-        else k_select<2><<<P, WAVE, 0, s>>>(lv, chunks, bestR, d_est, est_stride, d_uniform, d_out);
+        if (mode == 0) k_select<0><<<P, WAVE, 0, s>>>(lv, chunks, d_est, est_stride, d_uniform, d_out);
+        else k_select<2><<<P, WAVE, 0, s>>>(lv, chunks, d_est, est_stride, d_uniform, d_out);
     }
     return 0;
 }
@@ -4510,11 +4445,10 @@ static int ring_slot_bound(const Slam2dLevel& lv, double est_dist) {
 }
 
 // Blocks per particle of k_exact_select: enough to put every CU to work (256 CUs / P particles), at most 4; needs the
-// arrival counters (Slam2dLevel.sync).  SLAM2D_XS_SPLIT overrides (1 = one block per particle).
+// arrival counters (Slam2dLevel.sync).
 static int exact_split(const Slam2dLevel& lv, int P) {
-    static const int forced = [] { const char* e = getenv("SLAM2D_XS_SPLIT"); return e ? atoi(e) : 0; }();
     if (!lv.sync) return 1;
-    int n = forced > 0 ? forced : 256 / (P > 0 ? P : 1);      // (the kernel lets only XS_SPLIT_LIGHT of them work on a particle with few tiles)
+    int n = 256 / (P > 0 ? P : 1);      // (the kernel lets only XS_SPLIT_LIGHT of them work on a particle with few tiles)
     if (n > XS_SPLIT_MAX) n = XS_SPLIT_MAX;
     return n < 1 ? 1 : n;
 }
@@ -4566,24 +4500,16 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
         if (bound > 0 && 2 * bound <= nslot) ring_chunks = cdiv(bound, WAVE);     // worth it only for a thin ring
     }
     // Below SLAM2D_BEAM_TABLE_MIN beams k_frame_axis is not launched at all: the endpoint kernel's per-particle block does
-    // its work (one launch less per level); above, k_frame_axis also tabulates the beam endpoints once per particle.
-    static const bool keep_frame_kernel = [] { const char* e = getenv("SLAM2D_FRAME_KERNEL"); return e && atoi(e) == 1; }();
-    // ... from SLAM2D_FRAME_MIN_P particles per launch as well (round 6): the merged launch makes every angle block evaluate the
-    // cos / sin of all beams and every scatter block the frame; when the launch fills the machine that work costs more than the
-    // two launches it saves (config 2: k_endpoints 57 -> 27 + 26 us at 128 particles per launch, the step 0.309 -> 0.305 ms; at 256
-    // per launch 0.580 -> 0.561; at 16 per launch the two launches cost 0.113 -> 0.123)
-    static const int frame_min_p = [] { const char* e = getenv("SLAM2D_FRAME_MIN_P"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 128; }();
-    const bool framed = lidar->beams >= SLAM2D_BEAM_TABLE_MIN || keep_frame_kernel || lv.occ_gen == 0 || P >= frame_min_p;
+    // its work (one launch less per level) and the occupied-cell scatter rides in that launch as well; above, and from
+    // SLAM2D_FRAME_KERNEL_MIN_P particles per launch, k_frame_axis also tabulates the beam endpoints once per particle.
+    const bool framed = lidar->beams >= SLAM2D_BEAM_TABLE_MIN || lv.occ_gen == 0 || P >= SLAM2D_FRAME_KERNEL_MIN_P;
     const Slam2dMap* own = framed ? nullptr : d_maps;
-    // ... and then the occupied-cell scatter rides in the endpoint launch as well (SLAM2D_MERGE_SCATTER=0: its own launch)
-    static const bool merge_scatter = [] { const char* e = getenv("SLAM2D_MERGE_SCATTER"); return !e || atoi(e) != 0; }();
-    const bool merged = own && merge_scatter;
     if (lv.occ_gen < 0 || lv.occ_gen > 255) return SLAM2D_E_BADARG;
     if (lv.bnb && lv.bnb != 3) {
         // branch and bound over 4x4 pose tiles: tile bounds + seed tiles, surviving tiles + selection
         if (framed && (rc = launch_frames(*lidar, lv, d_maps, P, d_est, est_stride, d_flags, true, s, d_ranges))) return rc;
-        launch_endpoints(*lidar, lv, P, d_est, est_stride, d_ranges, est_moving_dist, d_psi_cs, d_flags, true, false, s, framed, own, merged);
-        if ((rc = launch_field(lv, d_maps, P, d_flags, true, s, merged))) return rc;
+        launch_endpoints(*lidar, lv, P, d_est, est_stride, d_ranges, est_moving_dist, d_psi_cs, d_flags, true, false, s, framed, own);
+        if ((rc = launch_field(lv, d_maps, P, d_flags, true, s, !framed))) return rc;
         const unsigned grid = (unsigned)cdiv(P, 8) * 8 * lv.ntheta;
         if (lv.bnb == 2) {
             StageScope prof(SLAM2D_STAGE_BOUND, s);
@@ -4605,8 +4531,8 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
     }
     // the endpoints need only the frame, so they run first and tell the field build which tiles matter
     if (framed && (rc = launch_frames(*lidar, lv, d_maps, P, d_est, est_stride, d_flags, true, s, d_ranges))) return rc;
-    launch_endpoints(*lidar, lv, P, d_est, est_stride, d_ranges, est_moving_dist, d_psi_cs, d_flags, true, ring_chunks > 0, s, framed, own, merged);
-    if ((rc = launch_field(lv, d_maps, P, d_flags, true, s, merged, ring_chunks > 0))) return rc;      // (the ring pass reads the field's maximum)
+    launch_endpoints(*lidar, lv, P, d_est, est_stride, d_ranges, est_moving_dist, d_psi_cs, d_flags, true, ring_chunks > 0, s, framed, own);
+    if ((rc = launch_field(lv, d_maps, P, d_flags, true, s, !framed, ring_chunks > 0))) return rc;      // (the ring pass reads the field's maximum)
     if ((rc = launch_scores(lv, P, d_est, est_stride, d_uniform, d_out, s, ring_chunks))) return rc;
     return launch_status();
 }

@@ -95,6 +95,22 @@ def test_one_abi_version_everywhere(L):
     assert not re.search(r"ABI_VERSION\s*==\s*\d", entry), "literal ABI version in __graft_entry__.py"
 
 
+def test_library_reads_only_the_documented_environment_switches():
+    """The library's `getenv` reads are the exception one can list: every SLAM2D_* name it reads is a row of
+    INTEGRATION.md's "Environment switches" table, and the set is exactly the switches something else uses
+    (`LOCAL_WORLD_SIZE` is torchrun's).  A/B of the library itself is another build, selected with SLAM2D_LIB."""
+    src = open(os.path.join(REPO, "slam-2d-lidar-scan_amd", "csrc", "slam2d.hip")).read()
+    read = set(re.findall(r'getenv\(\s*"([^"]+)"\s*\)', src))
+    assert len(re.findall(r"\bgetenv\b", src)) == len(re.findall(r'\bgetenv\(\s*"', src)), "getenv of a name that is not a literal"
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    table = doc[doc.index("## Environment switches"):]
+    rows = [l for l in table.splitlines()[1:] if l.startswith("|")]
+    documented = set(re.findall(r"`(SLAM2D_[A-Z0-9_]+)`", "\n".join(r.split("|")[1] for r in rows)))
+    ours = {n for n in read if n.startswith("SLAM2D_")}
+    assert ours <= documented, f"undocumented switches: {sorted(ours - documented)}"
+    assert read == {"SLAM2D_BOUND_LDS", "SLAM2D_LOCAL_RANKS", "SLAM2D_GROUP_THREADS", "LOCAL_WORLD_SIZE"}, sorted(read)
+
+
 def test_graft_entry_build_runs_end_to_end():
     """`__graft_entry__.build()` is what the driver and the README run: compile, load, import."""
     import shutil
