@@ -72,6 +72,11 @@ extern "C" {
                                               on the device (abort_mask).  With SLAM2D_F_SYNC_TIMEOUT beside it the scan is intact and may be
                                               run again (the gate gave up BEFORE anything was written); without this bit a timeout is fatal */
 
+#define SLAM2D_F_UPDATE_CELL_COLLISION 0x100u /* slam2d_grid_update*: two adjacent window columns (rows) of a particle round to ONE map
+                                              index (a pose on a half cell: rint's ties-to-even) -- the reference adds once per
+                                              statement there, a per-cell update cannot.  The particle's map is not touched by that
+                                              launch.  slam2d_map_scans is exact at such poses */
+
 #define SLAM2D_INIT_CELL 0x00010002u       /* visited = 1, total = 2 */
 #define SLAM2D_MAX_BLUR_RADIUS 16
 #define SLAM2D_MAX_BEAMS 2048
@@ -367,7 +372,10 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
  *                 after the beam's growth; a cell with final index (mx, my) is written at
  *                 wrap(mx - dc - ac, cols) + ac (wrap: a negative index + cols, as Python).  Such writes can land
  *                 on cells of other beams (the reference adds both increments): with d_beam_shift the counts are
- *                 updated atomically and occ_bits is NOT maintained -- call slam2d_map_refresh_bits afterwards. */
+ *                 updated atomically and occ_bits is NOT maintained -- call slam2d_map_refresh_bits afterwards.
+ * A particle whose pose puts two adjacent window columns or rows on ONE map index (a pose on a half cell of its map) is
+ * not updated at all and receives SLAM2D_F_UPDATE_CELL_COLLISION (here and in slam2d_grid_update_weights*, slam2d_scan_commit*,
+ * slam2d_groups_commit): the one-writer premise fails there; slam2d_map_scans is exact at such poses. */
 int slam2d_grid_update(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t P,
                        const double* d_pose, int32_t pose_stride, const double* d_ranges,
                        const int32_t* d_beam_shift, uint32_t* d_flags, void* stream);

@@ -26,7 +26,9 @@ F_COUNT_OVERFLOW = 0x10
 F_FLOOR_REDO = 0x20
 F_SYNC_TIMEOUT = 0x40
 F_SCAN_VOIDED = 0x80           # (snapshot only: the commit was a no-op on the device)
-FATAL_FLAGS = F_WINDOW_OUTSIDE_MAP | F_FIELD_INDEX | F_ENDPOINT_OUTSIDE | F_UPDATE_OUTSIDE_MAP | F_COUNT_OVERFLOW | F_SYNC_TIMEOUT
+F_UPDATE_CELL_COLLISION = 0x100
+FATAL_FLAGS = (F_WINDOW_OUTSIDE_MAP | F_FIELD_INDEX | F_ENDPOINT_OUTSIDE | F_UPDATE_OUTSIDE_MAP | F_COUNT_OVERFLOW | F_SYNC_TIMEOUT |
+               F_UPDATE_CELL_COLLISION)
 FLAG_NAMES = {
     F_WINDOW_OUTSIDE_MAP: "search window outside the map (grow the map first)",
     F_FIELD_INDEX: "occupied cell mapped outside the search field",
@@ -34,6 +36,8 @@ FLAG_NAMES = {
     F_UPDATE_OUTSIDE_MAP: "map update touched a cell outside the map",
     F_COUNT_OVERFLOW: "16-bit cell count overflow",
     F_FLOOR_REDO: "field minimum differed from the analytic floor (clamp redone)",
+    F_UPDATE_CELL_COLLISION: "map update at a pose on a half cell: two window cells round to one map cell (the batched update "
+                             "cannot reproduce the reference there; OccupancyGrid / map_from_poses can)",
     F_SYNC_TIMEOUT: "a device-side wait of the groups' normaliser gave up after its bound (30 s unless set: a producer never arrived)",
 }
 INIT_CELL = 0x00010002

@@ -3717,6 +3717,28 @@ __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar
         const bool lattice = !beam_shift && lid.lut_xs_step == lid.unit && fabs(Ax) < 1e8 && fabs(Ay) < 1e8 &&
                              fabs(fabs(Ax - rAx) - 0.5) > 1e-6 && fabs(fabs(Ay - rAy) - 0.5) > 1e-6 && !UPDB_NO_LATTICE;
         const int bx = (int)rAx, by = (int)rAy;
+        if (!lattice && !(lid.lut_xs_step > lid.unit * (1.0 + 1e-9))) {
+            // One writer per map cell is the premise of the plain read-modify-write below.  Off the lattice it can fail: at a
+            // pose on a half cell rint's ties-to-even sends two adjacent window columns (rows) to ONE map index (the window step
+            // is never below the unit: only neighbours can meet), where the reference's fancy-index statement adds once per
+            // statement (Utils/OccupancyGrid.py:149-152) and this kernel would add twice, or lose one of two increments that
+            // share an instruction.  Decided once per wave from the W - 1 neighbour pairs of each axis, the same for every wave
+            // of the particle: its map is then not touched at all and it gets SLAM2D_F_UPDATE_CELL_COLLISION -- the host raises
+            // (slam2d_map_scans computes these poses exactly).  A window step above the unit by more than the quotients' rounding
+            // error (< 1e-11 cells) keeps neighbours at least one index apart whatever the pose: those lidars skip the test.
+            bool meet = false;
+            for (int j = lane; j < W - 1; j += 64) {
+                const double a0 = lid.lut_xs_step != 0.0 ? (double)j * lid.lut_xs_step + -lid.max_range : lid.lut_xs[j];
+                const double a1 = lid.lut_xs_step != 0.0 ? (j + 1 == W - 1 ? lid.max_range : (double)(j + 1) * lid.lut_xs_step + -lid.max_range)
+                                                         : lid.lut_xs[j + 1];
+                meet |= rint(((px + a0) - m.lim_x0) / lid.unit) == rint(((px + a1) - m.lim_x0) / lid.unit) ||
+                        rint(((py + a0) - m.lim_y0) / lid.unit) == rint(((py + a1) - m.lim_y0) / lid.unit);
+            }
+            if (__any(meet)) {
+                if (lane == 0) atomicOr(&flags[p], SLAM2D_F_UPDATE_CELL_COLLISION);
+                return;
+            }
+        }
         for (int k0 = kbeg + lane; k0 < kend; k0 += 64 * UPDB_UNROLL) {
             // straight-line phases, every load of a phase issued before its first use (no branches in between)
             double r[UPDB_UNROLL], xj[UPDB_UNROLL], yi[UPDB_UNROLL];

@@ -341,6 +341,12 @@ class LidarModel:
         R = self.max_range
         return not (x - R < m.lim_x[0] or x + R > m.lim_x[1] or y - R < m.lim_y[0] or y + R > m.lim_y[1])
 
+    def window_collides(self, m, x, y):
+        """Two adjacent window columns or rows round to ONE index of map ``m`` at pose (x, y) -- a pose on a half cell, where rint's
+        ties-to-even breaks k_grid_update's one-writer-per-cell premise (the kernel's own test, SLAM2D_F_UPDATE_CELL_COLLISION)."""
+        xi, yi = m.to_map_idx(x + self.xs, y + self.xs, self.unit)
+        return bool((np.diff(xi) == 0).any() or (np.diff(yi) == 0).any())
+
     def plan_scans(self, m, poses, extents):
         """The reference's per-beam growth (:144-147) replayed over a batch of scans on MapState ``m`` (grown on the host
         with deferred_growth, materialised once), from the occupied extents of every beam (slam2d_occ_extent; None: every

@@ -324,6 +324,12 @@ class ParticleFilter:
             self._stage_inputs(0, rng_in)
         if count == 1:
             self.prev_raw_heading = None
+            if self.lidar.window_collides(eng.maps[0], reading['x'], reading['y']):
+                # (e.g. an odd number of cells per side with the first pose on the map's centre; the matched poses then stay on
+                # half cells, and the update kernel would flag every scan: SLAM2D_F_UPDATE_CELL_COLLISION)
+                raise _lib.Slam2dError("the first pose lies on a half cell of the map: two window columns round to one map cell and "
+                                       "the batched update cannot reproduce the reference there -- shift initXY by half a cell or use "
+                                       "a map length that is an even number of cells (OccupancyGrid / map_from_poses are exact here)")
             self.d_pose.copy_(torch.tensor([[reading['x'], reading['y'], reading['theta']]] * P, dtype=torch.float64))
             self.d_head.fill_(float("nan"))
             matched = np.tile([reading['x'], reading['y'], reading['theta']], (P, 1)).astype(np.float64)
