@@ -941,7 +941,8 @@ __global__ __launch_bounds__(TRIAGE_THREADS) void k_tile_triage(Slam2dLevel lv, 
 // and the update's -- x-adjacent tiles share the 128-byte lines of their occupancy halo (8 tiles wide), and with the blocks of a
 // particle dealt round the XCDs by blockIdx.x every XCD's L2 fetched its own copy of those lines (round 3: 34 MB of HBM
 // traffic per 32-particle launch for 6.9 MB processed, L2 hit rate 56 % with the (blocks, P) grid of rounds 1-3).
-// tail != 0 (round 4: levels without bounds, where that was all k_blur_check_redo was launched for): the minimum check of a frame
+// tail != 0 (levels where k_blur_check_redo is not launched, fold_field_check: those without bounds since round 4, and those whose
+// bounds k_bound_lds takes -- blur_tile's redo rewrites the block minima gmin, that kernel derives gmin2 from them): the minimum check of a frame
 // WITHOUT a free tile -- rare: then every tile was listed and blurred against the analytic floor -- is done by the last of the
 // particle's blur blocks to finish (arrival counter lv.sync[p][1]; plain stores + agent release before the ticket, agent acquire
 // after it: the slow, always-valid form -- it runs once in a blue moon).  A frame with a free tile, the normal case, costs nothing.
@@ -994,10 +995,50 @@ __global__ __launch_bounds__(BLUR_THREADS, BLUR_MIN_WAVES) void k_blur_clamp(Sla
 #define GMIN2_BLOCKS 16              // blocks per particle of k_blur_check_redo where it derives gmin2
 // gmin2 (branch and bound): element [Y][X] = min(gmin[Y..Y+1][X..X+1]) >> 12.  Blocks beyond the buffer are clamped
 // (duplicates only).
+// The arithmetic of an entry, shared by k_blur_check_redo (gmin2_entry, gmin2_dirty) and by k_bound_lds's prologue (bound_refresh_*): both
+// must leave the same bits in memory.
+typedef unsigned int gu4 __attribute__((ext_vector_type(4)));
+// one entry: the minimum of its 2 x 2 block minima (indices clamped to the image)
+__device__ __forceinline__ uint32_t gmin2_min2x2(const uint32_t* __restrict__ G, const int gp, const int Y, const int X) {
+    const int Y1 = min(Y + 1, gp - 1), X1 = min(X + 1, gp - 1);
+    return min(min(G[(size_t)Y * gp + X], G[(size_t)Y * gp + X1]), min(G[(size_t)Y1 * gp + X], G[(size_t)Y1 * gp + X1]));
+}
+// the 5 entries X = 4 tx - 1 .. 4 tx + 3 of row Y of a tile's reach: `em` and e.x .. e.w, unshifted.  Row-wise only for a tile off
+// the image's border (gmin2_row_on_border: those go entry by entry): two block-minima rows as 1 + 4 + 1 values each, the
+// middle four one aligned 16-byte load.
+struct Gmin2Row { uint32_t em; gu4 e; };
+__device__ __forceinline__ bool gmin2_row_on_border(const int tmax, const int gp, const int tx, const int Y) {
+    return tx == 0 || tx >= tmax - 1 || Y + 1 >= gp;
+}
+__device__ __forceinline__ Gmin2Row gmin2_row_minima(const uint32_t* __restrict__ G, const int gp, const int Y, const int tx) {
+    const uint32_t* __restrict__ r0 = G + (size_t)Y * gp + 4 * tx;
+    const uint32_t* __restrict__ r1 = r0 + gp;
+    const uint32_t am = r0[-1], ap = r0[4], bm = r1[-1], bp = r1[4];
+    const gu4 a = *reinterpret_cast<const gu4*>(r0), b = *reinterpret_cast<const gu4*>(r1);
+    const uint32_t cm = min(am, bm), c0 = min(a.x, b.x), c1 = min(a.y, b.y), c2 = min(a.z, b.z), c3 = min(a.w, b.w), cp = min(ap, bp);
+    Gmin2Row row;
+    row.em = min(cm, c0);
+    row.e.x = min(c0, c1); row.e.y = min(c1, c2); row.e.z = min(c2, c3); row.e.w = min(c3, cp);
+    return row;
+}
+// what is stored of a row: gmin2 holds >> 12 (o = the entry at X = 4 tx), the byte image >> 24 (ob likewise, an aligned word)
+__device__ __forceinline__ uint32_t gmin2_row_bytes(const Gmin2Row& row) {
+    return (row.e.x >> 24) | ((row.e.y >> 24) << 8) | ((row.e.z >> 24) << 16) | ((row.e.w >> 24) << 24);
+}
+__device__ __forceinline__ void gmin2_row_store_words(const Gmin2Row& row, uint32_t* __restrict__ o) {
+    o[-1] = row.em >> 12;
+    gu4 ov; ov.x = row.e.x >> 12; ov.y = row.e.y >> 12; ov.z = row.e.z >> 12; ov.w = row.e.w >> 12;
+    *reinterpret_cast<gu4*>(o) = ov;
+}
+template <typename B>
+__device__ __forceinline__ void gmin2_row_store_bytes(const Gmin2Row& row, B* ob) {
+    ob[-1] = (B)(row.em >> 24);
+    *reinterpret_cast<uint32_t*>(ob) = gmin2_row_bytes(row);
+}
 __device__ __forceinline__ void gmin2_entry(const Slam2dLevel& lv, const uint32_t* __restrict__ G, uint32_t* __restrict__ G2,
                                             const int p, const int gp, const int Y, const int X) {
     const int Y1 = min(Y + 1, gp - 1), X1 = min(X + 1, gp - 1);
-    const uint32_t v = min(min(G[(size_t)Y * gp + X], G[(size_t)Y * gp + X1]), min(G[(size_t)Y1 * gp + X], G[(size_t)Y1 * gp + X1]));
+    const uint32_t v = gmin2_min2x2(G, gp, Y, X);
     G2[(size_t)Y * gp + X] = v >> 12;
     if (lv.gmin2b) lv.gmin2b[((size_t)p * gp + Y) * lv.g2b_pitch + X] = (uint8_t)(v >> 24);      // (k_bound_lds)
     if (lv.bnb == 2) {
@@ -1040,35 +1081,22 @@ __device__ __forceinline__ void gmin2_dirty(const Slam2dLevel& lv, const int p, 
         // 5 x 5 entries per tile, one thread per (tile, entry row): the two block-minima rows it needs as 1 + 4 + 1 values each (the
         // middle four are one aligned 16-byte load), five entries out as 1 + 4 -- 6 loads and 2 (+ 2 byte-image) stores per row where
         // the entry-per-thread form below issued 20 and 5 (+ 5); same minima, same bits.  Tiles on the image's border go entry by entry.
-        typedef unsigned int gu4 __attribute__((ext_vector_type(4)));
         for (int idx = part * nthreads + tid; idx < (nb + nf) * 5; idx += parts * nthreads) {
             const int k = idx / 5, r = idx - k * 5;
             const int t = k < nb ? list[k] : list[ntile + (k - nb)];
             const int ty = t / lv.tmax, tx = t - ty * lv.tmax;
             const int Y = 4 * ty - 1 + r;
             if (Y < 0 || Y >= gp) continue;
-            if (tx == 0 || tx >= lv.tmax - 1 || Y + 1 >= gp) {
+            if (gmin2_row_on_border(lv.tmax, gp, tx, Y)) {
                 for (int c = 0; c < 5; ++c) {
                     const int X = 4 * tx - 1 + c;
                     if (X >= 0 && X < gp) gmin2_entry(lv, G, G2, p, gp, Y, X);
                 }
                 continue;
             }
-            const uint32_t* __restrict__ r0 = G + (size_t)Y * gp + 4 * tx;
-            const uint32_t* __restrict__ r1 = r0 + gp;
-            const uint32_t am = r0[-1], ap = r0[4], bm = r1[-1], bp = r1[4];
-            const gu4 a = *reinterpret_cast<const gu4*>(r0), b = *reinterpret_cast<const gu4*>(r1);
-            const uint32_t cm = min(am, bm), c0 = min(a.x, b.x), c1 = min(a.y, b.y), c2 = min(a.z, b.z), c3 = min(a.w, b.w), cp = min(ap, bp);
-            const uint32_t em = min(cm, c0), e0 = min(c0, c1), e1 = min(c1, c2), e2 = min(c2, c3), e3 = min(c3, cp);
-            uint32_t* __restrict__ o = G2 + (size_t)Y * gp + 4 * tx;
-            o[-1] = em >> 12;
-            gu4 ov; ov.x = e0 >> 12; ov.y = e1 >> 12; ov.z = e2 >> 12; ov.w = e3 >> 12;
-            *reinterpret_cast<gu4*>(o) = ov;
-            if (lv.gmin2b) {
-                uint8_t* __restrict__ ob = lv.gmin2b + ((size_t)p * gp + Y) * lv.g2b_pitch + 4 * tx;
-                ob[-1] = (uint8_t)(em >> 24);
-                *reinterpret_cast<uint32_t*>(ob) = (e0 >> 24) | ((e1 >> 24) << 8) | ((e2 >> 24) << 16) | ((e3 >> 24) << 24);
-            }
+            const Gmin2Row row = gmin2_row_minima(G, gp, Y, tx);
+            gmin2_row_store_words(row, G2 + (size_t)Y * gp + 4 * tx);
+            if (lv.gmin2b) gmin2_row_store_bytes(row, lv.gmin2b + ((size_t)p * gp + Y) * lv.g2b_pitch + 4 * tx);
         }
         return;
     }
@@ -2211,7 +2239,7 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const
 // K1e  branch and bound over 4x4 pose tiles (include/slam2d.h, "Branch and bound"): the same scores as k_sweep
 //      for every pose that can matter, from 1/16 of the gathers plus the exact scores of a few per cent of the tiles.
 //        blur / triage  write gmin (minimum of every aligned 4x4 block of the cost image) with the field tiles;
-//                  k_blur_check_redo derives gmin2 = min over 2x2 blocks (>> 12): a lower bound of the cost anywhere
+//                  k_blur_check_redo (or k_bound_lds's prologue) derives gmin2 = min over 2x2 blocks (>> 12): a lower bound of the cost anywhere
 //                  in the aligned 8x8 block that contains a pose tile's 4x4 window at a cell.
 //        k_bound   one wave per (particle, theta): upper bound U of every tile (lane = one pose-tile row x 4
 //                  consecutive tiles: ONE 16-byte load per cell from an image 1/16 the size of the field, 16 in
@@ -2465,8 +2493,80 @@ __device__ __forceinline__ void bound_seed_exact(const Slam2dLevel& lv, const in
 // RLE (long lists: ~1000 beams): neighbouring beams end in the same 4 x 4-cell block more often than not, so a wave's 64 cell offsets are
 // run-length compressed first (ballot of the run heads, the (offset, run length) pairs compacted through 256 bytes of LDS per wave)
 // and the gathers go over the runs: sum += entry x run length.
+//
+// refresh != 0 (the host folded k_blur_check_redo's launch away: fold_field_check): the prologue also brings the bound minima up
+// to date, which that launch did between the blur and this kernel.  What gmin2_dirty refreshes -- for every tile written at this
+// build (the triage's blur list and fill list) 5 rows of 1 + 4 + 1 entries, entry = min(2 x 2 of gmin), border tiles entry by
+// entry -- reads only the block minima of EARLIER launches (blur, triage fill), complete when this kernel starts: no barrier
+// between a particle's blocks is needed.  Every block patches the entries' bytes (>> 24) into ITS OWN LDS image; the block with
+// part == 0 also stores gmin2 (>> 12) and gmin2b to memory, the very values the separate launch left there -- a later scan
+// stages the entries that are not dirty then from gmin2b, and the level may be bounded through the 32-bit gmin2 later on.
+// Order: a dirty byte reaches LDS twice, stale with the staging copy and fresh with the refresh, so one barrier separates the
+// staging stores (any wave's) from the refresh stores; the refresh's loads (tilecount -> list -> gmin rows) are issued BEFORE
+// that barrier, beside the staging loads, so that only its stores lie behind it.  Sibling blocks of the particle may stage
+// while block part == 0 rewrites the same bytes of gmin2b: they see the old or the new value of a byte and then overwrite
+// exactly those bytes in LDS with the new one -- the image does not depend on the timing.
+// A frame without a free tile (!min_known: rare; the blur's tail has checked its minimum and redone the clamp) gets the
+// whole-frame pass of gmin2_pass instead -- its rows and columns are not those the tile lists reach.
+enum { REFRESH_NONE = 0, REFRESH_ROW = 1, REFRESH_BORDER = 2 };
+struct RefreshRow { int kind, Y, X0; Gmin2Row m; };
+// one entry, the slow way: loads and stores (border tiles, the whole-frame pass)
+__device__ __forceinline__ void bound_refresh_entry(const uint32_t* __restrict__ G, uint32_t* __restrict__ G2, uint8_t* __restrict__ G2B,
+                                                    unsigned char* g2s, const int gp, const int lp, const int Y, const int X,
+                                                    const bool writer) {
+    const uint32_t v = gmin2_min2x2(G, gp, Y, X);
+    g2s[Y * lp + X] = (unsigned char)(v >> 24);
+    if (writer) {
+        G2[(size_t)Y * gp + X] = v >> 12;
+        G2B[(size_t)Y * lp + X] = (uint8_t)(v >> 24);
+    }
+}
+// task idx = (tile idx / 5 of the two lists, entry row idx % 5): the tile, then the row's minima into registers (interior
+// tiles; nothing is stored)
+__device__ __forceinline__ int bound_refresh_tile(const int* __restrict__ list, const int ntile, const int nb, const int idx) {
+    const int k = idx / 5;
+    return k < nb ? list[k] : list[ntile + (k - nb)];
+}
+__device__ __forceinline__ RefreshRow bound_refresh_load(const uint32_t* __restrict__ G, const int tmax, const int gp, const int t, const int idx) {
+    RefreshRow row{REFRESH_NONE, 0, 0, Gmin2Row{0u, gu4{0u, 0u, 0u, 0u}}};
+    const int r = idx % 5;
+    const int ty = t / tmax, tx = t - ty * tmax;
+    const int Y = 4 * ty - 1 + r;
+    if (Y < 0 || Y >= gp) return row;
+    row.Y = Y; row.X0 = 4 * tx;
+    if (gmin2_row_on_border(tmax, gp, tx, Y)) { row.kind = REFRESH_BORDER; return row; }
+    row.m = gmin2_row_minima(G, gp, Y, tx);
+    row.kind = REFRESH_ROW;
+    return row;
+}
+__device__ __forceinline__ void bound_refresh_store(const RefreshRow& row, const uint32_t* __restrict__ G, uint32_t* __restrict__ G2,
+                                                    uint8_t* __restrict__ G2B, unsigned char* g2s, const int gp, const int lp,
+                                                    const bool writer) {
+    if (row.kind == REFRESH_BORDER) {
+        for (int c = 0; c < 5; ++c) {
+            const int X = row.X0 - 1 + c;
+            if (X >= 0 && X < gp) bound_refresh_entry(G, G2, G2B, g2s, gp, lp, row.Y, X, writer);
+        }
+        return;
+    }
+    if (row.kind != REFRESH_ROW) return;
+    gmin2_row_store_bytes(row.m, g2s + row.Y * lp + row.X0);                  // (lp % 16 == 0, X0 % 4 == 0: an aligned word)
+    if (writer) {
+        gmin2_row_store_words(row.m, G2 + (size_t)row.Y * gp + row.X0);
+        gmin2_row_store_bytes(row.m, G2B + (size_t)row.Y * lp + row.X0);
+    }
+}
+// the whole frame, as gmin2_pass covers it (a frame without a free tile: once in a blue moon, may be slow)
+__device__ __forceinline__ void bound_refresh_frame(const uint32_t* __restrict__ G, uint32_t* __restrict__ G2, uint8_t* __restrict__ G2B,
+                                                 unsigned char* g2s, const int gp, const int lp, const int rows, const int cols,
+                                                 const bool writer) {
+    for (int idx = threadIdx.x; idx < rows * cols; idx += blockDim.x) {
+        const int Y = idx / cols, X = idx - Y * cols;
+        bound_refresh_entry(G, G2, G2B, g2s, gp, lp, Y, X, writer);
+    }
+}
 template <int NSET, bool RLE>
-__global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int bpp, int tpb) {
+__global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int bpp, int tpb, int refresh) {
     extern __shared__ __attribute__((aligned(16))) unsigned char g2s[];                  // [gp][lp] (+ RLE: [waves][64] words)
     const int lp = lv.g2b_pitch;
     const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
@@ -2477,6 +2577,17 @@ __global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int b
     const int nbt = (nx + 3) >> 2, nq = (nbt + 3) >> 2, nbq4 = nq << 2;
     const int gp = lv.tmax << 2;
     DBG_CLOCK(0, b == 0);
+    // the refresh's chain starts ahead of the staging loads (refresh, and hence every branch on it, is uniform over the launch)
+    // -- tile counts, then this thread's tile of the lists: in flight with the image
+    const int ntile = lv.tmax * lv.tmax;
+    const int* __restrict__ dlist = lv.tilelist + (size_t)p * 2 * ntile;
+    int nblur = 0, ndirty = 0, min_known = 1, dtile = 0;
+    if (refresh) {
+        min_known = lv.frames[p].min_known;
+        nblur = lv.tilecount[2 * p];
+        ndirty = min_known ? (nblur + lv.tilecount[2 * p + 1]) * 5 : 0;
+        if (tid < ndirty) dtile = bound_refresh_tile(dlist, ntile, nblur, tid);
+    }
     {   // the image, as it lies in memory: 16-byte chunks, four loads in flight per thread
         const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(lv.gmin2b + (size_t)p * gp * lp);
         u32x4* dst = reinterpret_cast<u32x4*>(g2s);
@@ -2490,6 +2601,26 @@ __global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int b
         }
     }
     DBG_CLOCK(1, b == 0);
+    if (refresh) {                                          // the bound minima of the tiles written at this build (see above)
+        const int nt = blockDim.x;
+        const uint32_t* __restrict__ G = lv.gmin + (size_t)p * gp * gp;
+        uint32_t* __restrict__ G2 = lv.gmin2 + (size_t)p * gp * gp;
+        uint8_t* __restrict__ G2B = lv.gmin2b + (size_t)p * gp * lp;
+        const bool writer = part == 0;
+        RefreshRow row{REFRESH_NONE, 0, 0, Gmin2Row{0u, gu4{0u, 0u, 0u, 0u}}};
+        if (tid < ndirty) row = bound_refresh_load(G, lv.tmax, gp, dtile, tid);                    // loads only
+        __syncthreads();                                    // every wave's staging stores lie before any refresh store
+        bound_refresh_store(row, G, G2, G2B, g2s, gp, lp, writer);
+        for (int idx = tid + nt; idx < ndirty; idx += nt)   // (more tasks than threads: a launch of few waves, a long list)
+            bound_refresh_store(bound_refresh_load(G, lv.tmax, gp, bound_refresh_tile(dlist, ntile, nblur, idx), idx), G, G2, G2B, g2s, gp, lp, writer);
+        if (!min_known) {
+            // (block-uniform; rare.)  Every block of the particle walks the whole frame, four dependent 4-byte loads and a byte
+            // store per entry, ~30 000 entries over <= 1024 threads at config 2: some tens of microseconds, in a scan whose blur
+            // has just redone every tile of the frame with one wave
+            const Slam2dFrame fr = lv.frames[p];
+            bound_refresh_frame(G, G2, G2B, g2s, gp, lp, min(gp, (fr.fh >> 2) + 2), min(gp, (fr.fw >> 2) + 2), writer);
+        }
+    }
     // this lane's tiles (byte offsets into the LDS image, slots of the bounds array)
     int lbase[NSET], tslot[NSET];
     bool valid[NSET];
@@ -4210,13 +4341,28 @@ static bool grant_dynamic_lds(const void* kernel, size_t (&granted)[64], size_t 
     allowed = DYN_LDS_MAX;
     return true;
 }
-// one instantiation of k_bound_lds: its LDS granted, then launched (false: not granted, nothing launched)
+// How k_bound_lds runs at a level (bound_lds_plan): ok = it does -- every condition of its launch, the dynamic-LDS grant included,
+// was evaluated when the plan was made, so whoever reads the plan (the field build's fold, the launch) sees one decision.
+struct BoundLdsPlan { bool ok; int nset; bool rle; int bpp, tpb, nw; size_t lds; };
+// one instantiation of k_bound_lds: its LDS granted (launch == false: that is all; false: not granted), then launched
 template <int NSET, bool RLE>
-static bool launch_bound_lds_as(const Slam2dLevel& lv, int P, int bpp, int tpb, int nw, size_t lds, hipStream_t s) {
+static bool bound_lds_as(const Slam2dLevel& lv, int P, const BoundLdsPlan& pl, bool launch, int refresh, hipStream_t s) {
     static size_t granted[64] = {};
-    if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_bound_lds<NSET, RLE>), granted, lds)) return false;
-    k_bound_lds<NSET, RLE><<<(unsigned)cdiv(P, 8) * 8 * bpp, WAVE * nw, lds, s>>>(lv, P, bpp, tpb);
+    if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_bound_lds<NSET, RLE>), granted, pl.lds)) return false;
+    if (launch) k_bound_lds<NSET, RLE><<<(unsigned)cdiv(P, 8) * 8 * pl.bpp, WAVE * pl.nw, pl.lds, s>>>(lv, P, pl.bpp, pl.tpb, refresh);
     return true;
+}
+static bool bound_lds_dispatch(const Slam2dLevel& lv, int P, const BoundLdsPlan& pl, bool launch, int refresh, hipStream_t s) {
+    switch ((pl.nset - 1) * 2 + (pl.rle ? 1 : 0)) {
+        case 0: return bound_lds_as<1, false>(lv, P, pl, launch, refresh, s);
+        case 1: return bound_lds_as<1, true>(lv, P, pl, launch, refresh, s);
+        case 2: return bound_lds_as<2, false>(lv, P, pl, launch, refresh, s);
+        case 3: return bound_lds_as<2, true>(lv, P, pl, launch, refresh, s);
+        case 4: return bound_lds_as<3, false>(lv, P, pl, launch, refresh, s);
+        case 5: return bound_lds_as<3, true>(lv, P, pl, launch, refresh, s);
+        case 6: return bound_lds_as<4, false>(lv, P, pl, launch, refresh, s);
+        default: return bound_lds_as<4, true>(lv, P, pl, launch, refresh, s);
+    }
 }
 
 extern "C" {
@@ -4289,17 +4435,23 @@ static int launch_frames(const Slam2dLidar& lid, const Slam2dLevel& lv, const Sl
 }
 
 // occupied cells -> field image, tile triage (+ fill), blur + clamp, minimum check
+// Is k_blur_check_redo's launch folded away at this level?  Without the sweep's free-tile masks and without the prior pruning
+// (which reads the field's maximum) it has two duties left.  The minimum check of a frame without a free tile: the blur's last
+// block does it (k_blur_clamp, tail; its arrival counter is lv.sync word 1 -- k_exact_select counts in word 0, the sweep's fused
+// selection in word 2).  The bound minima gmin2 / gmin2b of the tiles just written: without bounds there are none (round 4: one
+// launch per level less, 2 x 6 us per scan at the reference's defaults); with bounds taken by k_bound_lds (bound_lds: the
+// level's BoundLdsPlan.ok) that kernel's prologue derives them.  Two-level and angle bounds, the full build and k_bound keep the launch.
+static bool fold_field_check(const Slam2dLevel& lv, bool lazy, bool field_max_needed, bool bound_lds) {
+    return lazy && (lv.bnb == 0 || (lv.bnb == 1 && bound_lds)) && !sweep_skips(lv) && !field_max_needed && lv.sync != nullptr;
+}
 static int launch_field(const Slam2dLevel& lv, const Slam2dMap* d_maps, int P, uint32_t* d_flags, bool lazy, hipStream_t s,
-                        bool scattered = false, bool field_max_needed = true) {
+                        bool scattered = false, bool field_max_needed = true, bool bound_lds = false) {
     if (!scattered) {
         StageScope prof(SLAM2D_STAGE_SCATTER, s);
         k_occ_scatter<<<dim3(cdiv(cdiv(lv.wmax, 32) + 1, 64), cdiv(lv.wmax, SCATTER_ROWS), P), dim3(64, 4), (size_t)lv.wmax * sizeof(int32_t), s>>>(lv, d_maps);
     }
     const int ntile = lv.tmax * lv.tmax;
-    // Without bounds (no gmin2 to derive), without the sweep's free-tile masks and without the prior pruning (which reads the
-    // field's maximum) k_blur_check_redo has ONE duty left: the minimum check of a frame without a free tile -- the blur's last
-    // block does it (k_blur_clamp, tail).  One launch per level less: 2 x 6 us per scan at the reference's defaults.
-    const bool folded = lazy && !lv.bnb && !sweep_skips(lv) && !field_max_needed && lv.sync != nullptr;
+    const bool folded = fold_field_check(lv, lazy, field_max_needed, bound_lds);
     {
         const int kb = (lv.blur_radius + 7) >> FLAG_SHIFT;
         const int rw = (flag_pitch(lv) >> 4) + 1;
@@ -4368,31 +4520,31 @@ static void launch_endpoints(const Slam2dLidar& lid, const Slam2dLevel& lv, int 
 #define BOUND_LDS_MAX_SPLIT 4
 #define BOUND_LDS_BLOCKS 128
 #define BOUND_LDS_BLOCKS_RLE 256     // long lists: an angle is 16 us of one wave (config 5's 64-particle launches, 139 angles, four blocks per particle)
-static bool launch_bound_lds(const Slam2dLevel& lv, int P, hipStream_t s) {
+// The one predicate "this level's bounds will be computed by k_bound_lds", with the launch's shape: made once per slam2d_match,
+// read by launch_field (which then leaves the refresh of the bound minima to that kernel) and by launch_bound_lds.
+static BoundLdsPlan bound_lds_plan(const Slam2dLevel& lv, int P) {
     static const int mode = [] { const char* e = getenv("SLAM2D_BOUND_LDS"); return e ? atoi(e) : -1; }();
-    if (mode == 0 || !lv.gmin2b) return false;
+    BoundLdsPlan pl{};
+    if (mode == 0 || lv.bnb != 1 || !lv.gmin2b) return pl;
     const int nx = 2 * lv.ncell + 1, nbt = (nx + 3) >> 2;
-    const int nset = cdiv(nbt * nbt, WAVE);
+    pl.nset = cdiv(nbt * nbt, WAVE);
     const int gp = lv.tmax << 2, lp = lv.g2b_pitch;
-    if (nset > 4 || lv.kmax > 2048 || lp < gp || (lp & 15)) return false;
+    if (pl.nset > 4 || lv.kmax > 2048 || lp < gp || (lp & 15)) return pl;
     const size_t image = ((size_t)gp * lp + 15) & ~(size_t)15;
     // run-length lists from SLAM2D_BEAM_TABLE_MIN cells (16-bit offsets in the run words)
-    const bool rle = lv.kmax >= SLAM2D_BEAM_TABLE_MIN && image + (size_t)nbt * lp < 65536;
-    const int blocks = rle ? BOUND_LDS_BLOCKS_RLE : BOUND_LDS_BLOCKS;
-    const int bpp = max(1, min(min(BOUND_LDS_MAX_SPLIT, lv.ntheta), blocks / max(P, 1)));
-    const int tpb = cdiv(lv.ntheta, bpp);                       // angles per block
-    const int rounds = cdiv(tpb, 16), nw = cdiv(tpb, rounds);
-    const size_t lds = image + (rle ? (size_t)nw * WAVE * sizeof(unsigned) : 0);
-    switch ((nset - 1) * 2 + (rle ? 1 : 0)) {
-        case 0: return launch_bound_lds_as<1, false>(lv, P, bpp, tpb, nw, lds, s);
-        case 1: return launch_bound_lds_as<1, true>(lv, P, bpp, tpb, nw, lds, s);
-        case 2: return launch_bound_lds_as<2, false>(lv, P, bpp, tpb, nw, lds, s);
-        case 3: return launch_bound_lds_as<2, true>(lv, P, bpp, tpb, nw, lds, s);
-        case 4: return launch_bound_lds_as<3, false>(lv, P, bpp, tpb, nw, lds, s);
-        case 5: return launch_bound_lds_as<3, true>(lv, P, bpp, tpb, nw, lds, s);
-        case 6: return launch_bound_lds_as<4, false>(lv, P, bpp, tpb, nw, lds, s);
-        default: return launch_bound_lds_as<4, true>(lv, P, bpp, tpb, nw, lds, s);
-    }
+    pl.rle = lv.kmax >= SLAM2D_BEAM_TABLE_MIN && image + (size_t)nbt * lp < 65536;
+    const int blocks = pl.rle ? BOUND_LDS_BLOCKS_RLE : BOUND_LDS_BLOCKS;
+    pl.bpp = max(1, min(min(BOUND_LDS_MAX_SPLIT, lv.ntheta), blocks / max(P, 1)));
+    pl.tpb = cdiv(lv.ntheta, pl.bpp);                           // angles per block
+    const int rounds = cdiv(pl.tpb, 16);
+    pl.nw = cdiv(pl.tpb, rounds);
+    pl.lds = image + (pl.rle ? (size_t)pl.nw * WAVE * sizeof(unsigned) : 0);
+    pl.ok = bound_lds_dispatch(lv, P, pl, false, 0, nullptr);      // (the grant alone)
+    return pl;
+}
+// false: nothing launched (the plan says k_bound)
+static bool launch_bound_lds(const Slam2dLevel& lv, int P, const BoundLdsPlan& pl, bool refresh, hipStream_t s) {
+    return pl.ok && bound_lds_dispatch(lv, P, pl, true, refresh ? 1 : 0, s);
 }
 
 static int launch_scores(const Slam2dLevel& lv, int P, const double* d_est, int est_stride, const double* d_uniform,
@@ -4531,7 +4683,10 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
         // branch and bound over 4x4 pose tiles: tile bounds + seed tiles, surviving tiles + selection
         if (framed && (rc = launch_frames(*lidar, lv, d_maps, P, d_est, est_stride, d_flags, true, s, d_ranges))) return rc;
         launch_endpoints(*lidar, lv, P, d_est, est_stride, d_ranges, est_moving_dist, d_psi_cs, d_flags, true, false, s, framed, own);
-        if ((rc = launch_field(lv, d_maps, P, d_flags, true, s, !framed))) return rc;
+        // (nothing here reads the field's maximum: that is the prior pruning's, which scores by the sweep)
+        const BoundLdsPlan plan = bound_lds_plan(lv, P);
+        const bool refresh = fold_field_check(lv, true, false, plan.ok);     // launch_field's own decision: k_bound_lds refreshes the bound minima
+        if ((rc = launch_field(lv, d_maps, P, d_flags, true, s, !framed, false, plan.ok))) return rc;
         const unsigned grid = (unsigned)cdiv(P, 8) * 8 * lv.ntheta;
         if (lv.bnb == 2) {
             StageScope prof(SLAM2D_STAGE_BOUND, s);
@@ -4540,8 +4695,10 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
             k_bound2<<<grid, WAVE, 0, s>>>(lv, P);
         } else {
             StageScope prof(SLAM2D_STAGE_BOUND, s);
-            if (!launch_bound_lds(lv, P, s))
+            if (!launch_bound_lds(lv, P, plan, refresh, s)) {
+                if (refresh) return SLAM2D_E_BADARG;       // (cannot happen: the fold read the same plan) never k_bound on stale minima
                 k_bound<<<(unsigned)cdiv(P, 8) * 8 * cdiv(lv.ntheta, BOUND_GROUP), WAVE * BOUND_GROUP, 0, s>>>(lv, P);
+            }
         }
         {
             StageScope prof(SLAM2D_STAGE_EXACT, s);
