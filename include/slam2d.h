@@ -492,7 +492,9 @@ int slam2d_scan_commit_next(const Slam2dLidar* lidar, const Slam2dMap* d_maps, i
  * sum exp(2 (lw - max))] of this rank's N particles.  The caller all-gathers the 24 bytes of every
  * rank (the only collective of a scan) and hands the [world][3] array to slam2d_weights_merge,
  * which folds it in rank order, writes this rank's normalised weights / log-weights and
- * d_stats[2] = [sum over ALL particles of (w - 1/total)^2, log of the pre-normalisation sum]. */
+ * d_stats[2] = [sum over ALL particles of (w - 1/total)^2, log of the pre-normalisation sum].
+ * slam2d_weights_local: a log-weight of -inf counts as weight 0 -- a rank of nothing but -inf leaves [-inf, 0, 0] -- a NaN makes the rank's sums NaN.
+ * slam2d_weights_merge: -inf particles get weight 0 and log-weight -inf if any particle of any rank is finite; one NaN, or -inf everywhere, makes every rank's weights and d_stats NaN. */
 int slam2d_weights_local(double* d_logw, const double* d_logconf, int32_t logconf_stride, int32_t N,
                          double* d_part, void* stream);
 int slam2d_weights_merge(double* d_logw, int32_t N, const double* d_parts, int32_t world,

@@ -3573,9 +3573,15 @@ __device__ __forceinline__ void weights_local_body(double* logw, const double* _
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] = fmax(red[tid], red[tid + o]); __syncthreads(); }
     mx = red[0];
     __syncthreads();
+    // A log-weight of -inf is weight 0 whatever the shard's maximum: with every entry -inf, exp(-inf - (-inf)) would be NaN, the
+    // merges' NaN * exp(-inf - gm) = NaN * 0 too, and every rank's weights with it -- k_weights gives those particles 0 as long as
+    // one particle anywhere is finite.  Such a shard leaves [-inf, 0, 0], the empty partial: the merges add 0 * 0.  A NaN entry is
+    // not -inf: it still reaches the sums (fmax drops it from the maximum), and -inf everywhere is still NaN after the merges (their scale is
+    // exp(-inf - (-inf)) then), like k_weights' 0 / 0.
     double s1 = 0.0, s2 = 0.0;
     for (int i = tid; i < N; i += 256) {
-        const double e = exp(logw[i] - mx);
+        const double v = logw[i];
+        const double e = v == -INFINITY ? 0.0 : exp(v - mx);
         s1 += e;
         s2 += e * e;
     }

@@ -1011,6 +1011,9 @@ class ParticleFilter:
     # The reference's resample trigger (:37) sits at total degeneracy: variance > ((N-1)/N)^2 + (N-1-1e-15)/N^2,
     # i.e. within ~1e-15 of the largest value sum (w - 1/N)^2 can take.  A variance more than this far below
     # that maximum cannot trigger, whatever the rounding of the reference's sequential sum:
+    # (Inside it the decision is the reference's wherever the smallest weight ratio eps is not 1e-15 .. 1e-17 -- the device's log-domain
+    # weights decide like the reference's linear ones for eps >= 1e-14 and <= 1e-18, tests/test_gpu_normaliser.py; in between the last
+    # bit of exp / log against a division decides, and a NumPy restatement of the same arithmetic already differs from :37 there.)
     _DEGENERACY_BAND = 1e-9
 
     def normalizeWeights(self):

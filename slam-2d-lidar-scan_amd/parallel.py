@@ -54,7 +54,9 @@ def normalize_sharded(logw_local, total, group=None):
     reduction order of the network, and the per-scan cost is one xGMI latency."""
     dev = logw_local.device
     m = logw_local.max() if logw_local.numel() else logw_local.new_tensor(-math.inf)
-    e = torch.exp(logw_local - m)
+    # (a log-weight of -inf is weight 0 even on a rank whose every entry is -inf, where exp(-inf - (-inf)) would be NaN and make every
+    # rank's weights NaN in the merge: weights_local_body in csrc/slam2d.hip does the same; a NaN entry stays NaN)
+    e = torch.where(logw_local == -math.inf, torch.zeros_like(logw_local), torch.exp(logw_local - m))
     mine = torch.stack((m, e.sum(), (e * e).sum()))
     if dist.is_initialized() and dist.get_world_size(group) > 1:
         world = dist.get_world_size(group)

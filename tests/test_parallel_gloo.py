@@ -63,6 +63,57 @@ def test_sharded_normaliser_and_migration(tmp_path, world, total):
     assert seen == total
 
 
+def _neginf_worker(rank, world, port, total, seed, dead, out_dir):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        logw_all = torch.from_numpy(_neginf_logw(total, world, seed, dead))
+        first, count = par.shard_range(total, world, rank)
+        w, logw, var = par.normalize_sharded(logw_all[first:first + count].clone(), total)
+        torch.save(dict(w=w, logw=logw, var=var), os.path.join(out_dir, f"r{rank}.pt"))
+    finally:
+        dist.destroy_process_group()
+
+
+def _neginf_logw(total, world, seed, dead):
+    """Seeded log-weights; the ranks in ``dead`` hold nothing but -inf, and one more entry elsewhere is -inf."""
+    logw = np.random.RandomState(seed).uniform(-400, -20, total)
+    alive = [r for r in range(world) if r not in dead]
+    for r in dead:
+        first, count = par.shard_range(total, world, r)
+        logw[first:first + count] = -np.inf
+    first, count = par.shard_range(total, world, alive[0])
+    if count > 1:
+        logw[first] = -np.inf
+    return logw
+
+
+@pytest.mark.parametrize("world,total,dead", [(2, 7, (0,)), (2, 8, (1,)), (3, 10, (0, 2)), (3, 4, (1,))])
+def test_sharded_normaliser_with_a_rank_of_minus_infinity(tmp_path, world, total, dead):
+    """A rank whose log-weights are all -inf while another rank holds finite ones: those particles get weight 0 and log-weight
+    -inf, everybody else the single-process normaliser's values, on EVERY rank -- not NaN everywhere (exp(-inf - (-inf)) in the
+    rank-local half).  The HIP kernels (weights_local_body) and this torch restatement agree on it."""
+    seed = 23
+    mp.spawn(_neginf_worker, args=(world, _free_port(), total, seed, dead, str(tmp_path)), nprocs=world, join=True)
+    logw_all = _neginf_logw(total, world, seed, dead)
+    w_ref = np.exp(logw_all - logw_all.max()); w_ref /= w_ref.sum()
+    var_ref = ((w_ref - 1 / total) ** 2).sum()
+    assert (w_ref == 0).sum() >= sum(par.shard_range(total, world, r)[1] for r in dead) and np.isfinite(var_ref)
+    for r in range(world):
+        o = torch.load(os.path.join(str(tmp_path), f"r{r}.pt"))
+        first, count = par.shard_range(total, world, r)
+        np.testing.assert_allclose(o["w"].numpy(), w_ref[first:first + count], rtol=1e-12, atol=0)
+        assert np.array_equal(o["logw"].numpy() == -np.inf, w_ref[first:first + count] == 0)
+        np.testing.assert_allclose(np.exp(o["logw"].numpy()), w_ref[first:first + count], rtol=1e-10, atol=0)
+        np.testing.assert_allclose(float(o["var"]), var_ref, rtol=1e-9)
+
+
+def test_sharded_normaliser_all_minus_infinity_is_nan():
+    """-inf everywhere stays the reference's 0/0: NaN weights (normalizeWeights raises on them), with or without a group."""
+    w, logw, var = par.normalize_sharded(torch.full((5,), -np.inf, dtype=torch.float64), 5)
+    assert torch.isnan(w).all() and torch.isnan(var)
+
+
 def _uneven_particle(i, seed):
     """Particle i of a seeded population whose maps have grown unevenly: its own extent, coordinate vectors
     (high-side growth compresses the spacing, Utils/OccupancyGrid.py:79-80), growth log, pose, heading, trajectory."""
