@@ -15,8 +15,9 @@
  *   - every pointer named d_* (and every pointer inside the structs) is DEVICE memory
  *     owned by the caller (the Python side allocates it as torch tensors);
  *     the library allocates no device memory and keeps no state between calls -- except the sleeping host threads of
- *     slam2d_groups_* (one per particle group beyond the first, created on first use; SLAM2D_GROUP_THREADS=0: none) and
- *     the event pairs of slam2d_prof_*.  The slam2d_groups_* calls are not re-entrant (one caller at a time).
+ *     slam2d_groups_* (one per particle group beyond the first, created on first use; SLAM2D_GROUP_THREADS=0: none),
+ *     the event pairs of slam2d_prof_* and the queue classes of the last slam2d_streams_create batch (which also owns, for
+ *     its duration, two pinned words for its probe).  The slam2d_groups_* calls are not re-entrant (one caller at a time).
  *   - every call enqueues work on `stream` (a hipStream_t passed as void*) and returns
  *     without synchronising; results are ordered after the call on that stream.
  *   - return value: 0 on success, otherwise a hipError_t code (> 0) or a
@@ -720,9 +721,21 @@ void slam2d_prof_disable(void);
 /* Ordering between streams for a host driver that runs groups of particles on several HIP streams (particles are
  * independent during a scan, Algorithm/FastSlam.py:25-27; only the weight normaliser, :30-48, joins them): events without
  * timing.  slam2d_event_record marks a point of `stream`; slam2d_stream_wait_event makes later work of `stream` wait for it. */
-/* n non-blocking streams created in one batch and each used once, so that they sit on distinct hardware queues (up to the
- * runtime's GPU_MAX_HW_QUEUES): the streams of particle groups.  A host driver creates them ONCE per process and reuses them. */
+/* n non-blocking streams for particle groups, PLACED on the runtime's hardware queues by measurement (round 8; before: created in one
+ * batch and hoped to land on distinct queues -- at the runtime's default of four queues two groups of four shared one and took turns).
+ * A bounded overlap probe (a ~150 us spin kernel on one stream, a time stamp on the other: the stamp precedes the spin's end only on
+ * another queue) sorts the streams into queue classes; where the batch holds fewer than four classes, further streams and then
+ * streams at the greatest priority are created, probed, and destroyed again if not handed out.  out[1..4] sit on pairwise distinct
+ * queues (the group streams of a two- and of a four-group run); out[0] (the normaliser's) not on the queue of out[1] or out[2]; the
+ * rest in any order.  Where four queues cannot be had (GPU_MAX_HW_QUEUES below 4) the best placement found is returned: no error.
+ * More than four groups still take turns at four queues: an application that can should set GPU_MAX_HW_QUEUES=8 before its first
+ * HIP call.  Costs about 10 ms (the first batch of a process 20-160 ms); a host driver calls it ONCE per process and device and reuses the streams.
+ * slam2d_streams_queue_classes: for n streams, the queue class of each in the LAST batch (-1: not of it) and the number of classes
+ * that batch found; stats is NULL or 6 words: tier that supplied the last class (0 the plain batch, 1 further streams, 2 priority
+ * streams), probes run, candidates created, candidates destroyed, microseconds taken, streams among out[1..4] that share a queue
+ * with an earlier one.  It makes no HIP call.  (An added symbol: no struct and no existing signature changed, the ABI number stays.) */
 int   slam2d_streams_create(void** out, int32_t n);
+int   slam2d_streams_queue_classes(void* const* streams, int32_t n, int32_t* out_class, int32_t* n_classes, int32_t* stats);
 void  slam2d_stream_destroy(void* stream);
 void* slam2d_event_create(void);
 void  slam2d_event_destroy(void* event);

@@ -19,7 +19,8 @@ __version__ = "0.1.0"
 # (Importing this package changes nothing in the process's environment.  Particle groups run on their own HIP streams, and streams
 # that share a hardware queue take turns: the HIP runtime spreads a process's streams over GPU_MAX_HW_QUEUES = 4 queues unless the
 # APPLICATION sets the variable before its first HIP call -- bench.py and the examples set 8; engine.group_streams() sets it only
-# when HIP has not been initialised yet and otherwise says so once.  INTEGRATION.md, "environment".)
+# when HIP has not been initialised yet.  At 4 queues the library still places up to four group streams on a queue each, by a
+# measured probe (slam2d_streams_create), and group_streams() warns where it could not.  INTEGRATION.md, "environment".)
 
 _LAZY = {
     "OccupancyGrid": ("grid", "OccupancyGrid"),

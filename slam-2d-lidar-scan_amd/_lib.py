@@ -198,6 +198,7 @@ SIGNATURES = {
     "slam2d_prof_every": (C.c_int, [C.c_int32]),
     "slam2d_prof_disable": (None, []),
     "slam2d_streams_create": (C.c_int, [C.POINTER(_vp), C.c_int32]),
+    "slam2d_streams_queue_classes": (C.c_int, [C.POINTER(_vp), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "slam2d_stream_destroy": (None, [_vp]),
     "slam2d_event_create": (_vp, []),
     "slam2d_event_destroy": (None, [_vp]),

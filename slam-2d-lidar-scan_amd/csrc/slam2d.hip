@@ -5388,22 +5388,194 @@ int slam2d_stream_wait_event(void* stream, void* event) { return event ? (int)hi
 
 // ---- a batch of streams for particle groups ----
 // Which HARDWARE queue a HIP stream sits on decides whether two groups overlap or take turns: the runtime keeps at most
-// GPU_MAX_HW_QUEUES of them and hands a new stream the least-referenced one.  Streams created one after the other, in one batch and
-// each used once at once, land on distinct queues (up to that limit); streams picked one by one out of a framework's round-robin pool
-// at different times do not (round 5: the closed loop in four groups ran 0.21 s with the first five pooled streams of a process and
-// 0.42-0.50 s with the pool's later ones; the bench's probe legs 0.12 against 0.25 ms per scan).
+// GPU_MAX_HW_QUEUES of them (4 unless the application sets more before its first HIP call) and decides itself which one a new stream
+// gets.  Creating the streams in one batch and using each once at once is not enough: at four queues the nine streams of a batch
+// came out with the four group streams on TWO queues, two groups alternating on each (round 8: config 2 in four groups 0.185 ms per
+// step against 0.11 on a queue each; round 5 had seen the same with pooled streams: 0.42-0.50 s against 0.21 s in the closed loop).
+// So the batch is PLACED BY MEASUREMENT.  The probe: k_spin (one wave, busy for PROBE_SPAN_TICKS of the 100 MHz wall clock, or
+// PROBE_SPIN_CAP iterations whatever the clock does) on stream a, then k_stamp on stream b, both synchronised, ticks read from a
+// pinned buffer.  The stamp precedes the spin's end only if b's queue is not a's -- one in-order queue starts nothing of b before a's
+// kernel ends, so "distinct" is never wrong; "same" can be an unlucky moment (the host descheduled between the two launches, a busy
+// device) and is believed only after PROBE_TRIES times.  No kernel waits for another; each ends by itself.
+// Candidates are sorted into queue classes against one representative per class (candidates x classes probes, not all pairs), in
+// three tiers: (0) the n streams created as before; (1) up to n further non-blocking streams, one at a time, while fewer than four
+// classes are known; (2) up to n streams at the device's greatest stream priority -- the runtime keeps a queue pool per priority (round 8:
+// measured so at one to three queues); the probe decides whether that holds.  Placement: out[1..4] (the group streams of a four- and of a two-group run) on pairwise distinct
+// queues; then out[0] (the normaliser's, busy beside two groups on a sharded rank) not on the queue of out[1] or out[2]; the rest in
+// creation order.  Tier-0 streams are preferred in creation order, so a batch whose streams already sit on distinct queues (eight
+// queues) comes out exactly as created.  Fewer than four classes after all tiers: the best placement found, not an error.
+// Bound: at most 3n candidates, each probed against at most PROBE_MAX_CLASSES representatives, a "same" up to PROBE_TRIES times:
+// 3n x 8 x 3 probes of ~0.2 ms (n = 9: 648 probes, 0.13 s; measured: profiles/r08_group_queues.md) -- once per process and device.
+constexpr long long PROBE_SPAN_TICKS = 15000;        // 150 us of the 100 MHz constant clock
+constexpr int PROBE_SPIN_CAP = 200000;               // clock reads: the span needs a few thousand; a stuck clock ends after a few ms
+constexpr int PROBE_TRIES = 3, PROBE_MAX_CLASSES = 8;
 __global__ void k_touch() {}
+__global__ void k_spin(long long* ticks) {
+    if (threadIdx.x != 0) return;
+    const long long t0 = (long long)wall_clock64();
+    long long t = t0;
+    for (int i = 0; i < PROBE_SPIN_CAP && t - t0 < PROBE_SPAN_TICKS; ++i) t = (long long)wall_clock64();
+    ticks[0] = t;
+}
+__global__ void k_stamp(long long* ticks) { if (threadIdx.x == 0) ticks[1] = (long long)wall_clock64(); }
+
+namespace {
+struct StreamBatch {                                 // the last batch of slam2d_streams_create, for slam2d_streams_queue_classes
+    std::mutex m;
+    void* stream[64];
+    int32_t cls[64];
+    int32_t n = 0, n_classes = 0;
+    int32_t stats[6] = {0, 0, 0, 0, 0, 0};           // tier, probes, created, destroyed, microseconds, streams placed on a shared queue among out[1..4]
+} g_batch;
+
+// 1: b's queue is not a's; 0: no overlap seen in PROBE_TRIES probes; < 0: -hipError_t
+int probe_distinct(hipStream_t a, hipStream_t b, long long* ticks, int32_t* probes) {
+    for (int t = 0; t < PROBE_TRIES; ++t) {
+        ticks[0] = 0; ticks[1] = 0;
+        k_spin<<<1, 64, 0, a>>>(ticks);
+        k_stamp<<<1, 64, 0, b>>>(ticks);
+        hipError_t e = hipGetLastError();
+        const hipError_t ea = hipStreamSynchronize(a), eb = hipStreamSynchronize(b);
+        if (e == hipSuccess) e = ea != hipSuccess ? ea : eb;
+        if (e != hipSuccess) return -(int)e;
+        ++*probes;
+        const volatile long long* v = ticks;
+        if (v[1] < v[0]) return 1;
+    }
+    return 0;
+}
+}  // namespace
+
 int slam2d_streams_create(void** out, int32_t n) {
     if (!out || n <= 0 || n > 64) return SLAM2D_E_BADARG;
+    constexpr int MAXC = 3 * 64;
+    hipStream_t cand[MAXC];
+    int cls[MAXC], nc = 0, ncls = 0, tier = 0;
+    hipStream_t rep[PROBE_MAX_CLASSES];
+    int32_t probes = 0, created = 0, destroyed = 0;
+    long long* ticks = nullptr;
+    const auto t_begin = std::chrono::steady_clock::now();
+    hipError_t err = hipSuccess;
+    auto fail = [&](hipError_t e) {
+        for (int j = 0; j < nc; ++j) (void)hipStreamDestroy(cand[j]);
+        if (ticks) (void)hipHostFree(ticks);
+        return (int)e;
+    };
+    // classify cand[i]: the class of the first representative it does not overlap with, or a new class (beyond PROBE_MAX_CLASSES: the last)
+    auto classify = [&](int i) -> hipError_t {
+        for (int k = 0; k < ncls; ++k) {
+            const int d = probe_distinct(rep[k], cand[i], ticks, &probes);
+            if (d < 0) return (hipError_t)(-d);
+            if (d == 0) { cls[i] = k; return hipSuccess; }
+        }
+        if (ncls < PROBE_MAX_CLASSES) { rep[ncls] = cand[i]; cls[i] = ncls++; }
+        else cls[i] = PROBE_MAX_CLASSES - 1;
+        return hipSuccess;
+    };
+    // tier 0: the batch as it has always been made
     for (int i = 0; i < n; ++i) {
         hipStream_t st;
         const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        if (e != hipSuccess) { for (int j = 0; j < i; ++j) (void)hipStreamDestroy((hipStream_t)out[j]); return (int)e; }
-        out[i] = (void*)st;
+        if (e != hipSuccess) return fail(e);
+        cand[nc++] = st; ++created;
         k_touch<<<1, 64, 0, st>>>();                   // (first use = queue assignment, in creation order)
     }
-    for (int i = 0; i < n; ++i) (void)hipStreamSynchronize((hipStream_t)out[i]);
+    for (int i = 0; i < n; ++i) (void)hipStreamSynchronize(cand[i]);
+    if ((err = hipGetLastError()) != hipSuccess) return fail(err);
+    if ((err = hipHostMalloc((void**)&ticks, 2 * sizeof(long long), hipHostMallocPortable)) != hipSuccess) { ticks = nullptr; return fail(err); }
+    // the group streams are looked for from element 1 on, so classify in that order: 1 .. n-1, then 0
+    for (int j = 0; j < n; ++j) if ((err = classify((j + 1) % n)) != hipSuccess) return fail(err);
+    const int want = n - 1 < 4 ? n - 1 : 4;            // distinct queues asked for
+    // tier 1: further plain streams; tier 2: streams at the greatest priority
+    int lo = 0, hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+    for (int t = 1; t <= 2 && ncls < want; ++t) {
+        if (t == 2 && hi == 0) break;                  // (no second priority level on this device)
+        for (int j = 0; j < n && ncls < want; ++j) {
+            hipStream_t st;
+            const hipError_t e = t == 1 ? hipStreamCreateWithFlags(&st, hipStreamNonBlocking) : hipStreamCreateWithPriority(&st, hipStreamNonBlocking, hi);
+            if (e != hipSuccess) return fail(e);
+            cand[nc++] = st; ++created;
+            k_touch<<<1, 64, 0, st>>>();
+            (void)hipStreamSynchronize(st);
+            const int before = ncls;
+            if ((err = classify(nc - 1)) != hipSuccess) return fail(err);
+            if (ncls > before) tier = t;
+        }
+    }
+    (void)hipHostFree(ticks); ticks = nullptr;
+    // placement
+    int pick[64], used[MAXC] = {0};
+    for (int i = 0; i < n; ++i) pick[i] = -1;
+    bool cls_used[PROBE_MAX_CLASSES] = {false};
+    int order[MAXC];                                   // candidates in the order of preference: 1 .. n-1, 0, then the later tiers
+    for (int j = 0; j < n; ++j) order[j] = (j + 1) % n;
+    for (int j = n; j < nc; ++j) order[j] = j;
+    for (int s = 1; s <= want; ++s)                    // out[1..4]: one stream of each class, while classes last
+        for (int j = 0; j < nc; ++j) {
+            const int c = order[j];
+            if (!used[c] && !cls_used[cls[c]]) { pick[s] = c; used[c] = 1; cls_used[cls[c]] = true; break; }
+        }
+    // out[0]: a free stream of a class no group stream has; else of a class other than out[1]'s and out[2]'s (moving that class's group
+    // stream to out[3] / out[4] where it sits at out[1] / out[2]); candidate 0 first
+    {
+        int best = -1, best_rank = 3;
+        for (int j = -1; j < nc; ++j) {
+            const int c = j < 0 ? 0 : order[j];
+            if (used[c]) continue;
+            int rank = cls_used[cls[c]] ? 1 : 0;
+            if (rank == 1) {                           // its class holds a group stream: usable if that stream can sit at out[3] or out[4]
+                int at = 0, groups = 0;
+                for (int s = 1; s <= want; ++s) if (pick[s] >= 0) { ++groups; if (cls[pick[s]] == cls[c]) at = s; }
+                if (at <= 2 && groups < 3) rank = 2;
+            }
+            if (rank < best_rank) { best = c; best_rank = rank; }
+        }
+        if (best >= 0) {
+            pick[0] = best; used[best] = 1;
+            for (int s = 1; s <= 2 && s <= want; ++s)
+                if (pick[s] >= 0 && cls[pick[s]] == cls[best])
+                    for (int u = want; u >= 3; --u)
+                        if (pick[u] >= 0 && cls[pick[u]] != cls[best]) { const int tmp = pick[s]; pick[s] = pick[u]; pick[u] = tmp; break; }
+        }
+    }
+    int shared = 0, groups_on[PROBE_MAX_CLASSES] = {0};
+    for (int s = 1; s <= want; ++s) if (pick[s] >= 0) ++groups_on[cls[pick[s]]];
+    for (int s = 0; s < n; ++s) {                      // whatever is still open: the free stream on the queue with the fewest group streams
+        if (pick[s] >= 0) continue;
+        int best = -1;
+        for (int j = 0; j < nc; ++j) {
+            const int c = order[j];
+            if (!used[c] && (best < 0 || (s >= 1 && s <= 4 && groups_on[cls[c]] < groups_on[cls[best]]))) best = c;
+        }
+        pick[s] = best; used[best] = 1;
+        if (s >= 1 && s <= 4 && groups_on[cls[best]]++ > 0) ++shared;
+    }
+    for (int j = 0; j < nc; ++j) if (!used[j]) { (void)hipStreamDestroy(cand[j]); ++destroyed; }
+    {
+        std::lock_guard<std::mutex> lk(g_batch.m);
+        g_batch.n = n; g_batch.n_classes = ncls;
+        for (int i = 0; i < n; ++i) { out[i] = (void*)cand[pick[i]]; g_batch.stream[i] = out[i]; g_batch.cls[i] = cls[pick[i]]; }
+        g_batch.stats[0] = tier; g_batch.stats[1] = probes; g_batch.stats[2] = created; g_batch.stats[3] = destroyed;
+        g_batch.stats[4] = (int32_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_begin).count();
+        g_batch.stats[5] = shared;
+    }
     return launch_status();
+}
+// The queue class of each of `streams` in the last batch of slam2d_streams_create (-1: not of that batch) and the number of classes
+// that batch found.  stats (NULL, or 6 words): the tier that supplied the last class (0 the plain batch, 1 further streams, 2 priority
+// streams), probes run, candidate streams created, candidates destroyed again, microseconds the batch took, group streams (elements
+// 1..4) that had to share a queue.  No HIP call: works without a device.
+int slam2d_streams_queue_classes(void* const* streams, int32_t n, int32_t* out_class, int32_t* n_classes, int32_t* stats) {
+    if (!streams || !out_class || !n_classes || n <= 0 || n > 64) return SLAM2D_E_BADARG;
+    std::lock_guard<std::mutex> lk(g_batch.m);
+    for (int i = 0; i < n; ++i) {
+        out_class[i] = -1;
+        for (int j = 0; j < g_batch.n; ++j) if (streams[i] && g_batch.stream[j] == streams[i]) { out_class[i] = g_batch.cls[j]; break; }
+    }
+    *n_classes = g_batch.n_classes;
+    if (stats) for (int i = 0; i < 6; ++i) stats[i] = g_batch.stats[i];
+    return 0;
 }
 void slam2d_stream_destroy(void* stream) { if (stream) (void)hipStreamDestroy((hipStream_t)stream); }
 

@@ -85,34 +85,45 @@ class _on_launch_stream:
 
 
 _GROUP_STREAMS = {}
+_GROUP_QUEUE_CLASSES = {}          # device -> hardware queue classes the first batch reached (slam2d_streams_queue_classes)
+_GROUP_WARNED = set()
 
 
 def group_streams(device, n):
     """``n`` HIP streams for particle groups (+ the normaliser's), created ONCE per device -- the first call makes a batch of
-    nine through the library (slam2d_streams_create: created and first used one after the other, so that they land on distinct
-    hardware queues) -- and handed out again to every later caller.  Which hardware queue a stream sits on decides how well the
-    groups overlap, and streams taken one by one out of torch's round-robin pool of 32 end up sharing queues: the twelfth set of
-    three fresh streams in one process measured 0.146 ms per step against 0.130 for the first eleven (round 4), the closed loop in
-    four groups 0.42-0.50 s against 0.21 s when two of its streams were taken from the pool later than the others (round 5)."""
+    nine through the library -- and handed out again to every later caller.  Which hardware queue a stream sits on decides how well
+    the groups overlap, and neither streams taken one by one out of torch's round-robin pool of 32 nor streams created in one batch
+    land on distinct queues by themselves (round 4: the twelfth set of three fresh streams in one process 0.146 ms per step against
+    0.130; round 5: the closed loop in four groups 0.42-0.50 s against 0.21 s; round 8: the batch's four group streams on two of the
+    runtime's default four queues, 0.185 ms per step against 0.11).  slam2d_streams_create therefore PLACES the batch with a measured
+    overlap probe: elements 1..4 (the group streams) on pairwise distinct hardware queues, element 0 (the normaliser's) not on the
+    queue of element 1 or 2.  More than four groups still take turns at four queues; where fewer than four queues could be reached
+    and more than two groups are asked for, this says so once."""
     dev = torch.device(device)
     key = str(dev)
     if n > 3 and "GPU_MAX_HW_QUEUES" not in os.environ and not _GROUP_STREAMS:
-        # more than two groups (+ the normaliser's stream) need more than the runtime's default of 4 hardware queues, and the
-        # runtime reads the variable when it initialises: this is the last place where this library can still set it -- if no HIP
-        # call has been made yet.  Otherwise the application has to (before importing torch.cuda work): say so, once.
+        # more than four groups (or four beside a busy normaliser stream) want more than the runtime's default of 4 hardware queues,
+        # and the runtime reads the variable when it initialises: this is the last place where this library can still set it -- if
+        # no HIP call has been made yet
         if not torch.cuda.is_initialized():
             os.environ["GPU_MAX_HW_QUEUES"] = "8"
-        else:
-            import warnings
-            warnings.warn("slam2d: %d particle-group streams on the HIP runtime's default of 4 hardware queues (HIP is already initialised): "
-                          "groups that share a queue take turns; set GPU_MAX_HW_QUEUES=8 before the process's first HIP call" % n, RuntimeWarning, stacklevel=2)
     have = _GROUP_STREAMS.setdefault(key, [])
     while len(have) < n:
-        k = max(9 if not have else 0, n - len(have))
+        first = not have
+        k = max(9 if first else 0, n - len(have))
         out = (C.c_void_p * k)()
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().slam2d_streams_create(out, k), "slam2d_streams_create")
         have.extend(torch.cuda.ExternalStream(int(p), device=dev) for p in out)
+        if first:
+            cls, ncls = (C.c_int32 * k)(), C.c_int32(0)
+            _lib.check(_lib.lib().slam2d_streams_queue_classes(out, k, cls, C.byref(ncls), None), "slam2d_streams_queue_classes")
+            _GROUP_QUEUE_CLASSES[key] = ncls.value
+    if n > 3 and _GROUP_QUEUE_CLASSES.get(key, 4) < 4 and key not in _GROUP_WARNED:
+        import warnings
+        _GROUP_WARNED.add(key)
+        warnings.warn("slam2d: %d particle-group streams, but only %d distinct hardware queues could be reached on %s: groups that share "
+                      "a queue take turns (GPU_MAX_HW_QUEUES below 4?)" % (n - 1, _GROUP_QUEUE_CLASSES[key], key), RuntimeWarning, stacklevel=2)
     return have[:n]
 
 
