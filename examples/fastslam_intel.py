@@ -28,6 +28,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--map-m", type=float, default=50.0)
     ap.add_argument("--png", default=None)
+    ap.add_argument("--ellipse", action="store_true", help="print the 1-sigma pose ellipse of the best particle's last match")
     args = ap.parse_args()
     pkg = importlib.import_module("slam-2d-lidar-scan_amd")
     dataio = importlib.import_module("slam-2d-lidar-scan_amd.dataio")
@@ -40,7 +41,15 @@ def main():
     n = min(args.scans, len(readings))
     for count, raw in enumerate(readings[:n], start=1):
         pf.updateParticles(raw, count)
-        if pf.weightUnbalanced():                                                   # FastSlam.py:160-162
+        unbalanced = pf.weightUnbalanced()
+        if args.ellipse and count == n and count > 1:
+            # (before a resample moves the particles) pose mean and covariance of the fine match over its whole pose cube
+            b = int(np.argmax(pf.weights))
+            mean, cov = pf.match_moments("fine")
+            ev, evec = np.linalg.eigh(cov[b][:2, :2])
+            print(f"scan {count}, particle {b}: mean pose {mean[b]}, 1-sigma ellipse {np.sqrt(np.maximum(ev, 0)) * 1e3} mm along "
+                  f"{np.degrees(np.arctan2(evec[1], evec[0]))} deg, sigma theta {np.degrees(np.sqrt(max(cov[b][2, 2], 0))):.3f} deg")
+        if unbalanced:                                                              # FastSlam.py:160-162
             pf.resample()
             resamples.append(count)
         if count % 100 == 0:

@@ -363,6 +363,45 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
                  double est_moving_dist, const double* d_psi_cs, const double* d_uniform,
                  Slam2dMatch* d_out, uint32_t* d_flags, uint32_t options, void* stream);
 
+/* Pose mean and covariance of a match over the WHOLE cube, in one pass (an added symbol: no struct and no existing signature
+ * changed, the ABI number stays).  Every pose (it, iy, ix) of the level's cube is scored again, exactly:
+ *     s = (-((double)sum_k field[cells[k] + iy*fpitch + ix] * (1/cost_scale)) + rv[iy][ix]) + tw[iy][ix]
+ * -- slam2d_sweep's expression over a 64-bit integer sum; an offset outside the particle's field reads 0 and never faults --
+ * weighted by w = exp(s - M), M = d_match[p].best_score, and reduced on the fly to the weighted first and second moments of the
+ * pose offsets (dx, dy, dtheta) = ((ix - ncell) * step, (iy - ncell) * step, thetas[it]).  level->cube is neither read nor
+ * written: after branch and bound it holds only the scored tiles, and what the skipped poses weigh (negligible for the
+ * confidence) is multiplied by offsets^2 of up to ncell^2 cells in a second moment.  The sums are taken about the arg-max pose
+ * (d_match[p].argmax) and shifted to the mean at the end; no floating-point atomics, a fixed order of summation: the same
+ * inputs give the same bits on every call, whichever path of slam2d_match produced them.
+ *
+ * PRECONDITION.  slam2d_match with any `options`, or slam2d_field_build followed by slam2d_sweep, has run for these P
+ * particles on `level`; nothing has written the level's workspaces since; this call is enqueued on the same stream or ordered
+ * after that work; d_match is that call's d_out and d_est the estimate it was given (d_est is not read on the device today: the
+ * offsets are relative to it).  What the call reads is then complete: level->cells / level->kcount (the unique endpoint cells
+ * of every angle, written by every path), level->prior (both planes at both levels; zeros at a fine level), level->thetas and
+ * level->field -- slam2d_match builds only the field tiles that the endpoint kernel marks in tileneed, but that kernel marks
+ * the tiles of every cell's WHOLE (2*ncell+1)^2 patch, i.e. every field cell some pose of the cube reads, whatever
+ * SLAM2D_MATCH_PRUNE_BY_PRIOR or the branch and bound then choose to score (a needed tile that holds the free-space constant
+ * holds it in the field, too).  The 16-byte load of the last slot of a pose row may touch cells beyond the patch; those lanes'
+ * values are discarded.
+ *
+ *   d_work: slam2d_match_moments_work(level, P) doubles of scratch
+ *           = P * ntheta * ceil((2*ncell+1) * ceil((2*ncell+1) / 4) / 64) * 12 (no HIP call; < 0: SLAM2D_E_*)
+ *   d_out[p*SLAM2D_MOMENTS_STRIDE + ...]:
+ *      0      sum of w
+ *      1-3    mean offset from the estimate (m, m, rad): the mean pose is d_est[p] + mean
+ *      4-9    covariance about the mean, normalised by sum w: xx, xy, xtheta, yy, ytheta, thetatheta (world axes)
+ *      10     M as used
+ *      11     number of poses summed (ntheta * (2*ncell+1)^2)
+ *      12     number of NaN scores (a NaN heading prior, Utils/ScanMatcher_OGBased.py:107); > 0: slots 0-9 are NaN
+ *      13-15  0
+ * No fault bit is raised: the call reads the level and writes only d_work and d_out.  SLAM2D_E_BADARG, before any HIP call:
+ * a NULL pointer, P <= 0, est_stride < 3, a level without field, cells, kcount, prior or thetas. */
+#define SLAM2D_MOMENTS_STRIDE 16
+int slam2d_match_moments(const Slam2dLevel* level, int32_t P, const double* d_est, int32_t est_stride,
+                         const Slam2dMatch* d_match, double* d_work, double* d_out, void* stream);
+int64_t slam2d_match_moments_work(const Slam2dLevel* level, int32_t P);
+
 /* updateOccupancyGrid for P particles (Utils/OccupancyGrid.py:127-159): one wave per beam walks
  * the cells of the beam's spoke up to the measured range (each window cell belongs to exactly
  * one spoke, each spoke to at most one beam, so the counts are updated without atomics).

@@ -10,7 +10,8 @@ with ``importlib.import_module("slam-2d-lidar-scan_amd")`` or through the
 ``OccupancyGrid`` / ``ScanMatcher`` keep the reference's class surface
 (Utils/OccupancyGrid.py, Utils/ScanMatcher_OGBased.py); ``ParticleFilter`` is the
 batched counterpart of Algorithm/FastSlam.py's.  ``map_from_poses`` builds the map of a log at
-given poses (Utils/OccupancyGrid.py:main).  All of them need the HIP library
+given poses (Utils/OccupancyGrid.py:main).  ``ScanMatcher.matchMoments`` / ``ParticleFilter.match_moments`` give the pose
+mean and covariance of the last match over its whole pose cube (``ParticleEngine.match_moments``).  All of them need the HIP library
 (``libslam2d_hip.so``, built by ``__graft_entry__.build()``) and a GPU; there is no
 CPU fallback.
 """

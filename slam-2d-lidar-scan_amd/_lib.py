@@ -52,6 +52,7 @@ MATCH_PRUNE_BY_PRIOR = 1
 MATCH_PRIOR_READY = 2
 PRUNE_MARGIN = 40.0
 BNB_MARGIN = 30.0
+MOMENTS_STRIDE = 16                  # doubles per particle of slam2d_match_moments' output row
 
 STAGE_SWEEP, STAGE_BLUR, STAGE_SCATTER, STAGE_UPDATE, STAGE_SELECT, STAGE_ENDPOINTS, STAGE_BOUND, STAGE_EXACT = range(8)
 STAGE_NAMES = {STAGE_SWEEP: "k_sweep", STAGE_BLUR: "k_blur_clamp", STAGE_SCATTER: "k_occ_scatter",
@@ -160,6 +161,8 @@ SIGNATURES = {
                                C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "slam2d_match": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), _vp, C.c_int32, _vp, C.c_int32, _vp,
                                C.c_double, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    "slam2d_match_moments": (C.c_int, [C.POINTER(Slam2dLevel), C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "slam2d_match_moments_work": (C.c_int64, [C.POINTER(Slam2dLevel), C.c_int32]),
     "slam2d_grid_update": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "slam2d_occ_extent": (C.c_int, [C.POINTER(Slam2dLidar), C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "slam2d_map_scans": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),

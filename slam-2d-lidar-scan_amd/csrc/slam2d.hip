@@ -4310,6 +4310,148 @@ __global__ void k_fill(uint32_t* cells, long long n, uint32_t value) {
 }
 
 // ------------------------------------------------------------------------------------
+// Pose mean and covariance of a match (slam2d_match_moments): every pose of the cube is scored again, exactly as k_sweep scores
+// it -- the same 64-bit integer sum over the unique endpoint cells, the same expression with the two prior planes -- and turned
+// into the weight w = exp(score - M), M = Slam2dMatch.best_score; the cube itself is neither read nor written (after branch and
+// bound it holds only the scored tiles, and the skipped poses' mass times offset^2 is not negligible for a second moment).
+// k_sweep's work shape: a block per (particle, theta, chunk of 64 slots), a lane owns the 4 consecutive dx of one slot through
+// one 16-byte buffer load per cell, the block's four waves split the cell list and meet in LDS.  Wave 0 then reduces
+// w, w * d, w * d d^T (d = offset from the ARG-MAX pose in metres / radians: the moments are shifted to the mean at the end,
+// where E[d d^T] - E[d] E[d]^T then subtracts numbers of the covariance's own size) with wave_sum -- a fixed order -- and leaves
+// one row of MOMENTS_ROW doubles per block in d_work.  k_moments_fold, one wave per particle, adds a particle's rows in index
+// order (a lane takes a contiguous run of rows, the lanes meet in wave_sum) and writes the SLAM2D_MOMENTS_STRIDE output doubles.
+// No atomics: the same inputs give the same bits on every call.
+// ------------------------------------------------------------------------------------
+#define MOMENTS_ROW 12               // sum w | sum w d (x, y, theta) | sum w d d^T (xx, xy, xt, yy, yt, tt) | poses | NaN scores
+__device__ __forceinline__ int moments_argmax(const Slam2dLevel& lv, const Slam2dMatch* __restrict__ match, const int p) {
+    const int nx = 2 * lv.ncell + 1;
+    const int a = match[p].argmax;
+    return (a >= 0 && a < lv.ntheta * nx * nx) ? a : 0;          // (a record nobody wrote: any pose serves as the origin)
+}
+__global__ __launch_bounds__(256) void k_moments(Slam2dLevel lv, int P, int chunks, int bpp, const Slam2dMatch* __restrict__ match,
+                                                 double* __restrict__ work) {
+    __shared__ unsigned long long part_s[3][WAVE * 4];
+    const int b = blockIdx.x;
+    const int xcd = b & 7, slot = b >> 3;                         // blocks of one particle share an XCD's L2, as in k_sweep
+    const int p = (slot / bpp) * 8 + xcd;
+    if (p >= P) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int w = slot % bpp;
+    const int it = w / chunks, ch = w - it * chunks;
+    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
+    const int nq = (nx + 3) >> 2, nslot = nx * nq;
+    const uint32_t* __restrict__ F = lv.field + (size_t)p * lv.fmax * lv.fpitch;
+    const int* __restrict__ cl = lv.cells + ((size_t)p * lv.ntheta + it) * lv.kmax;
+    const int K = min(lv.kcount[p * lv.ntheta + it], lv.kmax);
+    // k_sweep's buffer addressing: field base + per-lane byte offset + wave-uniform cell offset; beyond the particle's field: 0
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)F, (short)0, (int)((size_t)lv.fmax * lv.fpitch * sizeof(uint32_t)), 0x00020000);
+    const int u = ch * WAVE + lane;                               // the lane's slot
+    const int uu = u < nslot ? u : 0;
+    const int iy = uu / nq, dx = (uu - iy * nq) * 4;
+    const int off = (iy * lv.fpitch + dx) * 4;
+    const int q0 = iy * nx + dx;
+    const int nv = u < nslot ? min(4, nx - dx) : 0;               // valid poses of the slot (the last slot of a row: nx - dx)
+    unsigned lo[4] = {0u, 0u, 0u, 0u}, hi[4] = {0u, 0u, 0u, 0u};
+#pragma unroll 4
+    for (int k = wave; k < K; k += 4) {
+        const int cell = cl[k] * 4;
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, cell, 0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned s = lo[e] + v[e];
+            hi[e] += s < v[e] ? 1u : 0u;
+            lo[e] = s;
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) part_s[wave - 1][e * WAVE + lane] = ((unsigned long long)hi[e] << 32) | lo[e];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+    const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
+    const double inv = 1.0 / lv.cost_scale;
+    const double M = match[p].best_score;
+    const int am = moments_argmax(lv, match, p);
+    const int ita = am / npose, rema = am - ita * npose;
+    const int iya = rema / nx, ixa = rema - iya * nx;
+    const double dth = lv.thetas[it] - lv.thetas[ita];
+    const double dyv = (double)(iy - iya) * lv.step;
+    double prv[4], ptw[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int q = min(q0 + e, npose - 1);
+        prv[e] = pr[q];
+        ptw[e] = pr[npose + q];
+    }
+    double s0 = 0.0, sx = 0.0, sy = 0.0, st = 0.0, sxx = 0.0, sxy = 0.0, sxt = 0.0, syy = 0.0, syt = 0.0, stt = 0.0;
+    double cnt = 0.0, cnan = 0.0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e < nv) {
+            const unsigned long long acc = (((unsigned long long)hi[e] << 32) | lo[e]) + part_s[0][e * WAVE + lane] +
+                                           part_s[1][e * WAVE + lane] + part_s[2][e * WAVE + lane];
+            const double sum = -((double)acc * inv);
+            const double sc = (sum + prv[e]) + ptw[e];                              // :131, k_sweep's expression
+            const double wgt = exp(sc - M);
+            const double dxv = (double)(dx + e - ixa) * lv.step;
+            s0 += wgt;
+            sx += wgt * dxv; sy += wgt * dyv; st += wgt * dth;
+            sxx += wgt * (dxv * dxv); sxy += wgt * (dxv * dyv); sxt += wgt * (dxv * dth);
+            syy += wgt * (dyv * dyv); syt += wgt * (dyv * dth); stt += wgt * (dth * dth);
+            cnt += 1.0;
+            cnan += isnan(sc) ? 1.0 : 0.0;
+        }
+    }
+    double row[MOMENTS_ROW] = {s0, sx, sy, st, sxx, sxy, sxt, syy, syt, stt, cnt, cnan};
+#pragma unroll
+    for (int i = 0; i < MOMENTS_ROW; ++i) row[i] = wave_sum(row[i]);
+    if (lane == 0) {
+        double* dst = work + (((size_t)p * lv.ntheta + it) * chunks + ch) * MOMENTS_ROW;
+#pragma unroll
+        for (int i = 0; i < MOMENTS_ROW; ++i) dst[i] = row[i];
+    }
+}
+
+__global__ __launch_bounds__(64) void k_moments_fold(Slam2dLevel lv, int nrows, const Slam2dMatch* __restrict__ match,
+                                                     const double* __restrict__ work, double* __restrict__ out) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const double* __restrict__ rows = work + (size_t)p * nrows * MOMENTS_ROW;
+    const int per = (nrows + WAVE - 1) / WAVE;
+    const int r0 = min(nrows, lane * per), r1 = min(nrows, r0 + per);
+    double acc[MOMENTS_ROW];
+#pragma unroll
+    for (int i = 0; i < MOMENTS_ROW; ++i) acc[i] = 0.0;
+    for (int r = r0; r < r1; ++r)
+#pragma unroll
+        for (int i = 0; i < MOMENTS_ROW; ++i) acc[i] += rows[(size_t)r * MOMENTS_ROW + i];
+#pragma unroll
+    for (int i = 0; i < MOMENTS_ROW; ++i) acc[i] = wave_sum(acc[i]);
+    if (lane != 0) return;
+    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
+    const int am = moments_argmax(lv, match, p);
+    const int ita = am / npose, rema = am - ita * npose;
+    const int iya = rema / nx, ixa = rema - iya * nx;
+    double* o = out + (size_t)p * SLAM2D_MOMENTS_STRIDE;
+    const double s0 = acc[0];
+    const double mx = acc[1] / s0, my = acc[2] / s0, mt = acc[3] / s0;              // mean offset from the arg-max pose
+    o[0] = s0;
+    o[1] = (double)(ixa - lv.ncell) * lv.step + mx;                                // ... from the estimate
+    o[2] = (double)(iya - lv.ncell) * lv.step + my;
+    o[3] = lv.thetas[ita] + mt;
+    o[4] = acc[4] / s0 - mx * mx; o[5] = acc[5] / s0 - mx * my; o[6] = acc[6] / s0 - mx * mt;
+    o[7] = acc[7] / s0 - my * my; o[8] = acc[8] / s0 - my * mt; o[9] = acc[9] / s0 - mt * mt;
+    if (acc[11] > 0.0)                                                             // a NaN score: exp(NaN) made them NaN already
+        for (int i = 0; i < 10; ++i) o[i] = NAN;
+    o[10] = match[p].best_score;
+    o[11] = acc[10];
+    o[12] = acc[11];
+    o[13] = 0.0; o[14] = 0.0; o[15] = 0.0;
+}
+
+// ------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------
 static void launch_sweep(const Slam2dLevel& lv, int P, int chunks, hipStream_t s, int mode = 0, const double* sel_est = nullptr,
@@ -4719,6 +4861,42 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
     launch_endpoints(*lidar, lv, P, d_est, est_stride, d_ranges, est_moving_dist, d_psi_cs, d_flags, true, ring_chunks > 0, s, framed, own);
     if ((rc = launch_field(lv, d_maps, P, d_flags, true, s, !framed, ring_chunks > 0))) return rc;      // (the ring pass reads the field's maximum)
     if ((rc = launch_scores(lv, P, d_est, est_stride, d_uniform, d_out, s, ring_chunks))) return rc;
+    return launch_status();
+}
+
+// slots of 4 consecutive dx in chunks of 64, as launch_scores cuts a plane for k_sweep
+static int moments_chunks(const Slam2dLevel& lv) {
+    const int nx = 2 * lv.ncell + 1;
+    return cdiv(nx * ((nx + 3) / 4), WAVE);
+}
+static int check_moments_level(const Slam2dLevel* lv, int P) {
+    if (!lv || P <= 0) return SLAM2D_E_BADARG;
+    if (lv->fmax <= 0 || lv->fpitch < lv->fmax || lv->ncell < 0 || lv->ntheta <= 0 || lv->kmax <= 0 || !(lv->cost_scale > 0.0)) return SLAM2D_E_BADARG;
+    if ((long long)lv->fmax * lv->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;     // byte offsets into one field stay below 2^31
+    const long long nx = 2ll * lv->ncell + 1;
+    if (nx > 4096 || (long long)lv->ntheta * nx * nx >= (1ll << 31)) return SLAM2D_E_TOOLARGE;      // flat pose indices are int32
+    return 0;
+}
+
+int64_t slam2d_match_moments_work(const Slam2dLevel* level, int32_t P) {
+    const int rc = check_moments_level(level, P);
+    if (rc) return rc;
+    return (int64_t)P * level->ntheta * moments_chunks(*level) * MOMENTS_ROW;
+}
+
+int slam2d_match_moments(const Slam2dLevel* level, int32_t P, const double* d_est, int32_t est_stride,
+                         const Slam2dMatch* d_match, double* d_work, double* d_out, void* stream) {
+    if (!d_est || !d_match || !d_work || !d_out || est_stride < 3) return SLAM2D_E_BADARG;
+    const int rc = check_moments_level(level, P);
+    if (rc) return rc;
+    const Slam2dLevel& lv = *level;
+    if (!lv.field || !lv.cells || !lv.kcount || !lv.prior || !lv.thetas) return SLAM2D_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int chunks = moments_chunks(lv);
+    const int bpp = lv.ntheta * chunks;                                 // blocks (= rows of d_work) per particle
+    if ((long long)cdiv(P, 8) * 8 * bpp >= (1ll << 31)) return SLAM2D_E_TOOLARGE;
+    k_moments<<<(unsigned)cdiv(P, 8) * 8 * bpp, 256, 0, s>>>(lv, P, chunks, bpp, d_match, d_work);
+    k_moments_fold<<<P, WAVE, 0, s>>>(lv, bpp, d_match, d_work, d_out);
     return launch_status();
 }
 

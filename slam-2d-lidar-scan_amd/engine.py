@@ -719,6 +719,7 @@ class SearchLevel:
         self.rv_coef = -(1 / (2 * move_sigma ** 2))                               # :101
         self.tw_coef = -1 / (2 * turn_sigma ** 2)                                 # :108
         self.max_move_dev = max_move_dev
+        self.serial = 0                              # builds of this level's field so far (next_generation): who matched last
         npose = self.nx * self.nx
         self.npartial = self.ntheta * (-(-npose // 64))
         self.tmax = -(-self.fmax // 16)             # 16x16-cell tiles of the blur
@@ -859,6 +860,7 @@ class SearchLevel:
     def next_generation(self):
         """Advance the occupancy-image generation stamp (Slam2dLevel.occ_gen) for the next build: the
         image is zeroed once per 254 builds instead of at every build."""
+        self.serial += 1
         g = self.c.occ_gen + 1
         if g > 254:
             with _on_launch_stream():
@@ -915,6 +917,28 @@ class SearchLevel:
         off = self.t["cells"][p, it, :k].cpu().numpy()
         return off // self.fpitch + self.ncell, off % self.fpitch + self.ncell      # (cy, cx)
 
+    def moments_work(self):
+        """The scratch of slam2d_match_moments for this level's P particles, allocated at the first call and kept."""
+        w = self.t.get("moments_work")
+        if w is None:
+            n = _lib.lib().slam2d_match_moments_work(C.byref(self.c), self.P)
+            if n < 0:
+                check(int(n), "slam2d_match_moments_work")
+            w = self.t["moments_work"] = torch.zeros(int(n), dtype=torch.float64, device=self.device)
+        return w
+
+    @staticmethod
+    def moments_host(rows):
+        """Rows of slam2d_match_moments ([P, MOMENTS_STRIDE], tensor or array) as host arrays: dict(sum_w [P], mean [P,3] -- the
+        offset from the estimate in (m, m, rad) --, cov [P,3,3] symmetric, nan_count [P], best_score [P], poses [P])."""
+        r = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        r = r.reshape(-1, _lib.MOMENTS_STRIDE)
+        cov = np.empty((len(r), 3, 3))
+        for k, (i, j) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+            cov[:, i, j] = cov[:, j, i] = r[:, 4 + k]
+        return dict(sum_w=r[:, 0].copy(), mean=r[:, 1:4].copy(), cov=cov, nan_count=r[:, 12].astype(np.int64),
+                    best_score=r[:, 10].copy(), poses=r[:, 11].astype(np.int64))
+
     def algorithmic_bytes(self, n_window_cells=None):
         """SURVEY.md 8(d) per particle-scan at this level: field build
         2*c*Wm^2 + 4*Fh*Fw (c = 2 bytes per count: packed uint32 cell holds both),
@@ -941,6 +965,7 @@ class ParticleEngine:
         self.P = len(self.maps)
         self.flags = torch.zeros(self.P, dtype=torch.int32, device=self.device)
         self.match_buf = {}
+        self._built = {}                    # id(level) -> level.serial of this engine's last field build there (match_moments' callers)
         self.refresh_maps()
 
     def sync_bounds(self):
@@ -1022,6 +1047,7 @@ class ParticleEngine:
     def field_build(self, level, d_centre, stride):
         self.refresh_bits()
         level.next_generation()
+        self._built[id(level)] = level.serial
         check(self.L.slam2d_field_build(C.byref(self.lidar_c), C.byref(level.c), _ptr(self.d_maps), self.P,
                                         _ptr(d_centre), stride, _ptr(self.flags), _stream()), "slam2d_field_build")
 
@@ -1037,10 +1063,24 @@ class ParticleEngine:
         (SLAM2D_MATCH_PRUNE_BY_PRIOR; coarse level only; level.cube() then holds only the ring)."""
         self.refresh_bits()
         level.next_generation()
+        self._built[id(level)] = level.serial
         check(self.L.slam2d_match(C.byref(self.lidar_c), C.byref(level.c), _ptr(self.d_maps), self.P, _ptr(d_est),
                                   stride, _ptr(d_ranges), float(est_moving_dist), _ptr(d_psi_cs), _ptr(d_uniform),
                                   _ptr(d_out), _ptr(self.flags), _lib.MATCH_PRUNE_BY_PRIOR if prune else 0, _stream()),
               "slam2d_match")
+
+    def built_last(self, level):
+        """Whether this engine's build is the last one of `level`'s field (levels may be shared: matcher._shared_level)."""
+        return level.serial > 0 and self._built.get(id(level)) == level.serial
+
+    def match_moments(self, level, d_est, stride, d_match):
+        """Pose mean and covariance of the match that `match` (or `field_build` + `sweep`) left on `level`: [P, MOMENTS_STRIDE]
+        on the device (include/slam2d.h, slam2d_match_moments; ``SearchLevel.moments_host`` unpacks it).  d_est / d_match: the
+        estimate and the result buffer of that call.  Scores every pose of the cube again; reads nothing of level.cube()."""
+        out = torch.empty((self.P, _lib.MOMENTS_STRIDE), dtype=torch.float64, device=self.device)
+        check(self.L.slam2d_match_moments(C.byref(level.c), self.P, _ptr(d_est), stride, _ptr(d_match),
+                                          _ptr(level.moments_work()), _ptr(out), _stream()), "slam2d_match_moments")
+        return out
 
     def grid_update(self, d_pose, stride, d_ranges, d_beam_shift=None):
         self._before_update()

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, parallel
-from .engine import MATCH_DOUBLES, LidarModel, MapState, ParticleEngine, SearchLevel, pinned_stream, require_gpu, _ptr, _stream
+from .engine import MATCH_DOUBLES, LidarModel, MapState, ParticleEngine, SearchLevel, pinned_stream, require_gpu, _on_launch_stream, _ptr, _stream
 
 
 class ParticleView:
@@ -1161,6 +1161,27 @@ class ParticleFilter:
         self.all_weights = np.full(n, 1 / n)
         self.d_logw.fill_(math.log(1 / n))
         self.d_w.fill_(1 / n)
+
+    def match_moments(self, level="fine"):
+        """Pose mean and covariance of every particle's last match at one level, over the whole pose cube (include/slam2d.h,
+        slam2d_match_moments): ``(mean_pose [P,3], cov [P,3,3])`` in (m, m, rad) for this rank's particles.  Valid after
+        ``updateParticles`` (count > 1), however many groups ``run()`` would use: the groups' levels are views of the one level
+        this runs on.  Inside ``run()`` the next scan's speculative match has already overwritten the level when a scan's
+        results reach the host: it raises there."""
+        if level not in ("fine", "coarse"):
+            raise ValueError("level is 'fine' or 'coarse'")
+        lv = self.fine if level == "fine" else self.coarse
+        if not self.engine.built_last(lv):
+            raise _lib.Slam2dError(f"match_moments: the {level} level does not hold the last updateParticles' match (no scan matched "
+                                   "yet, or the level was rebuilt since: inside run() the next scan's speculative match has "
+                                   "already overwritten it when a scan's results reach the host)")
+        d_match = self.m_fine if level == "fine" else self.m_coarse
+        d_est, stride = (self.m_coarse, MATCH_DOUBLES) if level == "fine" else (self.d_est, 3)
+        with _on_launch_stream():
+            rows = self.engine.match_moments(lv, d_est, stride, d_match)
+            est = d_est[:, :3].cpu().numpy()
+        mom = lv.moments_host(rows)
+        return est + mom["mean"], mom["cov"]
 
     def best_particle(self):
         return self.particles[int(np.argmax(self.weights))]

@@ -185,6 +185,42 @@ class ScanMatcher:
             og._last_match = dict(ref=matched, pose=(matched["x"], matched["y"], matched["theta"]), rng=rMeasure, d_pose=m_fine, d_rng=d_rng, eng=eng)
             return matched, np.float64(c["confidence"])                            # :79
 
+    def matchMoments(self, level="fine"):
+        """Pose mean and covariance of the last ``matchScan`` (count > 1) of this matcher at one of its two levels, over the
+        whole pose cube (include/slam2d.h, slam2d_match_moments): ``dict(pose_mean=(x, y, theta), cov=3x3 in (m, m, rad),
+        sum_w, log_confidence)`` with log_confidence = best score + log(sum_w).  Runs on the state that match left on the
+        device.  The workspaces are shared by all matchers of one configuration (_shared_level): raises ``Slam2dError`` when
+        the level has been used by another match since -- never another grid's moments."""
+        if level not in ("fine", "coarse"):
+            raise ValueError("level is 'fine' or 'coarse'")
+        last = getattr(self, "last", None)
+        if not last or level not in last:
+            raise _lib.Slam2dError("matchMoments needs a matchScan (count > 1) of this matcher first")
+        lv = self.fine_level() if level == "fine" else self.coarse_level()
+        with _Exclusive(lv), pinned_stream():
+            eng = self.og._engine
+            io = getattr(eng, "_call_io", None) if eng is not None else None
+            if io is None or not eng.built_last(lv):
+                raise _lib.Slam2dError(f"the {level} level's shared workspace has been used by another match since this matcher's "
+                                       "last matchScan: match again first")
+            d_match = io.m_fine if level == "fine" else io.m_coarse
+            d_est, stride = (io.m_coarse, MATCH_DOUBLES) if level == "fine" else (io.d_in[0:3], 3)
+            rows = eng.match_moments(lv, d_est, stride, d_match)
+            # one download: the rows, and the records they were computed from (another matcher of this grid and configuration
+            # may have matched since: the records then are not this matcher's)
+            host = torch.cat([rows.reshape(-1), io.d_out[:2 * MATCH_DOUBLES]]).cpu().numpy()
+            m = host[_lib.MOMENTS_STRIDE:].view(_MATCH_DTYPE)
+            for name, rec in (("coarse", m[0]), ("fine", m[1])):
+                if name in last and rec.tobytes() != last[name].tobytes():
+                    raise _lib.Slam2dError("another matcher of this grid has matched since this matcher's last matchScan: "
+                                           "match again first")
+            mom = lv.moments_host(host[:_lib.MOMENTS_STRIDE])
+            est = (float(m[0]["x"]), float(m[0]["y"]), float(m[0]["theta"])) if level == "fine" else tuple(float(v) for v in io.h_in.numpy()[0:3])
+            mean = mom["mean"][0]
+            sum_w = float(mom["sum_w"][0])
+            return dict(pose_mean=(est[0] + mean[0], est[1] + mean[1], est[2] + mean[2]), cov=mom["cov"][0], sum_w=sum_w,
+                        log_confidence=float(mom["best_score"][0]) + math.log(sum_w) if sum_w > 0 else float("nan"))
+
     def searchToMatch(self, probSP, estimatedX, estimatedY, estimatedTheta, rMeasure, xRangeList, yRangeList,
                       searchRadius, searchHalfRad, unitLength, estMovingDist, estMovingTheta, fineSearch=False,
                       matchMax=True):
