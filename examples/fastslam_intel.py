@@ -2,7 +2,7 @@
 """BASELINE config 3: FastSLAM over the bundled Intel log (910 scans x 180 beams) with the batched
 GPU particle filter at the reference's defaults (Algorithm/FastSlam.py:197-207), map growth on.
 
-    python examples/fastslam_intel.py [--particles 64] [--scans 910] [--seed 0] [--png out.png]
+    python examples/fastslam_intel.py [--particles 64] [--scans 910] [--seed 0] [--png out.png] [--ellipse] [--residual]
 
 Prints throughput and a few sanity figures (resample count, final weight spread, map extent,
 trajectory length); optionally writes the best particle's map like the reference's per-scan PNG.
@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--map-m", type=float, default=50.0)
     ap.add_argument("--png", default=None)
     ap.add_argument("--ellipse", action="store_true", help="print the 1-sigma pose ellipse of the best particle's last match")
+    ap.add_argument("--residual", action="store_true", help="print how well the best particle's map predicts the last scan, per beam")
     args = ap.parse_args()
     pkg = importlib.import_module("slam-2d-lidar-scan_amd")
     dataio = importlib.import_module("slam-2d-lidar-scan_amd.dataio")
@@ -70,6 +71,16 @@ def main():
     m = pf.engine.maps[best]
     v, t = m.download()
     print(f"map {m.rows}x{m.cols}, occupied cells {(2 * v > t).sum()}, observed cells {(t > 2).sum()}, growth steps {len(m.growth_log)}")
+    if args.residual:
+        # the scan the best particle's own map expects at its last matched pose (ParticleFilter.predict_scans), against the measured one
+        pred = {k: a[best] for k, a in pf.predict_scans().items()}
+        rng = np.asarray(readings[n - 1]["range"], dtype=np.float64)
+        returned = rng < ogP[5]
+        both = returned & pred["hit"]
+        err = np.abs(rng - pred["range"])[both]
+        print(f"last scan, particle {best}: the map predicts {both.sum()} of {returned.sum()} returned beams "
+              f"({100 * both.sum() / max(returned.sum(), 1):.1f} %); |measured - predicted| median "
+              f"{np.median(err) if err.size else float('nan'):.3f} m, 90th percentile {np.percentile(err, 90) if err.size else float('nan'):.3f} m")
     if args.png:
         import matplotlib
         matplotlib.use("Agg")

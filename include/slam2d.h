@@ -445,6 +445,35 @@ int slam2d_map_scans(const Slam2dLidar* lidar, const Slam2dMap* d_map, int32_t S
                      const double* d_ranges, const Slam2dBeamPlan* d_plan, const uint16_t* d_lut_bin, const double* d_lut_r,
                      uint32_t* d_flags, void* stream);
 
+/* The scan a map expects at a pose, per beam: the inverse of updateOccupancyGrid in the update's own discretisation (an added
+ * symbol: no struct and no existing signature changed, the ABI number stays).  The update writes a beam's wall into the cells of ONE
+ * angular spoke of the window (Utils/OccupancyGrid.py:131-152), so the range a map predicts for the beam is the nearest occupied
+ * cell of that spoke -- a map predicts back exactly the walls the update put there.  For pose s = (x, y, theta) in map
+ * d_maps[s * map_stride] (map_stride 1: one map per pose, the filter's P particles in P maps; 0: every pose in map 0) and beam b:
+ *   1. spoke = (spoke_start + (int)rint(theta / (2 pi) * num_spokes) + b) mod num_spokes, in [0, num_spokes): the heading is
+ *      quantised to the angular step, as in the update (:131,134);
+ *   2. every cell k of that spoke, window row i, column j, radius r_k = spoke_r[k], has the map index
+ *      mx = rint(((x + lut_xs[j]) - lim_x0) / unit), my = rint(((y + lut_xs[i]) - lim_y0) / unit)  (convertRealXYToMapIdx,
+ *      :104-105,144-145; the kernel's shortcuts give these integers);
+ *   3. cell k is a HIT iff 0 <= mx < cols, 0 <= my < rows, bit (mx & 31) of occ_bits[my * bits_pitch + (mx >> 5)] is set and
+ *      r_min < r_k < r_max (both strict).  A cell outside the map is free: no access leaves the map.  A pose with a non-finite
+ *      component, or whose quotient theta / (2 pi) * num_spokes or map-index quotient at a window edge (lut_xs = -+max_range) is
+ *      not below 1e9 in magnitude, has no hit on any beam and never reaches a conversion to an integer;
+ *   4. r_hit = min r_k over the hits; the WALL is the set of hits with r_k < r_hit + (wall_half + wall_half); r_far = max r_k
+ *      over the wall, n_hit = the number of cells in the wall.  No hit: r_hit = +inf, r_far = -inf, n_hit = 0;
+ *   5. d_out[(s * beams + b) * SLAM2D_PREDICT_STRIDE + 0..3] = r_hit, r_far, (double)n_hit, 0.
+ * A min, a max and a count of tabulated radii: the same inputs give the same bits on every call.
+ * PRECONDITION: occ_bits is in step with `cells` (the field build's precondition: slam2d_grid_update keeps it, after any other
+ * write to `cells` call slam2d_map_refresh_bits).  Unobserved and free cells are not told apart (that needs the counts).
+ * No fault bit is raised: the call reads the map descriptors, the bits and the lidar tables, writes only d_out, allocates nothing,
+ * enqueues on `stream` and does not synchronise.  SLAM2D_E_BADARG, before any HIP call: a NULL lidar, d_maps, d_pose or d_out, NULL
+ * spoke tables, S <= 0, pose_stride < 3, map_stride not 0 or 1, beams <= 0 or > SLAM2D_MAX_BEAMS, !(r_min >= 0), !(r_max > r_min);
+ * SLAM2D_E_TOOLARGE: S * ceil(beams / 4) blocks exceed a grid. */
+#define SLAM2D_PREDICT_STRIDE 4
+int slam2d_predict_scan(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t map_stride, int32_t S,
+                        const double* d_pose, int32_t pose_stride, double r_min, double r_max,
+                        double* d_out, void* stream);
+
 /* Particle.updateEstimatedPose for P particles (Algorithm/FastSlam.py:77-106): the pose prior of the
  * next scan from the previous matched poses and the raw odometry increment.
  *   d_prev_pose[p*3 + 0..2]  previous matched pose (prevMatchedReading)

@@ -4147,6 +4147,186 @@ __global__ __launch_bounds__(64 * MAPS_BEAMS) void k_map_scans(Slam2dLidar lid, 
     if (f) atomicOr(flags, f);
 }
 
+// ---- the scan a map expects at a pose (slam2d_predict_scan): the inverse of the update, in the update's discretisation ----
+// The update writes a beam's wall into the cells of ONE spoke of the window (Utils/OccupancyGrid.py:131-152); the range a map
+// predicts for the beam is therefore the nearest occupied cell of that spoke: a min, a max and a count over table radii.
+#define PRED_UNROLL 4
+#define PRED_KEEP 1                  // chunks of 64 * PRED_UNROLL cells whose hits k_predict_scan keeps in registers for the wall
+
+// The cells k = kb + lane + 64 u (u < PRED_UNROLL) of one spoke list: rr[u] = the cell's tabulated radius where it is a HIT -- k < kend,
+// its map index inside the map, its occupancy bit set, r_min < r < r_max -- and +inf elsewhere.  Straight-line phases, every load
+// of a phase issued before its first use: the walk is a chain list -> cell -> bit word.  The map index is convertRealXYToMapIdx
+// (:104-105,144-145) with k_grid_update's two shortcuts, which give the exact division's integers: the lattice offset (decided
+// once per wave by the caller) and the reciprocal with the exact-division fallback next to a rounding boundary.  A cell outside
+// the map reads bit word 0 and discards it: no access leaves the map.
+__device__ __forceinline__ void predict_hits(const Slam2dLidar& lid, const Slam2dMap& m, const int kb, const int kend, const int lane,
+                                             const double px, const double py, const double inv_unit, const bool lattice,
+                                             const int bx, const int by, const double r_min, const double r_max,
+                                             double (&rr)[PRED_UNROLL]) {
+    const int W = lid.lut_w;
+    double r[PRED_UNROLL];
+    uint32_t cell[PRED_UNROLL], word[PRED_UNROLL];
+    int mxs[PRED_UNROLL], mys[PRED_UNROLL];
+#pragma unroll
+    for (int u = 0; u < PRED_UNROLL; ++u) {
+        const int k = min(kb + lane + u * 64, kend - 1);
+        r[u] = lid.spoke_r[k];
+        cell[u] = lid.spoke_cells[k];
+    }
+    if (lattice) {
+#pragma unroll
+        for (int u = 0; u < PRED_UNROLL; ++u) {
+            mxs[u] = (int)(cell[u] & 0xffffu) + bx;
+            mys[u] = (int)(cell[u] >> 16) + by;
+        }
+    } else {
+        double xj[PRED_UNROLL], yi[PRED_UNROLL];
+        if (lid.lut_xs_step != 0.0) {
+#pragma unroll
+            for (int u = 0; u < PRED_UNROLL; ++u) {
+                const int cj = (int)(cell[u] & 0xffffu), ci = (int)(cell[u] >> 16);
+                xj[u] = cj == W - 1 ? lid.max_range : (double)cj * lid.lut_xs_step + -lid.max_range;
+                yi[u] = ci == W - 1 ? lid.max_range : (double)ci * lid.lut_xs_step + -lid.max_range;
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < PRED_UNROLL; ++u) {
+                xj[u] = lid.lut_xs[cell[u] & 0xffffu];
+                yi[u] = lid.lut_xs[cell[u] >> 16];
+            }
+        }
+        bool slow = false;
+#pragma unroll
+        for (int u = 0; u < PRED_UNROLL; ++u) {
+            const double tx = ((px + xj[u]) - m.lim_x0) * inv_unit, ty = ((py + yi[u]) - m.lim_y0) * inv_unit;
+            const double rx = rint(tx), ry = rint(ty);
+            slow |= fabs(fabs(tx - rx) - 0.5) < 1e-6 || fabs(fabs(ty - ry) - 0.5) < 1e-6 || !(fabs(tx) < 1e9) || !(fabs(ty) < 1e9);
+            mxs[u] = (int)rx; mys[u] = (int)ry;           // (a quotient beyond 1e9 is replaced below before anything reads this)
+        }
+        if (__any(slow)) {                                 // a quotient next to a rounding boundary: exact division
+#pragma unroll
+            for (int u = 0; u < PRED_UNROLL; ++u) {
+                const double tx = ((px + xj[u]) - m.lim_x0) / lid.unit, ty = ((py + yi[u]) - m.lim_y0) / lid.unit;
+                mxs[u] = fabs(tx) < 1e9 ? (int)rint(tx) : -1;
+                mys[u] = fabs(ty) < 1e9 ? (int)rint(ty) : -1;
+            }
+        }
+    }
+    bool inside[PRED_UNROLL];
+#pragma unroll
+    for (int u = 0; u < PRED_UNROLL; ++u) {
+        inside[u] = mxs[u] >= 0 && mxs[u] < m.cols && mys[u] >= 0 && mys[u] < m.rows;
+        word[u] = m.occ_bits[inside[u] ? (size_t)mys[u] * (size_t)m.bits_pitch + (size_t)(mxs[u] >> 5) : (size_t)0];
+    }
+#pragma unroll
+    for (int u = 0; u < PRED_UNROLL; ++u) {
+        const bool hit = inside[u] && ((word[u] >> (mxs[u] & 31)) & 1u) && kb + lane + u * 64 < kend && r[u] > r_min && r[u] < r_max;
+        rr[u] = hit ? r[u] : INFINITY;
+    }
+}
+
+// One wave per (pose, beam), MAPS_BEAMS adjacent beams of one pose per block.  out[(s * beams + b) * SLAM2D_PREDICT_STRIDE + 0..3] =
+// (r_hit, r_far, n_hit, 0): the smallest radius over the beam's hits, and the largest radius and the number of the hits with
+// r < r_hit + wallThickness -- the wall the update would have put there; (+inf, -inf, 0, 0) for a beam without a hit.
+// The cells of a spoke are ordered by radial band and floor(r / unit) is monotone in r, so r_hit lies in the first band that holds
+// a hit, and the wall's cells in the bands up to the one that holds r_hit + wallThickness: the walk stops behind that band (a
+// wave-uniform exit).  Work follows the cells up to the first wall, as the update's, not the window.
+__global__ __launch_bounds__(64 * MAPS_BEAMS) void k_predict_scan(Slam2dLidar lid, const Slam2dMap* __restrict__ maps, int map_stride, int S,
+                                                                 int groups, const double* __restrict__ pose, int pstride,
+                                                                 double r_min, double r_max, double* __restrict__ out) {
+    const int s = blockIdx.x / groups, beam = (blockIdx.x % groups) * MAPS_BEAMS + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (s >= S || beam >= lid.beams) return;
+    const Slam2dMap m = maps[(size_t)s * map_stride];
+    const double px = pose[(size_t)s * pstride], py = pose[(size_t)s * pstride + 1], th = pose[(size_t)s * pstride + 2];
+    double r_hit = INFINITY, r_far = -INFINITY;
+    int n_hit = 0;
+    // A pose with a non-finite component, or one whose heading quotient or window-edge quotients are not below 1e9, sees nothing:
+    // decided here, before any conversion to an integer (the quotients of the cells in between lie between those of the edges)
+    const double R = lid.max_range;
+    const bool valid = isfinite(px) && isfinite(py) && isfinite(th) && fabs(th / (2 * 3.141592653589793) * (double)lid.num_spokes) < 1e9 &&
+                       fabs(((px + -R) - m.lim_x0) / lid.unit) < 1e9 && fabs(((px + R) - m.lim_x0) / lid.unit) < 1e9 &&
+                       fabs(((py + -R) - m.lim_y0) / lid.unit) < 1e9 && fabs(((py + R) - m.lim_y0) / lid.unit) < 1e9;
+    if (valid && m.rows > 0 && m.cols > 0 && m.occ_bits) {
+        const int nb = lid.num_bands;
+        const int* __restrict__ bp = lid.spoke_band + (size_t)beam_spoke(lid, th, beam) * (nb + 1);
+        // cells with r > r_min sit in bands >= band(r_min), cells with r < r_max in bands <= band(r_max)
+        const int qlo = (int)fmin(floor(r_min / lid.unit), 2.0e9), qhi = (int)fmin(floor(r_max / lid.unit), 2.0e9);
+        const int kbeg = bp[min(qlo / SLAM2D_SPOKE_BAND, nb)], kend = bp[min(qhi / SLAM2D_SPOKE_BAND + 1, nb)];
+        const double inv_unit = 1.0 / lid.unit;
+        // the lattice shortcut of k_grid_update, under its conditions: window step == map unit, the offset away from a half cell
+        const double Ax = ((px + -R) - m.lim_x0) * inv_unit, Ay = ((py + -R) - m.lim_y0) * inv_unit;
+        const double rAx = rint(Ax), rAy = rint(Ay);
+        const bool lattice = lid.lut_xs_step == lid.unit && fabs(Ax) < 1e8 && fabs(Ay) < 1e8 &&
+                             fabs(fabs(Ax - rAx) - 0.5) > 1e-6 && fabs(fabs(Ay - rAy) - 0.5) > 1e-6;
+        const int bx = lattice ? (int)rAx : 0, by = lattice ? (int)rAy : 0;
+        // the band starts of the spoke, one per lane (a table of more than 64 entries is read from memory): the walk's limits
+        // follow the nearest hit found so far, and a load from the table there would sit in the chain of every chunk
+        const int bp_lane = (nb < 64 && lane <= nb) ? bp[lane] : 0;
+        auto band_start = [&](const int i) { return nb < 64 ? __shfl(bp_lane, i) : bp[i]; };
+        const double wall = lid.wall_half + lid.wall_half;
+        // ONE walk where it can be: the hits of up to PRED_KEEP chunks that hold any stay in registers
+        // while the walk goes on to the end of the band that holds r_hit + wallThickness (the limit only moves inwards as r_hit
+        // falls, and never before the end of r_hit's own band, so r_hit is final when the walk ends); the wall is then taken
+        // from the kept chunks.  A wall spread over more chunks than that is walked again from the band of r_hit.
+        double keep[PRED_KEEP][PRED_UNROLL];
+        int fb = 0, klim = kend, nkept = 0;
+        for (int kb = kbeg; kb < klim; kb += 64 * PRED_UNROLL) {
+            double rr[PRED_UNROLL];
+            predict_hits(lid, m, kb, kend, lane, px, py, inv_unit, lattice, bx, by, r_min, r_max, rr);
+            double lr = rr[0];
+#pragma unroll
+            for (int u = 1; u < PRED_UNROLL; ++u) lr = fmin(lr, rr[u]);
+            const bool any = __ballot(lr < INFINITY) != 0ull;        // (wave-uniform)
+            if (any) {                                                // (a chunk without a hit has nothing for the wall)
+#pragma unroll
+                for (int q = 0; q < PRED_KEEP; ++q)
+                    if (nkept == q) {
+#pragma unroll
+                        for (int u = 0; u < PRED_UNROLL; ++u) keep[q][u] = rr[u];
+                    }
+                ++nkept;
+                r_hit = fmin(r_hit, wave64_min(lr));
+                fb = min((int)fmin(floor(r_hit / lid.unit), 2.0e9) / SLAM2D_SPOKE_BAND, nb - 1);
+                const int qw = (int)fmin(floor((r_hit + wall) / lid.unit), 2.0e9);
+                klim = min(kend, band_start(min(qw / SLAM2D_SPOKE_BAND + 1, nb)));
+            }
+        }
+        if (r_hit < INFINITY) {
+            const double wall_end = r_hit + wall;
+            double far = -INFINITY;
+            if (nkept <= PRED_KEEP) {
+#pragma unroll
+                for (int q = 0; q < PRED_KEEP; ++q)
+                    if (q < nkept) {
+#pragma unroll
+                        for (int u = 0; u < PRED_UNROLL; ++u) {
+                            const bool in_wall = keep[q][u] < wall_end;
+                            if (in_wall) far = fmax(far, keep[q][u]);
+                            n_hit += __popcll(__ballot(in_wall));
+                        }
+                    }
+            } else {
+                const int wbeg = max(kbeg, band_start(fb));
+                for (int kb = wbeg; kb < klim; kb += 64 * PRED_UNROLL) {
+                    double rr[PRED_UNROLL];
+                    predict_hits(lid, m, kb, klim, lane, px, py, inv_unit, lattice, bx, by, r_min, r_max, rr);
+#pragma unroll
+                    for (int u = 0; u < PRED_UNROLL; ++u) {
+                        const bool in_wall = rr[u] < wall_end;
+                        if (in_wall) far = fmax(far, rr[u]);
+                        n_hit += __popcll(__ballot(in_wall));
+                    }
+                }
+            }
+            r_far = wave64_max(far);
+        }
+    }
+    if (lane == 0) {
+        double* o = out + ((size_t)s * lid.beams + beam) * SLAM2D_PREDICT_STRIDE;
+        o[0] = r_hit; o[1] = r_far; o[2] = (double)n_hit; o[3] = 0.0;
+    }
+}
+
 // Sharded normaliser, merge half: every rank folds the gathered [world][3] partials in rank order
 // (so the result does not depend on the network's reduction order), normalises its own particles
 // and evaluates sum (w - 1/N)^2 = sum w^2 - 1/N over ALL N particles (Algorithm/FastSlam.py:32-35).
@@ -4945,6 +5125,22 @@ int slam2d_map_scans(const Slam2dLidar* lidar, const Slam2dMap* d_map, int32_t S
     if ((long long)S * groups > 0x7fffffffll) return SLAM2D_E_TOOLARGE;
     k_map_scans<<<S * groups, 64 * MAPS_BEAMS, 0, (hipStream_t)stream>>>(*lidar, d_map, S, groups, d_pose, pose_stride, d_ranges, d_plan, d_lut_bin,
                                                         d_lut_r, d_flags);
+    return launch_status();
+}
+
+int slam2d_predict_scan(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t map_stride, int32_t S, const double* d_pose,
+                        int32_t pose_stride, double r_min, double r_max, double* d_out, void* stream) {
+    if (!lidar || !d_maps || !d_pose || !d_out || S <= 0 || pose_stride < 3 || (map_stride != 0 && map_stride != 1))
+        return SLAM2D_E_BADARG;
+    if (!lidar->spoke_band || !lidar->spoke_cells || !lidar->spoke_r || (!lidar->lut_xs && lidar->lut_xs_step == 0.0) ||
+        lidar->num_bands < 1 || lidar->num_spokes < 1 || lidar->lut_w < 2 || lidar->lut_w > 65535 || !(lidar->unit > 0.0))
+        return SLAM2D_E_BADARG;
+    if (lidar->beams <= 0 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_BADARG;
+    if (!(r_min >= 0.0) || !(r_max > r_min)) return SLAM2D_E_BADARG;              // (the negated forms refuse a NaN)
+    const int groups = cdiv(lidar->beams, MAPS_BEAMS);
+    if ((long long)S * groups > 0x7fffffffll) return SLAM2D_E_TOOLARGE;
+    k_predict_scan<<<S * groups, 64 * MAPS_BEAMS, 0, (hipStream_t)stream>>>(*lidar, d_maps, map_stride, S, groups, d_pose, pose_stride,
+                                                                            r_min, r_max, d_out);
     return launch_status();
 }
 

@@ -1082,6 +1082,33 @@ class ParticleEngine:
                                           _ptr(level.moments_work()), _ptr(out), _stream()), "slam2d_match_moments")
         return out
 
+    def predict_scan(self, d_pose, stride, S=None, one_map=False, r_min=0.0, r_max=None):
+        """The scan this engine's maps expect at the poses ``d_pose[s * stride + 0..2]`` (include/slam2d.h, slam2d_predict_scan):
+        ``[S, beams, PREDICT_STRIDE]`` on the device, rows (r_hit, r_far, n_hit, 0).  Pose s is seen in map s (S <= P; S
+        defaults to P), or -- ``one_map`` -- every pose in map 0 (S defaults to the rows of ``d_pose``).  ``r_max`` defaults to
+        lidarMaxRange.  The occupancy bits are brought in step first (``refresh_bits``); ``predict_host`` unpacks the result."""
+        if S is None:
+            S = d_pose.numel() // stride if one_map else self.P
+        if not one_map and S > self.P:
+            raise ValueError(f"{S} poses for {self.P} maps")
+        self.refresh_bits()
+        out = torch.empty((S, self.lidar.beams, _lib.PREDICT_STRIDE), dtype=torch.float64, device=self.device)
+        check(self.L.slam2d_predict_scan(C.byref(self.lidar_c), _ptr(self.d_maps), 0 if one_map else 1, S, _ptr(d_pose), stride,
+                                         float(r_min), float(self.lidar.max_range if r_max is None else r_max), _ptr(out), _stream()),
+              "slam2d_predict_scan")
+        return out
+
+    def predict_host(self, rows, no_return=None):
+        """Rows of ``predict_scan`` as a dict of host arrays shaped like ``rows`` without its last axis: ``first`` (r_hit; +inf
+        without a hit), ``far`` (r_far; -inf), ``cells`` (n_hit, int), ``hit`` (bool) and ``range`` = (first + far) / 2 where
+        hit, else ``no_return`` -- lidarMaxRange unless given: the reference logs' value of a beam without return."""
+        r = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        first, far, cells = r[..., 0].copy(), r[..., 1].copy(), r[..., 2].astype(np.int64)
+        hit = cells > 0
+        rng = np.full(first.shape, float(self.lidar.max_range if no_return is None else no_return))
+        rng[hit] = (first[hit] + far[hit]) / 2
+        return dict(first=first, far=far, cells=cells, hit=hit, range=rng)
+
     def grid_update(self, d_pose, stride, d_ranges, d_beam_shift=None):
         self._before_update()
         self.refresh_bits()

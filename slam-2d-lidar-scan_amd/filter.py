@@ -391,9 +391,11 @@ class ParticleFilter:
         ``force_resample``: scan counts after which to resample regardless (tests).  ``on_scan(count, self, unbalanced)``
         is called once a scan's results are on the host.  Returns the list of (count, resample indices)."""
         with pinned_stream():
+            self._in_run = True                  # (predict_scans: a pipelined scan may be in flight until this returns)
             try:
                 return self._run(readings, first_count, force_resample, on_scan)
             finally:
+                self._in_run = False
                 # whatever ended the run (a fault raised from a scan's report, the caller's on_scan): no worker thread may still be
                 # issuing a match over descriptors this object owns
                 try:
@@ -1182,6 +1184,30 @@ class ParticleFilter:
             est = d_est[:, :3].cpu().numpy()
         mom = lv.moments_host(rows)
         return est + mom["mean"], mom["cov"]
+
+    def predict_scans(self, poses=None, r_min=0.0, r_max=None, no_return=None):
+        """The scan every particle's own map expects at that particle's pose, in one launch (include/slam2d.h,
+        slam2d_predict_scan with one map per pose): the dict of ``OccupancyGrid.predictScan`` -- first, far, cells, hit, range --
+        of ``[P, beams]`` arrays for this rank's particles.  ``poses``: ``[P, 3]`` (x, y, theta), one per particle; default: the
+        last matched poses, which every commit leaves on the device (after a resample: those of the surviving particles).
+        Ordered like ``MapView.mapImage``: on the current stream, behind everything ``updateParticles`` or ``run()`` enqueued.
+        Valid between ``updateParticles`` calls and after ``run()`` has returned.  Inside ``run()`` (its ``on_scan`` callback) the
+        next scan may be in flight on the groups' streams, about to write the maps and the poses: it raises there."""
+        if getattr(self, "_in_run", False):
+            raise _lib.Slam2dError("predict_scans: run() is in progress and a pipelined scan may be in flight (it writes the maps and "
+                                   "the matched poses): call it between updateParticles calls or after run() has returned")
+        eng, P = self.engine, self.numParticles
+        if poses is None:
+            if self.prev_matched is None:
+                raise _lib.Slam2dError("predict_scans: no scan has been processed yet, there are no matched poses")
+            d_pose = self.d_pose
+        else:
+            poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+            if len(poses) != P:
+                raise ValueError(f"predict_scans needs one pose per particle: {P} rows, got {len(poses)}")
+            d_pose = eng.to_device(poses)
+        rows = eng.predict_scan(d_pose, 3, P, one_map=False, r_min=r_min, r_max=r_max)
+        return eng.predict_host(rows, no_return)                    # (the download synchronises: an upload outlives the kernel)
 
     def best_particle(self):
         return self.particles[int(np.argmax(self.weights))]

@@ -255,6 +255,38 @@ class OccupancyGrid:
         xIdx, yIdx = self.convertRealXYToMapIdx(xRange, yRange)
         return self.map.image(xIdx[0], xIdx[1], yIdx[0], yIdx[1], flipud=True, as_u8=as_u8).cpu().numpy()
 
+    # ---- the scan this map expects at a pose (slam2d_predict_scan): the inverse of updateOccupancyGrid ----
+    def predictScans(self, poses, r_min=0.0, r_max=None, no_return=None):
+        """``predictScan`` for ``[S, 3]`` poses (x, y, theta) in one launch: the same dict, of ``[S, beams]`` arrays."""
+        self.flush()                                                # (a fault of the last update must not pass unseen into a prediction)
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        eng = self.engine()
+        if len(poses) == 0:
+            return eng.predict_host(np.zeros((0, self.numSamplesPerRev, _lib.PREDICT_STRIDE)), no_return)
+        rows = eng.predict_scan(eng.to_device(poses), 3, len(poses), one_map=True, r_min=r_min, r_max=r_max)
+        return eng.predict_host(rows, no_return)                    # (the download synchronises: the upload outlives the kernel)
+
+    def predictScan(self, reading_or_pose, r_min=0.0, r_max=None, no_return=None):
+        """The ranges this map expects the lidar to report at a pose -- a reading dict (its 'x', 'y', 'theta') or (x, y, theta) --
+        per beam, in the update's own discretisation: a beam's wall is written into the cells of one angular spoke of the window
+        (Utils/OccupancyGrid.py:131-152), so its predicted range is the nearest occupied cell of that spoke with a tabulated radius
+        in (r_min, r_max); the heading is quantised to the angular step, as in the update.  Returns a dict of ``[beams]`` arrays:
+        ``first`` / ``far`` (nearest cell of the wall and the farthest within wallThickness behind it: what an update at that
+        range wrote), ``cells`` (their number), ``hit`` and ``range`` = (first + far) / 2 where hit, else ``no_return``
+        (default lidarMaxRange, as the reference's logs report a beam without return).  ``r_max`` defaults to lidarMaxRange."""
+        p = reading_or_pose
+        pose = [p['x'], p['y'], p['theta']] if isinstance(p, dict) else list(p)
+        return {k: v[0] for k, v in self.predictScans([pose], r_min, r_max, no_return).items()}
+
+    def scanResidual(self, reading):
+        """Measured minus predicted ``range`` per beam at the reading's pose; NaN where the beam did not return
+        (range >= lidarMaxRange) or the map predicts no hit."""
+        pred = self.predictScan(reading)
+        rng = np.asarray(reading['range'], dtype=np.float64)
+        res = rng - pred["range"]
+        res[~pred["hit"] | (rng >= self.lidarMaxRange)] = np.nan
+        return res
+
     # ---- plotting (host Matplotlib, off the hot path; Utils/OccupancyGrid.py:161-175) ----
     def plotOccupancyGrid(self, xRange=None, yRange=None, plotThreshold=True):
         import matplotlib.pyplot as plt
