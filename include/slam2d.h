@@ -474,6 +474,42 @@ int slam2d_predict_scan(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32
                         const double* d_pose, int32_t pose_stride, double r_min, double r_max,
                         double* d_out, void* stream);
 
+/* A scan's score at any poses in a level's field: what the sweep sums for ONE pose of a cube, for N free poses anywhere in the
+ * frame -- the measurement model of Monte-Carlo localisation (an added symbol: no struct and no existing signature changed, the
+ * ABI number stays).  PRECONDITION: slam2d_field_build -- the FULL build; slam2d_match's lazy build leaves stale tiles -- has run
+ * for slot p_field of `level` on this stream (or the call is ordered behind it), and nothing has written that slot's field or
+ * frame since.  Read: level->frames[p_field] (xlo, ylo, fh, fw), that slot of level->field, fmax, fpitch, step, cost_scale; of
+ * `lidar` only beams, fov, max_range.  For pose n = (x, y, theta) at d_pose[n * pose_stride + 0..2] and its scan at
+ * d_ranges + n * ranges_stride (ranges_stride 0: one scan for all poses; >= beams: a scan per pose), with B = beams:
+ *   1. beam angle, as numpy.linspace(theta - fov/2, theta + fov/2, B) (Utils/ScanMatcher_OGBased.py:82-83): a0 = theta - fov/2,
+ *      a1 = theta + fov/2, astep = (a1 - a0) / (B - 1), a_b = (b == B - 1) ? a1 : b * astep + a0; B == 1: a0;
+ *   2. beam b is IN RANGE iff r_b < max_range (:84): NaN and +inf are out, 0 and negative ranges are in;
+ *   3. in range: px = x + cos(a_b) * r_b, py = y + sin(a_b) * r_b (:87-88), qx = (px - xlo) / step, qy = (py - ylo) / step
+ *      (:174-175), in those operations and that order (no contraction);
+ *   4. the beam is INSIDE iff |qx| < 1e9 and |qy| < 1e9 (a NaN fails) and cx = (int)qx, cy = (int)qy (truncation, astype(int))
+ *      satisfy 0 <= cx < fw, 0 <= cy < fh.  A quotient that fails the guard never reaches a conversion to an integer, and no
+ *      field access leaves [0, fh) x [0, fw);
+ *   5. U = the SET of cells (cy, cx) of the inside beams (np.unique, :120); sum_u = sum over U of field[cy * fpitch + cx],
+ *      sum_b = the same sum over every inside beam, duplicates counted; 64-bit integers (below 2048 * 2^32 < 2^53);
+ *   6. d_out[n * SLAM2D_SCORE_STRIDE + 0..7] =
+ *        0  -((double)sum_u * (1 / cost_scale))   the reference's score of the scan at the pose: convTotal of a fine search at zero
+ *                                                 offset (:129-130), no prior
+ *        1  |U|
+ *        2  -((double)sum_b * (1 / cost_scale))   the per-beam score: no reward for folding the scan into few cells
+ *        3  inside beams        4  beams in range        5  (double)sum_u        6  (double)sum_b        7  0
+ * Sums over a set of integers: the same inputs give the same bits on every call, whichever beam claims a cell.  A pose with a
+ * non-finite component has no inside beam (zeros in slots 0-3, 5, 6) and never faults.  No fault bit is raised: the call writes
+ * only d_out, allocates nothing, is ONE launch on `stream` and does not synchronise.  SLAM2D_E_BADARG, before any HIP call: a NULL
+ * lidar, level, d_pose, d_ranges or d_out, a level without field or frames, N <= 0, p_field < 0, pose_stride < 3, ranges_stride
+ * neither 0 nor >= beams, beams < 1 or > SLAM2D_MAX_BEAMS, !(max_range > 0), !(step > 0), !(cost_scale > 0), fmax <= 0 or
+ * fpitch < fmax; SLAM2D_E_TOOLARGE: the poses exceed one launch (4 poses per 256 threads, 2 per 128 above 1365 beams, fewer than 2^32
+ * threads), or fmax * fpitch >= 2^29 (slam2d_field_build's own limit). */
+#define SLAM2D_SCORE_STRIDE 8
+int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N,
+                       const double* d_pose, int32_t pose_stride,
+                       const double* d_ranges, int32_t ranges_stride,
+                       double* d_out, void* stream);
+
 /* Particle.updateEstimatedPose for P particles (Algorithm/FastSlam.py:77-106): the pose prior of the
  * next scan from the previous matched poses and the raw odometry increment.
  *   d_prev_pose[p*3 + 0..2]  previous matched pose (prevMatchedReading)

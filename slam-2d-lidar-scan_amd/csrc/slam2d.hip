@@ -4327,6 +4327,102 @@ __global__ __launch_bounds__(64 * MAPS_BEAMS) void k_predict_scan(Slam2dLidar li
     }
 }
 
+// ---- a scan's score at any poses in a level's field (slam2d_score_poses): the front half of k_endpoints without its angle loop ----
+// What the sweep sums for one pose of a cube (Utils/ScanMatcher_OGBased.py:81-89,117-121,129-130,173-176), for N free poses: the
+// cost of the SET of field cells the in-range beams end in (np.unique, :120), an integer sum, so whichever beam claims a cell the
+// result is the same bits.
+#define SCORE_WAVES 4                // poses (waves) per block while four hash sets stay within 32 KB; two beyond (score_hash_size() == 4096)
+
+// slots of a pose's hash set of cell keys: a power of two >= 1.5 * beams (load factor <= 2/3: an empty slot ends every probe), >= 64
+__host__ __device__ __forceinline__ int score_hash_size(const int beams) {
+    int h = 64;
+    while (h < beams + ((beams + 1) >> 1)) h <<= 1;
+    return h;
+}
+__device__ __forceinline__ unsigned long long wave64_sum_u64(const unsigned long long v) {      // (all 64 lanes active)
+    const unsigned long long t = row16_sum_u64(v);
+    unsigned long long s = 0ull;
+#pragma unroll
+    for (int l = 0; l < 64; l += 16)
+        s += ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(t >> 32), l) << 32) |
+             (unsigned)__builtin_amdgcn_readlane((int)(unsigned)t, l);
+    return s;
+}
+
+// One wave per pose, blockDim.x / 64 poses per block, beams interleaved over the lanes (beam = 64 i + lane: a wave's range loads
+// are contiguous).  out[n * SLAM2D_SCORE_STRIDE + 0..7] as include/slam2d.h lists them.  The hash set holds keys only: the lane
+// whose atomicCAS finds a slot empty owns the cell and adds its cost to sum_u, every inside beam adds to sum_b.  The wave's
+// hash set is its own, so the one barrier only orders its clearing before the insertions.  Reads frames[p_field], the slot's
+// field and the inputs; writes out; no global atomic, no fault bit.
+__global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar lid, Slam2dLevel lv, int p_field, int N, int hsize,
+                                                                  const double* __restrict__ pose, int pstride,
+                                                                  const double* __restrict__ ranges, int rstride,
+                                                                  double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) int score_lds[];              // [blockDim.x / 64][hsize] keys
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = blockIdx.x * (blockDim.x >> 6) + wv;
+    int* hkey = score_lds + wv * hsize;
+    const int hmask = hsize - 1;
+    for (int i = lane; i < hsize; i += 64) hkey[i] = INT_MAX;                    // (no key: cx < 2^15 leaves the low half below 0xffff)
+    __syncthreads();
+    if (n >= N) return;                                                          // (wave-uniform)
+    const Slam2dFrame fr = lv.frames[p_field];
+    // (a frame is at most fmax x fmax: whatever the frame record holds, no access leaves the slot's image)
+    const int fw = min(fr.fw, min(lv.fmax, lv.fpitch)), fh = min(fr.fh, lv.fmax);
+    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const double x = pose[(size_t)n * pstride], y = pose[(size_t)n * pstride + 1], th = pose[(size_t)n * pstride + 2];
+    const double* __restrict__ rg = ranges + (size_t)n * rstride;
+    const int B = lid.beams;
+    const double a0 = th - lid.fov / 2, a1 = th + lid.fov / 2;                   // np.linspace(theta - fov/2, theta + fov/2, num=B) (:82-83)
+    const double astep = (a1 - a0) / (double)(B - 1);
+    unsigned long long sum_u = 0ull, sum_b = 0ull;                               // (this lane's share)
+    int n_u = 0, n_in = 0, n_rng = 0;                                            // (the wave's counts: ballots)
+    for (int b0 = 0; b0 < B; b0 += 64) {                                         // (wave-uniform trip count)
+        const int b = b0 + lane;
+        const double r = b < B ? rg[b] : NAN;
+        const bool in_range = r < lid.max_range;                                 // :84 (NaN and +inf are out, 0 and negatives in)
+        bool inside = false;
+        int key = INT_MAX;
+        uint32_t cost = 0u;
+        if (in_range) {
+            const double a = B == 1 ? a0 : (b == B - 1) ? a1 : (double)b * astep + a0;
+            const double px = x + cos(a) * r, py = y + sin(a) * r;               // :87-88
+            const double qx = (px - fr.xlo) / lv.step, qy = (py - fr.ylo) / lv.step;   // :174-175
+            if (fabs(qx) < 1e9 && fabs(qy) < 1e9) {                              // (the negated forms keep a NaN from the conversion)
+                const int cx = (int)qx, cy = (int)qy;                            // astype(int): truncation
+                if (cx >= 0 && cx < fw && cy >= 0 && cy < fh) {
+                    inside = true;
+                    key = (cy << 16) | cx;
+                    cost = field[(size_t)cy * lv.fpitch + cx];
+                }
+            }
+        }
+        bool owns = false;
+        if (inside) {
+            int h = (int)(((unsigned)key * 2654435761u) >> 7) & hmask;
+            for (;;) {
+                const int prev = atomicCAS(&hkey[h], INT_MAX, key);
+                if (prev == INT_MAX) { owns = true; break; }
+                if (prev == key) break;
+                h = (h + 1) & hmask;
+            }
+            sum_b += cost;
+            if (owns) sum_u += cost;
+        }
+        n_rng += __popcll(__ballot(in_range));
+        n_in += __popcll(__ballot(inside));
+        n_u += __popcll(__ballot(owns));
+    }
+    sum_u = wave64_sum_u64(sum_u);
+    sum_b = wave64_sum_u64(sum_b);
+    if (lane == 0) {
+        const double inv = 1.0 / lv.cost_scale;
+        double* o = out + (size_t)n * SLAM2D_SCORE_STRIDE;
+        o[0] = -((double)sum_u * inv); o[1] = (double)n_u; o[2] = -((double)sum_b * inv); o[3] = (double)n_in;
+        o[4] = (double)n_rng; o[5] = (double)sum_u; o[6] = (double)sum_b; o[7] = 0.0;
+    }
+}
+
 // Sharded normaliser, merge half: every rank folds the gathered [world][3] partials in rank order
 // (so the result does not depend on the network's reduction order), normalises its own particles
 // and evaluates sum (w - 1/N)^2 = sum w^2 - 1/N over ALL N particles (Algorithm/FastSlam.py:32-35).
@@ -5141,6 +5237,25 @@ int slam2d_predict_scan(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32
     if ((long long)S * groups > 0x7fffffffll) return SLAM2D_E_TOOLARGE;
     k_predict_scan<<<S * groups, 64 * MAPS_BEAMS, 0, (hipStream_t)stream>>>(*lidar, d_maps, map_stride, S, groups, d_pose, pose_stride,
                                                                             r_min, r_max, d_out);
+    return launch_status();
+}
+
+int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose,
+                       int32_t pose_stride, const double* d_ranges, int32_t ranges_stride, double* d_out, void* stream) {
+    if (!lidar || !level || !d_pose || !d_ranges || !d_out || !level->field || !level->frames) return SLAM2D_E_BADARG;
+    if (N <= 0 || p_field < 0 || pose_stride < 3) return SLAM2D_E_BADARG;
+    if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_BADARG;
+    if (ranges_stride != 0 && ranges_stride < lidar->beams) return SLAM2D_E_BADARG;
+    if (!(lidar->max_range > 0.0) || !(level->step > 0.0) || !(level->cost_scale > 0.0)) return SLAM2D_E_BADARG;   // (the negated forms refuse a NaN)
+    // the field's own limits (check_level): a cell key packs (row << 16 | column), offsets into one image stay below 2^31
+    if (level->fmax <= 0 || level->fpitch < level->fmax) return SLAM2D_E_BADARG;
+    if ((long long)level->fmax * level->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;
+    const int hsize = score_hash_size(lidar->beams);
+    const int waves = hsize > 2048 ? SCORE_WAVES / 2 : SCORE_WAVES;               // <= 32 KB of hash sets per block
+    const long long blocks = ((long long)N + waves - 1) / waves;
+    if (blocks * (64 * waves) > 0xffffffffll) return SLAM2D_E_TOOLARGE;           // (a launch holds fewer than 2^32 threads)
+    k_score_poses<<<(unsigned)blocks, 64 * waves, (size_t)waves * hsize * sizeof(int), (hipStream_t)stream>>>(
+        *lidar, *level, p_field, N, hsize, d_pose, pose_stride, d_ranges, ranges_stride, d_out);
     return launch_status();
 }
 

@@ -1109,6 +1109,29 @@ class ParticleEngine:
         rng[hit] = (first[hit] + far[hit]) / 2
         return dict(first=first, far=far, cells=cells, hit=hit, range=rng)
 
+    def score_poses(self, level, p_field, d_pose, pose_stride, N, d_ranges, ranges_stride):
+        """The score of a scan at N free poses ``d_pose[n * pose_stride + 0..2]`` in the field that ``field_build`` -- the full
+        build, not ``match`` -- left in slot ``p_field`` of ``level`` (include/slam2d.h, slam2d_score_poses):
+        ``[N, SCORE_STRIDE]`` on the device.  ``ranges_stride`` 0: the one scan ``d_ranges[0..beams)`` for every pose; >= beams: a scan
+        per pose.  One launch on the current stream; ``score_host`` unpacks the rows."""
+        if not 0 <= p_field < level.P:
+            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        out = torch.empty((N, _lib.SCORE_STRIDE), dtype=torch.float64, device=self.device)
+        check(self.L.slam2d_score_poses(C.byref(self.lidar_c), C.byref(level.c), p_field, N, _ptr(d_pose), pose_stride,
+                                        _ptr(d_ranges), ranges_stride, _ptr(out), _stream()), "slam2d_score_poses")
+        return out
+
+    @staticmethod
+    def score_host(rows):
+        """Rows of ``score_poses`` as a dict of host arrays [N]: ``score`` (the reference's score of the scan at the pose: minus
+        the cost of the SET of cells its beams end in), ``cells`` (the size of that set), ``beam_score`` (the same sum over every
+        beam inside the field, duplicates counted), ``inside``, ``in_range`` and ``outside`` = in_range - inside (int)."""
+        r = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        r = r.reshape(-1, _lib.SCORE_STRIDE)
+        inside, in_range = r[:, 3].astype(np.int64), r[:, 4].astype(np.int64)
+        return dict(score=r[:, 0].copy(), cells=r[:, 1].astype(np.int64), beam_score=r[:, 2].copy(), inside=inside, in_range=in_range,
+                    outside=in_range - inside)
+
     def grid_update(self, d_pose, stride, d_ranges, d_beam_shift=None):
         self._before_update()
         self.refresh_bits()

@@ -86,6 +86,64 @@ def _shared_level(og, key_extra, **kw):
     return _level_cache[key]
 
 
+# ---- the covering level of ScanMatcher.scorePoses, planned on the host ----
+def covering_window(poses, window=None):
+    """(cx, cy, half) of the square that ``scorePoses`` frames its field on: ``window`` as given, else the bounding box of the
+    finite poses (centre, larger half-edge); (0, 0, 0) when there is none."""
+    if window is not None:
+        cx, cy, half = (float(v) for v in window)
+        if not (math.isfinite(cx) and math.isfinite(cy) and math.isfinite(half) and half >= 0):
+            raise ValueError(f"window = (cx, cy, half) wants finite numbers and half >= 0, not {window!r}")
+        return cx, cy, half
+    xy = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    xy = xy[np.isfinite(xy).all(axis=1), :2]
+    if not len(xy):
+        return 0.0, 0.0, 0.0
+    lo, hi = xy.min(axis=0), xy.max(axis=0)
+    return float((lo[0] + hi[0]) / 2), float((lo[1] + hi[1]) / 2), float(max(hi[0] - lo[0], hi[1] - lo[1]) / 2)
+
+
+def round_up_125(v):
+    """The smallest of ..., 0.5, 1, 2, 5, 10, 20, 50, ... that is >= v (v > 0): pose sets of similar extent share one level."""
+    e = math.floor(math.log10(v))
+    for k in (e - 1, e, e + 1):
+        for m in (1, 2, 5):
+            c = m * 10.0 ** k if k >= 0 else m / 10.0 ** -k
+            if c >= v:
+                return c
+    raise AssertionError(v)
+
+
+def field_build_limits(reach, step, unit):
+    """None when slam2d_field_build accepts a level of this reach, else what it refuses (check_level and check_field_args in
+    csrc/slam2d.hip, and the map-window row k_occ_scatter keeps in 64 KB of LDS)."""
+    fmax = int(2 * reach / step) + 2
+    fpitch = -(-fmax // 16) * 16
+    tmax = -(-fmax // 16)
+    wmax = int(2 * reach / unit) + 3
+    if fmax * fpitch >= 1 << 29:
+        return f"a field of {fmax} x {fpitch} cells (fmax * fpitch must stay below 2^29)"
+    if tmax * tmax > 28000:
+        return f"{tmax} x {tmax} field tiles (at most 28000)"
+    if wmax * 4 > 65536:
+        return f"a map window of {wmax} cells per row (at most 16384)"
+    return None
+
+
+def covering_radius(half, max_range, step, unit):
+    """The ``search_radius_ctor`` of the covering level for a window of half-edge ``half``: the level's reach, 1.1 * max_range +
+    this (Utils/ScanMatcher_OGBased.py:21), is at least half + max_range, so every endpoint of an in-range beam of a pose in the
+    window lies in the field.  Rounded up (round_up_125) where slam2d_field_build still accepts the level, else to whole steps;
+    ValueError naming ``window`` when even that is beyond the build's limits."""
+    need = max(half + max_range - 1.1 * max_range, step)
+    exact = math.ceil(need / step) * step
+    for ctor in (round_up_125(need), exact):
+        if field_build_limits(1.1 * max_range + ctor, step, unit) is None:
+            return ctor
+    raise ValueError(f"window: a half-edge of {half:g} m at a step of {step:g} m needs "
+                     f"{field_build_limits(1.1 * max_range + exact, step, unit)}; score a smaller window or use the coarse level")
+
+
 class ScanMatcher:
     def __init__(self, og, searchRadius, searchHalfRad, scanSigmaInNumGrid, moveRSigma, maxMoveDeviation, turnSigma,
                  missMatchProbAtCoarse, coarseFactor):
@@ -221,6 +279,58 @@ class ScanMatcher:
             return dict(pose_mean=(est[0] + mean[0], est[1] + mean[1], est[2] + mean[2]), cov=mom["cov"][0], sum_w=sum_w,
                         log_confidence=float(mom["best_score"][0]) + math.log(sum_w) if sum_w > 0 else float("nan"))
 
+    def covering_level(self, level, half):
+        """The cached level whose field covers a window of half-edge ``half`` at this matcher's fine or coarse configuration
+        (step, sigma and miss probability exactly as fine_level() / coarse_level() derive them), with a cube of one angle."""
+        if level not in ("fine", "coarse"):
+            raise ValueError("level is 'fine' or 'coarse'")
+        unit = self.og.unitGridSize
+        if level == "fine":
+            step, sigma, miss = unit, self.scanSigmaInNumGrid, self.missMatchProbAtCoarse ** (2 / self.coarseFactor)      # :66,69
+        else:
+            step, sigma, miss = self.coarseFactor * unit, self.scanSigmaInNumGrid / self.coarseFactor, self.missMatchProbAtCoarse   # :54-55
+        ctor = covering_radius(half, self.og.lidarMaxRange, step, unit)
+        key = ("cover", step, sigma, miss, ctor, self.moveRSigma, self.maxMoveDeviation, self.turnSigma)
+        return _shared_level(self.og, key, step=step, sigma=sigma, miss_prob=miss, search_radius_ctor=ctor, radius=step,
+                             half_rad=0.0, fine=True, move_sigma=self.moveRSigma, max_move_dev=self.maxMoveDeviation,
+                             turn_sigma=self.turnSigma)
+
+    def scorePoses(self, poses, reading_or_ranges, level="fine", window=None):
+        """How well a scan fits at N free poses anywhere in the map (include/slam2d.h, slam2d_score_poses): the reference's score
+        of the scan -- convTotal of a fine search at zero offset, no prior (:129-130) -- at each pose ``poses[n] = (x, y,
+        theta)``, in ONE launch.  ``reading_or_ranges``: a reading dict, ``[beams]`` ranges for every pose, or ``[N, beams]``, a
+        scan per pose.  The field is this matcher's ``level`` ('fine' or 'coarse') built in full on a frame that covers the
+        bounding box of the finite poses -- or ``window = (cx, cy, half)`` -- plus lidarMaxRange; the map grows to hold that
+        frame as in frameSearchSpace (:27).  Returns a dict of [N] host arrays: ``score``, ``cells``, ``beam_score``,
+        ``inside``, ``in_range``, ``outside`` (ParticleEngine.score_host); ``self.last_cover`` keeps the level and its frame.
+        ValueError naming ``window`` when the frame is beyond what the field build accepts."""
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
+        rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
+        N, B = len(poses), self.og.numSamplesPerRev
+        if N == 0:
+            raise ValueError("no poses")
+        if rng.shape not in ((B,), (N, B)):
+            raise ValueError(f"ranges of shape {rng.shape}: want ({B},) or ({N}, {B})")
+        cx, cy, half = covering_window(poses, window)
+        lv = self.covering_level(level, half)
+        with _Exclusive(lv), pinned_stream():
+            og = self.og
+            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = og.engine()
+            eng.field_build(lv, eng.to_device([[cx, cy]]), 2)
+            rows = eng.score_poses(lv, 0, eng.to_device(poses), 3, N, eng.to_device(rng), 0 if rng.ndim == 1 else B)
+            # one download: the rows and the build's fault word
+            host = torch.cat([rows.reshape(-1), eng.flags[:1].to(torch.float64)]).cpu().numpy()
+            bits = int(host[-1])
+            if bits:
+                eng.flags.zero_()
+                if bits & _lib.FATAL_FLAGS:
+                    raise _lib.Slam2dError(f"scorePoses: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
+            self.last_flags = bits
+            self.last_cover = dict(level=lv, window=(cx, cy, half))
+            return eng.score_host(host[:-1])
+
     def searchToMatch(self, probSP, estimatedX, estimatedY, estimatedTheta, rMeasure, xRangeList, yRangeList,
                       searchRadius, searchHalfRad, unitLength, estMovingDist, estMovingTheta, fineSearch=False,
                       matchMax=True):
@@ -278,5 +388,6 @@ class ScanMatcher:
         new = ScanMatcher.__new__(ScanMatcher)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            setattr(new, k, copy.deepcopy(v, memo))       # og: clones the device map, alias preserved via memo
+            # og: clones the device map, alias preserved via memo; last_cover names a SHARED level (_shared_level): by reference
+            setattr(new, k, v if k == "last_cover" else copy.deepcopy(v, memo))
         return new
