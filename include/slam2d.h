@@ -415,7 +415,14 @@ int64_t slam2d_match_moments_work(const Slam2dLevel* level, int32_t P);
  *                 updated atomically and occ_bits is NOT maintained -- call slam2d_map_refresh_bits afterwards.
  * A particle whose pose puts two adjacent window columns or rows on ONE map index (a pose on a half cell of its map) is
  * not updated at all and receives SLAM2D_F_UPDATE_CELL_COLLISION (here and in slam2d_grid_update_weights*, slam2d_scan_commit*,
- * slam2d_groups_commit): the one-writer premise fails there; slam2d_map_scans is exact at such poses. */
+ * slam2d_groups_commit): the one-writer premise fails there; slam2d_map_scans is exact at such poses.
+ * A cell whose map-index quotient ((x + lut_xs[j]) - lim_x0) / unit (or its y twin) is NaN -- a non-finite x or y -- or not below
+ * 1e9 in magnitude never reaches a conversion to an integer: it is outside the map, raises SLAM2D_F_UPDATE_OUTSIDE_MAP and
+ * writes nothing, with d_beam_shift too.
+ * SLAM2D_E_BADARG, before any HIP call, for a lidar no spoke walk can read (also slam2d_occ_extent, slam2d_map_scans,
+ * slam2d_predict_scan): NULL, a NULL spoke_band, spoke_cells or spoke_r, num_bands < 1, num_spokes < 1, lut_w < 2 or > 65535,
+ * !(unit > 0), or no window coordinates -- lut_xs NULL with lut_xs_step == 0; slam2d_occ_extent and slam2d_map_scans read the
+ * table itself and refuse every NULL lut_xs. */
 int slam2d_grid_update(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t P,
                        const double* d_pose, int32_t pose_stride, const double* d_ranges,
                        const int32_t* d_beam_shift, uint32_t* d_flags, void* stream);
@@ -454,7 +461,7 @@ int slam2d_map_scans(const Slam2dLidar* lidar, const Slam2dMap* d_map, int32_t S
  *      quantised to the angular step, as in the update (:131,134);
  *   2. every cell k of that spoke, window row i, column j, radius r_k = spoke_r[k], has the map index
  *      mx = rint(((x + lut_xs[j]) - lim_x0) / unit), my = rint(((y + lut_xs[i]) - lim_y0) / unit)  (convertRealXYToMapIdx,
- *      :104-105,144-145; the kernel's shortcuts give these integers);
+ *      :104-105,144-145; computed by the update's own code, whose shortcuts give these integers);
  *   3. cell k is a HIT iff 0 <= mx < cols, 0 <= my < rows, bit (mx & 31) of occ_bits[my * bits_pitch + (mx >> 5)] is set and
  *      r_min < r_k < r_max (both strict).  A cell outside the map is free: no access leaves the map.  A pose with a non-finite
  *      component, or whose quotient theta / (2 pi) * num_spokes or map-index quotient at a window edge (lut_xs = -+max_range) is

@@ -212,25 +212,12 @@ __device__ __forceinline__ int wave_scan_incl_i32(int v) {
     return v;
 }
 
-// (int)(v / step) -- truncation, as astype(int) -- and rint(v / unit) without the fp64 division (~35 issue slots each): v * (1 / d)
-// differs from v / d by < 4e-16 relative, so the two agree unless the quotient is within 1e-6 of an integer (a half-integer for
-// rint), where the exact division decides.
-__device__ __forceinline__ int trunc_div(const double v, const double step, const double inv_step) {
-    const double t = v * inv_step;
-    if (fabs(t - rint(t)) < 1e-6 || !(fabs(t) < 1e9)) return (int)(v / step);
-    return (int)t;
-}
-__device__ __forceinline__ int rint_div(const double v, const double unit, const double inv_unit) {
-    const double t = v * inv_unit;
-    double rt = rint(t);
-    if (fabs(fabs(t - rt) - 0.5) < 1e-6 || !(fabs(t) < 1e9)) rt = rint(v / unit);
-    return (int)rt;
-}
-
-// trunc_div for non-negative quotients below 2^31 WITHOUT the division when the quotient sits on an integer n -- which is the rule,
-// not the exception: the reference's poses stay on the map's lattice, so (coordinate - window edge) / step is an
-// integer give or take an ulp for every column of the window, rounds either way, and trunc_div's guard sends every one of them
-// through the fp64 division (~35 issue slots).  (int)(v / step) is n iff the correctly rounded quotient reaches n.  r = v - n * step
+// (int)(v / step) -- truncation, as astype(int) -- without the fp64 division (~35 issue slots): v * (1 / step) differs from
+// v / step by < 4e-16 relative, so the two truncate alike unless the quotient is within 1e-6 of an integer, where the exact
+// quotient decides -- for non-negative quotients below 2^31 still WITHOUT the division when the quotient sits on an integer n, which
+// is the rule, not the exception: the reference's poses stay on the map's lattice, so (coordinate - window edge) / step
+// is an integer give or take an ulp for every column of the window and rounds either way: a guard that divided would send every one
+// of them through the division.  (int)(v / step) is n iff the correctly rounded quotient reaches n.  r = v - n * step
 // is exact as one fma (v and n * step agree in all but their last bits).  r >= 0: the real quotient is >= n, so is its rounding.
 // r < 0: the quotient rounds UP to n iff it lies within half a spacing g of the doubles just below n (g = ulp(n), half that when n is
 // a power of two; the tie goes to n, whose mantissa is even): r >= -(g / 2) * step, a product with a power of two, exact.
@@ -1422,7 +1409,7 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
                 const double dx = bdx[q], dy = bdy[q];
                 const double qx = ex + c * dx - s * dy;                             // :169
                 const double qy = ey + s * dx + c * dy;                             // :170
-                // (a reciprocal multiply with an exact-division guard, as rint_div below, measured no faster: 173.9 vs 166.9 us
+                // (a reciprocal multiply with an exact-division guard, as window_map_index's, measured no faster: 173.9 vs 166.9 us
                 // at 1081 beams -- the kernel is a chain of barriers and LDS round trips, not instruction issue)
                 const int cx = (int)((qx - fr.xlo) / lv.step);                      // :174
                 const int cy = (int)((qy - fr.ylo) / lv.step);                      // :175
@@ -2248,22 +2235,6 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const
 //        k_exact   one wave per (particle, theta): every tile with U >= bnb_best - SLAM2D_PRUNE_MARGIN is scored
 //                  exactly (lane = pose row x 1/16 of the cell list); ONE partial {max, argmax, sum exp} per theta.
 // ------------------------------------------------------------------------------------
-struct Running { double m, s; int arg, nan; };
-__device__ __forceinline__ void running_merge(Running& a, const double tm, const double ts, const int targ, const int tnan) {
-    if (a.nan || tnan) {
-        const int arg = (a.nan && tnan) ? min(a.arg, targ) : (tnan ? targ : a.arg);
-        a.nan = 1; a.arg = arg; a.m = NAN; a.s = NAN;
-        return;
-    }
-    if (tm == -INFINITY) return;
-    if (tm > a.m) { a.s = a.s * exp(a.m - tm) + ts; a.m = tm; a.arg = targ; }
-    else { a.s += ts * exp(tm - a.m); if (tm == a.m && targ < a.arg) a.arg = targ; }
-}
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o) {
-    const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
 // exact cost sums of the 16 poses of tile (by, bx): lane = (pose row r = lane / 16, cell slice s = lane % 16) scores
 // the 4 poses (4 by + r, 4 bx .. 4 bx + 3) against cells k0 + s, k0 + s + kstep, ...; on return every lane of a
 // row group holds the row's 4 sums over ALL the cells this wave walked (reduced over the 16 slices).
@@ -2432,11 +2403,6 @@ __global__ __launch_bounds__(64 * BOUND_GROUP) void k_bound(Slam2dLevel lv, int 
     DBG_CLOCK(4, b == 0);
 }
 
-__device__ __forceinline__ int wave64_min_i32(int v) {
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
 // The seed of one (particle, theta): tile `seed` (the one with the largest bound) scored exactly by one wave; its best score
 // raises lv.bnb_best[p].  (k_bound carries the same lines inline.)
 __device__ __forceinline__ void bound_seed_exact(const Slam2dLevel& lv, const int p, const int sby, const int sbx, const int* __restrict__ cl,
@@ -3714,9 +3680,6 @@ __global__ __launch_bounds__(256) void k_weights(double* logw, const double* __r
 // beam; a block takes UPDB_BEAMS adjacent beams of one particle (adjacent wedges share cache lines)
 // and all blocks of a particle run on one XCD (block b -> XCD b % 8) so those lines meet in one L2.
 // Each window cell belongs to exactly one spoke and each spoke to at most one beam: plain RMW.
-// (int)rint(v / unit) without the fp64 division (~70 issue slots on gfx950, and the update needs two per
-// cell): v * (1/unit) differs from v / unit by < 4e-16 relative, so the two round to the same integer
-// unless the quotient is within 1e-6 of a half-integer -- there the exact division decides.
 #define UPDB_BEAMS 4                 // = waves per block
 #ifndef UPDB_UNROLL
 #define UPDB_UNROLL 4
@@ -3730,6 +3693,114 @@ __global__ __launch_bounds__(256) void k_weights(double* logw, const double* __r
 #ifndef UPDB_SKIP_R
 #define UPDB_SKIP_R 1
 #endif
+
+// ---- the spoke walk shared by k_grid_update, k_occ_extent, k_map_scans and k_predict_scan ----
+// The spoke of a beam: spokesOffsetIdxByTheta = int(rint(theta / (2*pi) * numSpokes)) (:131) past the spoke of beam 0 (:134), in [0, S)
+__device__ __forceinline__ int beam_spoke(const Slam2dLidar& lid, double th, int beam) {
+    const int S = lid.num_spokes;
+    int first = (lid.spoke_start + (int)rint(th / (2 * 3.141592653589793) * (double)S)) % S;
+    if (first < 0) first += S;
+    return (first + beam) % S;
+}
+
+// The tabulated band starts of a spoke's cell list: num_bands + 1 entries, the last one the list's end
+__device__ __forceinline__ const int* spoke_bands(const Slam2dLidar& lid, const int spoke) {
+    return lid.spoke_band + (size_t)spoke * (lid.num_bands + 1);
+}
+
+// The span [kbeg, kend) of a spoke's cell list that holds every cell with lo < r < hi, and kwall, the start of the band of lo.
+// floor(r / unit) is monotone in r: cells with r > lo sit in bands >= band(lo), cells with r < hi in bands <= band(hi).  The
+// cells of the bands wholly below band(lo) -- [kbeg, kwall) of a walk from the centre, which also wants the cells below lo (the
+// free cells of a returned beam, :138) -- have floor(r / unit) < floor(lo / unit), hence r < lo, whatever the table says.
+// false: hi admits no cell.
+__device__ __forceinline__ bool beam_bands(const Slam2dLidar& lid, const int spoke, const double lo, const double hi, const bool from_centre,
+                                           int& kbeg, int& kwall, int& kend) {
+    const int nb = lid.num_bands;
+    const int* __restrict__ bp = spoke_bands(lid, spoke);
+    const int qlo = lo > 0.0 ? (int)fmin(floor(lo / lid.unit), 2.0e9) : 0;
+    const int qhi = hi > 0.0 ? (int)fmin(floor(hi / lid.unit), 2.0e9) : -1;
+    if (qhi < 0) return false;
+    const int bw = min(qlo / SLAM2D_SPOKE_BAND, nb), b0 = from_centre ? 0 : bw, b1 = min(qhi / SLAM2D_SPOKE_BAND + 1, nb);
+    kwall = bp[bw]; kbeg = bp[b0]; kend = bp[max(b0, b1)];
+    return true;
+}
+
+// Window coordinate of column (row) j: np.linspace(-R, R, W)[j] = j * step + (-R), last element R (lut_xs_step, checked against
+// the table by the host), else the table itself
+__device__ __forceinline__ double window_coord(const Slam2dLidar& lid, const int j) {
+    if (lid.lut_xs_step != 0.0) return j == lid.lut_w - 1 ? lid.max_range : (double)j * lid.lut_xs_step + -lid.max_range;
+    return lid.lut_xs[j];
+}
+
+// The map index of a window cell is rint(((pose + xs[j]) - mapLim0) / unit) (:104-105,144-145), two fp64 chains per cell.  When
+// the window step IS the map unit (lidarMaxRange a whole number of cells: every configuration in use) that is rint(A + j) with
+// A = (pose - R - mapLim0) / unit: the fp64 evaluation differs from the real A + j by < 1e-11 cells (three roundings at magnitude
+// <= 1e4), so it rounds to j + rint(A) whenever A is farther than 1e-6 from a half-integer -- decided once per wave: {on, rint(A)}.
+// A pose that close to a rounding boundary, off the lattice or not finite is not `on` and takes window_map_index's per-cell path.
+// (Config 5: 138 k waves x ~25 fp64 instructions per cell saved; the update is instruction-bound there.)
+struct WindowLattice { bool on; int bx, by; };
+__device__ __forceinline__ WindowLattice window_lattice(const Slam2dLidar& lid, const Slam2dMap& m, const double px, const double py,
+                                                        const double inv_unit) {
+    const double Ax = ((px + -lid.max_range) - m.lim_x0) * inv_unit, Ay = ((py + -lid.max_range) - m.lim_y0) * inv_unit;
+    const double rAx = rint(Ax), rAy = rint(Ay);
+    const bool on = lid.lut_xs_step == lid.unit && fabs(Ax) < 1e8 && fabs(Ay) < 1e8 &&
+                    fabs(fabs(Ax - rAx) - 0.5) > 1e-6 && fabs(fabs(Ay - rAy) - 0.5) > 1e-6;
+    return {on, on ? (int)rAx : 0, on ? (int)rAy : 0};
+}
+
+// convertRealXYToMapIdx (:104-105,144-145) of U window cells (row << 16 | column) of one lane: the integers of the exact division.
+// Straight-line phases with no branch that depends on a lane.  On the lattice: column index + the wave's offset, nothing else.
+// Off it, (int)rint(v / unit) without the fp64 division (~70 issue slots on gfx950, two per cell): v * (1 / unit) differs from
+// v / unit by < 4e-16 relative, so the two round to the same integer unless the quotient is within 1e-6 of a half-integer --
+// there, for the whole wave, the exact division decides.  A quotient that is NaN or not below 1e9 never reaches an integer
+// conversion: its index is WINDOW_IDX_NONE, outside every map, and -- unlike -1, which Python's wrap sends to the last column --
+// still negative after a stale-index launch's wrap and shifts (k_grid_update: - sx - ax + wc + ax, a map's rows * pitch < 2^32).
+#define WINDOW_IDX_NONE (-(1 << 30))
+template <int U>
+__device__ __forceinline__ void window_map_index(const Slam2dLidar& lid, const Slam2dMap& m, const double px, const double py,
+                                                 const double inv_unit, const bool lattice, const int bx, const int by,
+                                                 const uint32_t (&cell)[U], int (&mxs)[U], int (&mys)[U]) {
+    if (lattice) {                                             // (wave-uniform)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            mxs[u] = (int)(cell[u] & 0xffffu) + bx;
+            mys[u] = (int)(cell[u] >> 16) + by;
+        }
+        return;
+    }
+    double xj[U], yi[U];
+    // (window_coord's own wave-uniform test, taken once ahead of the phase instead of between its loads: both arms are the same call)
+    if (lid.lut_xs_step != 0.0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            xj[u] = window_coord(lid, (int)(cell[u] & 0xffffu));
+            yi[u] = window_coord(lid, (int)(cell[u] >> 16));
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            xj[u] = window_coord(lid, (int)(cell[u] & 0xffffu));
+            yi[u] = window_coord(lid, (int)(cell[u] >> 16));
+        }
+    }
+    bool slow = false;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const double tx = ((px + xj[u]) - m.lim_x0) * inv_unit, ty = ((py + yi[u]) - m.lim_y0) * inv_unit;
+        const double rx = rint(tx), ry = rint(ty);
+        slow |= fabs(fabs(tx - rx) - 0.5) < 1e-6 || fabs(fabs(ty - ry) - 0.5) < 1e-6 || !(fabs(tx) < 1e9) || !(fabs(ty) < 1e9);
+        mxs[u] = (int)rx; mys[u] = (int)ry;                    // (a quotient beyond 1e9 is replaced below before anything reads this)
+    }
+    if (__any(slow)) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double tx = ((px + xj[u]) - m.lim_x0) / lid.unit, ty = ((py + yi[u]) - m.lim_y0) / lid.unit;
+            mxs[u] = fabs(tx) < 1e9 ? (int)rint(tx) : WINDOW_IDX_NONE;
+            mys[u] = fabs(ty) < 1e9 ? (int)rint(ty) : WINDOW_IDX_NONE;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar lid, const Slam2dMap* __restrict__ maps, int P,
                                                            const double* __restrict__ pose, int pstride,
                                                            const double* __restrict__ ranges,
@@ -3800,37 +3871,26 @@ __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar
     const int xcd = bidx & 7, q = bidx >> 3;
     const int p = (q / groups) * 8 + xcd, g = q % groups;
     if (p >= P) return;
-    const int W = lid.lut_w, S = lid.num_spokes, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int W = lid.lut_w, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const Slam2dMap m = maps[p];
     const double px = pose[(size_t)p * pstride], py = pose[(size_t)p * pstride + 1], th = pose[(size_t)p * pstride + 2];
-    // spokesOffsetIdxByTheta = int(rint(theta / (2*pi) * numSpokes))  (:131)
-    const int offset = (int)rint(th / (2 * 3.141592653589793) * (double)S);
-    int first_spoke = (lid.spoke_start + offset) % S;            // spoke of beam 0 (:134), in [0, S)
-    if (first_spoke < 0) first_spoke += S;
     const double inv_unit = 1.0 / lid.unit;
     uint32_t f = 0;
     // one wave per beam, UPDB_UNROLL chunks of 64 cells in flight: the walk is a chain of dependent loads
     // (list -> cell -> store), so the loads of several chunks are issued before the first use.  The map
-    // index of a cell is computed per cell (rint_div: tabulating both axes per block costs more than that)
+    // index of a cell is computed per cell (window_map_index: tabulating both axes per block costs more than that)
     {
         const int beam = g * UPDB_BEAMS + wave;
         if (beam >= lid.beams) return;
         const double rg = ranges[beam];
         const double lo = rg - lid.wall_half, hi = rg + lid.wall_half;
         const bool returned = rg < lid.max_range;
-        const int spoke = (first_spoke + beam) % S;
-        // floor(r / unit) is monotone in r: cells with r > lo sit in bands >= band(lo), cells with r < hi in
-        // bands <= band(hi); a beam without return marks no free cells (:138) and starts at its wall band
-        const int nb = lid.num_bands;
-        const int* __restrict__ bp = lid.spoke_band + (size_t)spoke * (nb + 1);
-        const int qlo = lo > 0.0 ? (int)fmin(floor(lo / lid.unit), 2.0e9) : 0;
-        const int qhi = hi > 0.0 ? (int)fmin(floor(hi / lid.unit), 2.0e9) : -1;
-        if (qhi < 0) return;
-        const int b0 = returned ? 0 : min(qlo / SLAM2D_SPOKE_BAND, nb), b1 = min(qhi / SLAM2D_SPOKE_BAND + 1, nb);
-        const int kbeg = bp[b0], kend = bp[max(b0, b1)];
-        // cells of the bands wholly below band(lo) have floor(r / unit) < floor(lo / unit), hence r < lo: free by construction
-        // (most of a returned beam's cells); their radii are not read (8 of a chunk's ~36 lines; UPDB_SKIP_R=0: read them all)
-        const int klo = (UPDB_SKIP_R && lo > 0.0) ? bp[min(qlo / SLAM2D_SPOKE_BAND, nb)] : kbeg;
+        // a beam without return marks no free cells (:138) and starts at its wall band
+        int kbeg, kwall, kend;
+        if (!beam_bands(lid, beam_spoke(lid, th, beam), lo, hi, returned, kbeg, kwall, kend)) return;
+        // the cells below the wall band are free by construction (most of a returned beam's cells): their radii are not read
+        // (8 of a chunk's ~36 lines; UPDB_SKIP_R=0: read them all)
+        const int klo = UPDB_SKIP_R ? kwall : kbeg;
         const double* __restrict__ sr = lid.spoke_r;
         const uint32_t* __restrict__ sc = lid.spoke_cells;
         // stale indices of a beam during which the map grew on a low side (:144-152): shift of the beam's own growth,
@@ -3842,18 +3902,8 @@ __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar
             sx = bs[0]; sy = bs[1]; ax = bs[2]; ay = bs[3]; wc = bs[4]; wr = bs[5];
         }
         const uint32_t ncells = (uint32_t)m.rows * (uint32_t)m.pitch;
-        // The map index of a window cell is rint(((pose + xs[j]) - mapLim0) / unit) (:104-105,144-145), two fp64 chains per
-        // cell.  When the window step IS the map unit (lidarMaxRange a whole number of cells: every configuration in use)
-        // that is rint(A + j) with A = (pose - R - mapLim0) / unit: the fp64 evaluation differs from the real A + j by
-        // < 1e-11 cells (three roundings at magnitude <= 1e4), so it rounds to j + rint(A) whenever A is farther than
-        // 1e-6 from a half-integer -- decided once per particle; a particle that close to a rounding boundary takes the
-        // per-cell path with its exact-division fallback.  (Config 5: 138 k waves x ~25 fp64 instructions per cell saved;
-        // the kernel is instruction-bound there.)
-        const double Ax = ((px + -lid.max_range) - m.lim_x0) * inv_unit, Ay = ((py + -lid.max_range) - m.lim_y0) * inv_unit;
-        const double rAx = rint(Ax), rAy = rint(Ay);
-        const bool lattice = !beam_shift && lid.lut_xs_step == lid.unit && fabs(Ax) < 1e8 && fabs(Ay) < 1e8 &&
-                             fabs(fabs(Ax - rAx) - 0.5) > 1e-6 && fabs(fabs(Ay - rAy) - 0.5) > 1e-6 && !UPDB_NO_LATTICE;
-        const int bx = (int)rAx, by = (int)rAy;
+        const WindowLattice wl = window_lattice(lid, m, px, py, inv_unit);
+        const bool lattice = !beam_shift && wl.on && !UPDB_NO_LATTICE;
         if (!lattice && !(lid.lut_xs_step > lid.unit * (1.0 + 1e-9))) {
             // One writer per map cell is the premise of the plain read-modify-write below.  Off the lattice it can fail: at a
             // pose on a half cell rint's ties-to-even sends two adjacent window columns (rows) to ONE map index (the window step
@@ -3865,9 +3915,7 @@ __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar
             // error (< 1e-11 cells) keeps neighbours at least one index apart whatever the pose: those lidars skip the test.
             bool meet = false;
             for (int j = lane; j < W - 1; j += 64) {
-                const double a0 = lid.lut_xs_step != 0.0 ? (double)j * lid.lut_xs_step + -lid.max_range : lid.lut_xs[j];
-                const double a1 = lid.lut_xs_step != 0.0 ? (j + 1 == W - 1 ? lid.max_range : (double)(j + 1) * lid.lut_xs_step + -lid.max_range)
-                                                         : lid.lut_xs[j + 1];
+                const double a0 = window_coord(lid, j), a1 = window_coord(lid, j + 1);
                 meet |= rint(((px + a0) - m.lim_x0) / lid.unit) == rint(((px + a1) - m.lim_x0) / lid.unit) ||
                         rint(((py + a0) - m.lim_y0) / lid.unit) == rint(((py + a1) - m.lim_y0) / lid.unit);
             }
@@ -3878,7 +3926,7 @@ __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar
         }
         for (int k0 = kbeg + lane; k0 < kend; k0 += 64 * UPDB_UNROLL) {
             // straight-line phases, every load of a phase issued before its first use (no branches in between)
-            double r[UPDB_UNROLL], xj[UPDB_UNROLL], yi[UPDB_UNROLL];
+            double r[UPDB_UNROLL];
             uint32_t cell[UPDB_UNROLL], inc[UPDB_UNROLL], c[UPDB_UNROLL], at[UPDB_UNROLL];
             int mxs[UPDB_UNROLL], mys[UPDB_UNROLL];
             if ((k0 - lane) + 64 * UPDB_UNROLL <= klo) {        // (wave-uniform)
@@ -3895,47 +3943,7 @@ __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar
                     cell[u] = sc[k];
                 }
             }
-            if (lattice) {
-                // the window's cells sit on the map's lattice: column index + the particle's offset, nothing else
-#pragma unroll
-                for (int u = 0; u < UPDB_UNROLL; ++u) {
-                    mxs[u] = (int)(cell[u] & 0xffffu) + bx;
-                    mys[u] = (int)(cell[u] >> 16) + by;
-                }
-            } else {
-            // window coordinate of a column / row: np.linspace(-R, R, W)[j] = j * step + (-R), last element R
-            // (lut_xs_step, checked against the table by the host), else the table itself
-            if (lid.lut_xs_step != 0.0) {
-#pragma unroll
-                for (int u = 0; u < UPDB_UNROLL; ++u) {
-                    const int cj = (int)(cell[u] & 0xffffu), ci = (int)(cell[u] >> 16);
-                    xj[u] = cj == W - 1 ? lid.max_range : (double)cj * lid.lut_xs_step + -lid.max_range;
-                    yi[u] = ci == W - 1 ? lid.max_range : (double)ci * lid.lut_xs_step + -lid.max_range;
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < UPDB_UNROLL; ++u) {
-                    xj[u] = lid.lut_xs[cell[u] & 0xffffu];
-                    yi[u] = lid.lut_xs[cell[u] >> 16];
-                }
-            }
-            bool slow = false;
-#pragma unroll
-            for (int u = 0; u < UPDB_UNROLL; ++u) {
-                // convertRealXYToMapIdx(x + xAtSpokeDir, ...)  (:104-105,144-145) as rint_div, fast path only
-                const double tx = ((px + xj[u]) - m.lim_x0) * inv_unit, ty = ((py + yi[u]) - m.lim_y0) * inv_unit;
-                const double rx = rint(tx), ry = rint(ty);
-                slow |= fabs(fabs(tx - rx) - 0.5) < 1e-6 || fabs(fabs(ty - ry) - 0.5) < 1e-6 || !(fabs(tx) < 1e9) || !(fabs(ty) < 1e9);
-                mxs[u] = (int)rx; mys[u] = (int)ry;
-            }
-            if (__any(slow)) {                                     // a quotient next to a rounding boundary: exact division
-#pragma unroll
-                for (int u = 0; u < UPDB_UNROLL; ++u) {
-                    mxs[u] = (int)rint(((px + xj[u]) - m.lim_x0) / lid.unit);
-                    mys[u] = (int)rint(((py + yi[u]) - m.lim_y0) / lid.unit);
-                }
-            }
-            }
+            window_map_index<UPDB_UNROLL>(lid, m, px, py, inv_unit, lattice, wl.bx, wl.by, cell, mxs, mys);
 #pragma unroll
             for (int u = 0; u < UPDB_UNROLL; ++u) {
                 inc[u] = 0u;
@@ -4008,13 +4016,6 @@ __global__ __launch_bounds__(256, UPDB_MIN_WAVES) void k_grid_update(Slam2dLidar
 // the beam's spoke cells by radial band as k_grid_update does.
 #define MAPS_BEAMS 4
 
-__device__ __forceinline__ int beam_spoke(const Slam2dLidar& lid, double th, int beam) {
-    const int S = lid.num_spokes;
-    int first = (lid.spoke_start + (int)rint(th / (2 * 3.141592653589793) * (double)S)) % S;     // :131,134
-    if (first < 0) first += S;
-    return (first + beam) % S;
-}
-
 // Exact fp64 extent of the occupied points x + xAtSpokeDir[occ], y + yAtSpokeDir[occ] of every (scan, beam) (:142-147):
 // out[(s * B + b) * 4 + 0..3] = (min x, max x, min y, max y), +inf / -inf for a beam without occupied cells.  checkMapToExpand
 // (:108-118) only asks any(x < lim) and its kin, so these four numbers replay a beam's growth exactly.
@@ -4025,14 +4026,10 @@ __global__ __launch_bounds__(64 * MAPS_BEAMS) void k_occ_extent(Slam2dLidar lid,
     const double px = pose[(size_t)s * pstride], py = pose[(size_t)s * pstride + 1], th = pose[(size_t)s * pstride + 2];
     const double rg = ranges[(size_t)s * lid.beams + beam];
     const double lo = rg - lid.wall_half, hi = rg + lid.wall_half;
-    const int nb = lid.num_bands;
-    const int* __restrict__ bp = lid.spoke_band + (size_t)beam_spoke(lid, th, beam) * (nb + 1);
     double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-    const int qlo = lo > 0.0 ? (int)fmin(floor(lo / lid.unit), 2.0e9) : 0;
-    const int qhi = hi > 0.0 ? (int)fmin(floor(hi / lid.unit), 2.0e9) : -1;
-    if (qhi >= 0) {
-        const int b0 = min(qlo / SLAM2D_SPOKE_BAND, nb), b1 = min(qhi / SLAM2D_SPOKE_BAND + 1, nb);
-        for (int k = bp[b0] + lane; k < bp[max(b0, b1)]; k += 64) {
+    int kbeg, kwall, kend;
+    if (beam_bands(lid, beam_spoke(lid, th, beam), lo, hi, false, kbeg, kwall, kend)) {
+        for (int k = kbeg + lane; k < kend; k += 64) {
             const double r = lid.spoke_r[k];
             if (!(r > lo && r < hi)) continue;                                     // :142-143
             const uint32_t c = lid.spoke_cells[k];
@@ -4100,15 +4097,11 @@ __global__ __launch_bounds__(64 * MAPS_BEAMS) void k_map_scans(Slam2dLidar lid, 
     const double rg = ranges[(size_t)s * lid.beams + beam];
     const double lo = rg - lid.wall_half, hi = rg + lid.wall_half;
     const bool returned = rg < lid.max_range;
-    const int W = lid.lut_w, nb = lid.num_bands, spoke = beam_spoke(lid, th, beam);
-    const int* __restrict__ bp = lid.spoke_band + (size_t)spoke * (nb + 1);
-    const int qlo = lo > 0.0 ? (int)fmin(floor(lo / lid.unit), 2.0e9) : 0;
-    const int qhi = hi > 0.0 ? (int)fmin(floor(hi / lid.unit), 2.0e9) : -1;
-    if (qhi < 0) return;
-    const int b0 = returned ? 0 : min(qlo / SLAM2D_SPOKE_BAND, nb), b1 = min(qhi / SLAM2D_SPOKE_BAND + 1, nb);
-    const int kend = bp[max(b0, b1)];
+    const int W = lid.lut_w, spoke = beam_spoke(lid, th, beam);
+    int kbeg, kwall, kend;
+    if (!beam_bands(lid, spoke, lo, hi, returned, kbeg, kwall, kend)) return;
     uint32_t f = 0;
-    for (int k = bp[b0] + lane; k < kend; k += 64) {
+    for (int k = kbeg + lane; k < kend; k += 64) {
         const double r = lid.spoke_r[k];
         const int cls = (returned && r < lo) ? 1 : (r > lo && r < hi) ? 2 : 0;       // :138-143
         if (!cls) continue;
@@ -4155,15 +4148,13 @@ __global__ __launch_bounds__(64 * MAPS_BEAMS) void k_map_scans(Slam2dLidar lid, 
 
 // The cells k = kb + lane + 64 u (u < PRED_UNROLL) of one spoke list: rr[u] = the cell's tabulated radius where it is a HIT -- k < kend,
 // its map index inside the map, its occupancy bit set, r_min < r < r_max -- and +inf elsewhere.  Straight-line phases, every load
-// of a phase issued before its first use: the walk is a chain list -> cell -> bit word.  The map index is convertRealXYToMapIdx
-// (:104-105,144-145) with k_grid_update's two shortcuts, which give the exact division's integers: the lattice offset (decided
-// once per wave by the caller) and the reciprocal with the exact-division fallback next to a rounding boundary.  A cell outside
-// the map reads bit word 0 and discards it: no access leaves the map.
+// of a phase issued before its first use: the walk is a chain list -> cell -> bit word.  The map index is the update's own
+// (window_map_index, the lattice decided once per wave by the caller).  A cell outside the map reads bit word 0 and discards
+// it: no access leaves the map.
 __device__ __forceinline__ void predict_hits(const Slam2dLidar& lid, const Slam2dMap& m, const int kb, const int kend, const int lane,
                                              const double px, const double py, const double inv_unit, const bool lattice,
                                              const int bx, const int by, const double r_min, const double r_max,
                                              double (&rr)[PRED_UNROLL]) {
-    const int W = lid.lut_w;
     double r[PRED_UNROLL];
     uint32_t cell[PRED_UNROLL], word[PRED_UNROLL];
     int mxs[PRED_UNROLL], mys[PRED_UNROLL];
@@ -4173,45 +4164,7 @@ __device__ __forceinline__ void predict_hits(const Slam2dLidar& lid, const Slam2
         r[u] = lid.spoke_r[k];
         cell[u] = lid.spoke_cells[k];
     }
-    if (lattice) {
-#pragma unroll
-        for (int u = 0; u < PRED_UNROLL; ++u) {
-            mxs[u] = (int)(cell[u] & 0xffffu) + bx;
-            mys[u] = (int)(cell[u] >> 16) + by;
-        }
-    } else {
-        double xj[PRED_UNROLL], yi[PRED_UNROLL];
-        if (lid.lut_xs_step != 0.0) {
-#pragma unroll
-            for (int u = 0; u < PRED_UNROLL; ++u) {
-                const int cj = (int)(cell[u] & 0xffffu), ci = (int)(cell[u] >> 16);
-                xj[u] = cj == W - 1 ? lid.max_range : (double)cj * lid.lut_xs_step + -lid.max_range;
-                yi[u] = ci == W - 1 ? lid.max_range : (double)ci * lid.lut_xs_step + -lid.max_range;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < PRED_UNROLL; ++u) {
-                xj[u] = lid.lut_xs[cell[u] & 0xffffu];
-                yi[u] = lid.lut_xs[cell[u] >> 16];
-            }
-        }
-        bool slow = false;
-#pragma unroll
-        for (int u = 0; u < PRED_UNROLL; ++u) {
-            const double tx = ((px + xj[u]) - m.lim_x0) * inv_unit, ty = ((py + yi[u]) - m.lim_y0) * inv_unit;
-            const double rx = rint(tx), ry = rint(ty);
-            slow |= fabs(fabs(tx - rx) - 0.5) < 1e-6 || fabs(fabs(ty - ry) - 0.5) < 1e-6 || !(fabs(tx) < 1e9) || !(fabs(ty) < 1e9);
-            mxs[u] = (int)rx; mys[u] = (int)ry;           // (a quotient beyond 1e9 is replaced below before anything reads this)
-        }
-        if (__any(slow)) {                                 // a quotient next to a rounding boundary: exact division
-#pragma unroll
-            for (int u = 0; u < PRED_UNROLL; ++u) {
-                const double tx = ((px + xj[u]) - m.lim_x0) / lid.unit, ty = ((py + yi[u]) - m.lim_y0) / lid.unit;
-                mxs[u] = fabs(tx) < 1e9 ? (int)rint(tx) : -1;
-                mys[u] = fabs(ty) < 1e9 ? (int)rint(ty) : -1;
-            }
-        }
-    }
+    window_map_index<PRED_UNROLL>(lid, m, px, py, inv_unit, lattice, bx, by, cell, mxs, mys);
     bool inside[PRED_UNROLL];
 #pragma unroll
     for (int u = 0; u < PRED_UNROLL; ++u) {
@@ -4247,18 +4200,12 @@ __global__ __launch_bounds__(64 * MAPS_BEAMS) void k_predict_scan(Slam2dLidar li
                        fabs(((px + -R) - m.lim_x0) / lid.unit) < 1e9 && fabs(((px + R) - m.lim_x0) / lid.unit) < 1e9 &&
                        fabs(((py + -R) - m.lim_y0) / lid.unit) < 1e9 && fabs(((py + R) - m.lim_y0) / lid.unit) < 1e9;
     if (valid && m.rows > 0 && m.cols > 0 && m.occ_bits) {
-        const int nb = lid.num_bands;
-        const int* __restrict__ bp = lid.spoke_band + (size_t)beam_spoke(lid, th, beam) * (nb + 1);
-        // cells with r > r_min sit in bands >= band(r_min), cells with r < r_max in bands <= band(r_max)
-        const int qlo = (int)fmin(floor(r_min / lid.unit), 2.0e9), qhi = (int)fmin(floor(r_max / lid.unit), 2.0e9);
-        const int kbeg = bp[min(qlo / SLAM2D_SPOKE_BAND, nb)], kend = bp[min(qhi / SLAM2D_SPOKE_BAND + 1, nb)];
+        const int nb = lid.num_bands, spoke = beam_spoke(lid, th, beam);
+        const int* __restrict__ bp = spoke_bands(lid, spoke);
+        int kbeg = 0, kwall = 0, kend = 0;                                     // (an empty walk; never left so: the host admits
+        beam_bands(lid, spoke, r_min, r_max, false, kbeg, kwall, kend);        //  0 <= r_min < r_max only)
         const double inv_unit = 1.0 / lid.unit;
-        // the lattice shortcut of k_grid_update, under its conditions: window step == map unit, the offset away from a half cell
-        const double Ax = ((px + -R) - m.lim_x0) * inv_unit, Ay = ((py + -R) - m.lim_y0) * inv_unit;
-        const double rAx = rint(Ax), rAy = rint(Ay);
-        const bool lattice = lid.lut_xs_step == lid.unit && fabs(Ax) < 1e8 && fabs(Ay) < 1e8 &&
-                             fabs(fabs(Ax - rAx) - 0.5) > 1e-6 && fabs(fabs(Ay - rAy) - 0.5) > 1e-6;
-        const int bx = lattice ? (int)rAx : 0, by = lattice ? (int)rAy : 0;
+        const WindowLattice wl = window_lattice(lid, m, px, py, inv_unit);
         // the band starts of the spoke, one per lane (a table of more than 64 entries is read from memory): the walk's limits
         // follow the nearest hit found so far, and a load from the table there would sit in the chain of every chunk
         const int bp_lane = (nb < 64 && lane <= nb) ? bp[lane] : 0;
@@ -4272,7 +4219,7 @@ __global__ __launch_bounds__(64 * MAPS_BEAMS) void k_predict_scan(Slam2dLidar li
         int fb = 0, klim = kend, nkept = 0;
         for (int kb = kbeg; kb < klim; kb += 64 * PRED_UNROLL) {
             double rr[PRED_UNROLL];
-            predict_hits(lid, m, kb, kend, lane, px, py, inv_unit, lattice, bx, by, r_min, r_max, rr);
+            predict_hits(lid, m, kb, kend, lane, px, py, inv_unit, wl.on, wl.bx, wl.by, r_min, r_max, rr);
             double lr = rr[0];
 #pragma unroll
             for (int u = 1; u < PRED_UNROLL; ++u) lr = fmin(lr, rr[u]);
@@ -4309,7 +4256,7 @@ __global__ __launch_bounds__(64 * MAPS_BEAMS) void k_predict_scan(Slam2dLidar li
                 const int wbeg = max(kbeg, band_start(fb));
                 for (int kb = wbeg; kb < klim; kb += 64 * PRED_UNROLL) {
                     double rr[PRED_UNROLL];
-                    predict_hits(lid, m, kb, klim, lane, px, py, inv_unit, lattice, bx, by, r_min, r_max, rr);
+                    predict_hits(lid, m, kb, klim, lane, px, py, inv_unit, wl.on, wl.bx, wl.by, r_min, r_max, rr);
 #pragma unroll
                     for (int u = 0; u < PRED_UNROLL; ++u) {
                         const bool in_wall = rr[u] < wall_end;
@@ -5176,12 +5123,20 @@ int slam2d_match_moments(const Slam2dLevel* level, int32_t P, const double* d_es
     return launch_status();
 }
 
+// The lidar tables every spoke walk reads (k_grid_update, k_occ_extent, k_map_scans, k_predict_scan).  need_table: the kernel reads
+// lut_xs itself; the others take the window coordinates from lut_xs_step where it is set (window_coord).  The negated form refuses
+// a NaN unit.  The beam count is each entry point's own check: their codes differ.
+static int check_spoke_lidar(const Slam2dLidar* lidar, const bool need_table) {
+    if (!lidar || !lidar->spoke_band || !lidar->spoke_cells || !lidar->spoke_r) return SLAM2D_E_BADARG;
+    if (lidar->num_bands < 1 || lidar->num_spokes < 1 || lidar->lut_w < 2 || lidar->lut_w > 65535 || !(lidar->unit > 0.0)) return SLAM2D_E_BADARG;
+    if (!lidar->lut_xs && (need_table || lidar->lut_xs_step == 0.0)) return SLAM2D_E_BADARG;
+    return 0;
+}
+
 static int launch_update(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t P, const double* d_pose, int32_t pose_stride,
                          const double* d_ranges, const int32_t* d_beam_shift, uint32_t* d_flags, const WeightsJob& wj, void* stream) {
-    if (!lidar || !d_maps || !d_pose || !d_ranges || !d_flags || P <= 0 || pose_stride < 3) return SLAM2D_E_BADARG;
+    if (!d_maps || !d_pose || !d_ranges || !d_flags || P <= 0 || pose_stride < 3 || check_spoke_lidar(lidar, false)) return SLAM2D_E_BADARG;
     if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_TOOLARGE;
-    if (!lidar->spoke_band || !lidar->spoke_cells || !lidar->spoke_r || lidar->num_bands < 1 || lidar->lut_w > 65535)
-        return SLAM2D_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const int groups = cdiv(lidar->beams, UPDB_BEAMS);
     StageScope prof(SLAM2D_STAGE_UPDATE, s);
@@ -5198,10 +5153,8 @@ int slam2d_grid_update(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_
 
 int slam2d_occ_extent(const Slam2dLidar* lidar, int32_t S, const double* d_pose, int32_t pose_stride, const double* d_ranges,
                       double* d_out, void* stream) {
-    if (!lidar || !d_pose || !d_ranges || !d_out || S <= 0 || pose_stride < 3) return SLAM2D_E_BADARG;
+    if (!d_pose || !d_ranges || !d_out || S <= 0 || pose_stride < 3 || check_spoke_lidar(lidar, true)) return SLAM2D_E_BADARG;
     if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_TOOLARGE;
-    if (!lidar->spoke_band || !lidar->spoke_cells || !lidar->spoke_r || !lidar->lut_xs || lidar->num_bands < 1 || lidar->lut_w > 65535)
-        return SLAM2D_E_BADARG;
     const int groups = cdiv(lidar->beams, MAPS_BEAMS);
     if ((long long)S * groups > 0x7fffffffll) return SLAM2D_E_TOOLARGE;
     k_occ_extent<<<S * groups, 64 * MAPS_BEAMS, 0, (hipStream_t)stream>>>(*lidar, S, groups, d_pose, pose_stride, d_ranges, d_out);
@@ -5211,12 +5164,10 @@ int slam2d_occ_extent(const Slam2dLidar* lidar, int32_t S, const double* d_pose,
 int slam2d_map_scans(const Slam2dLidar* lidar, const Slam2dMap* d_map, int32_t S, const double* d_pose, int32_t pose_stride,
                      const double* d_ranges, const Slam2dBeamPlan* d_plan, const uint16_t* d_lut_bin, const double* d_lut_r,
                      uint32_t* d_flags, void* stream) {
-    if (!lidar || !d_map || !d_pose || !d_ranges || !d_plan || !d_lut_bin || !d_lut_r || !d_flags || S <= 0 || pose_stride < 3)
+    if (!d_map || !d_pose || !d_ranges || !d_plan || !d_lut_bin || !d_lut_r || !d_flags || S <= 0 || pose_stride < 3 ||
+        check_spoke_lidar(lidar, true))
         return SLAM2D_E_BADARG;
     if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_TOOLARGE;
-    if (!lidar->spoke_band || !lidar->spoke_cells || !lidar->spoke_r || !lidar->lut_xs || lidar->num_bands < 1 || lidar->lut_w > 65535 ||
-        lidar->lut_w < 2)
-        return SLAM2D_E_BADARG;
     const int groups = cdiv(lidar->beams, MAPS_BEAMS);
     if ((long long)S * groups > 0x7fffffffll) return SLAM2D_E_TOOLARGE;
     k_map_scans<<<S * groups, 64 * MAPS_BEAMS, 0, (hipStream_t)stream>>>(*lidar, d_map, S, groups, d_pose, pose_stride, d_ranges, d_plan, d_lut_bin,
@@ -5226,10 +5177,7 @@ int slam2d_map_scans(const Slam2dLidar* lidar, const Slam2dMap* d_map, int32_t S
 
 int slam2d_predict_scan(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t map_stride, int32_t S, const double* d_pose,
                         int32_t pose_stride, double r_min, double r_max, double* d_out, void* stream) {
-    if (!lidar || !d_maps || !d_pose || !d_out || S <= 0 || pose_stride < 3 || (map_stride != 0 && map_stride != 1))
-        return SLAM2D_E_BADARG;
-    if (!lidar->spoke_band || !lidar->spoke_cells || !lidar->spoke_r || (!lidar->lut_xs && lidar->lut_xs_step == 0.0) ||
-        lidar->num_bands < 1 || lidar->num_spokes < 1 || lidar->lut_w < 2 || lidar->lut_w > 65535 || !(lidar->unit > 0.0))
+    if (!d_maps || !d_pose || !d_out || S <= 0 || pose_stride < 3 || (map_stride != 0 && map_stride != 1) || check_spoke_lidar(lidar, false))
         return SLAM2D_E_BADARG;
     if (lidar->beams <= 0 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_BADARG;
     if (!(r_min >= 0.0) || !(r_max > r_min)) return SLAM2D_E_BADARG;              // (the negated forms refuse a NaN)

@@ -410,3 +410,45 @@ def test_grid_update_flags_a_particle_on_a_half_cell_and_leaves_its_map(pkg, mod
     with pytest.raises(E._lib.Slam2dError, match="half cell"):
         eng.grid_update(d_pose, 3, d_rng)
         eng.take_flags()
+
+
+@pytest.mark.parametrize("mode", ["plain", "stale_index", "fused"])
+def test_grid_update_flags_a_particle_without_a_map_index_and_leaves_its_map(pkg, mode):
+    """slam2d_grid_update with a particle at x = NaN and one at x = 2e8 (map-index quotient 2e9: neighbouring window columns stay
+    distinct there, so the collision test does not fire) between particles off and on the lattice: the former two have no map
+    index an int can hold, get exactly SLAM2D_F_UPDATE_OUTSIDE_MAP and keep their maps bit for bit -- cell (0, 0) and the last
+    column, where a converted NaN or a wrapped -1 would land, included; the latter two are updated as the oracle says -- twice
+    the same.  Also through the stale-index launch (zero shifts, Python's wrap applied) and the fused launch."""
+    import torch
+    s = se.sensor(0)
+    lut = se.lut_of(s)
+    rs = np.random.RandomState(78)
+    kinds = ["off", "nan_x", "huge_x", "on"]
+    P = len(kinds)
+    og0 = se.grid_of(s, lut)
+    poses = [se.pose_of(rs, s, og0, "off" if k.endswith("_x") else k) for k in kinds]
+    poses[1] = (float("nan"),) + poses[1][1:]
+    poses[2] = (2e8,) + poses[2][1:]
+    ranges = se.random_ranges(rs, s)
+    se.plant(rs, s, lut, poses[0][2], ranges)
+    for _ in range(2):
+        eng = _engine(s, P)
+        d_pose, d_rng = eng.to_device(np.array(poses)), eng.to_device(ranges)
+        if mode == "fused":
+            logw = torch.full((P,), -np.log(P), dtype=torch.float64, device=DEVICE)
+            eng.grid_update_weights(d_pose, 3, d_rng, logw, eng.to_device(np.zeros(P)).data_ptr(), 1,
+                                    torch.zeros(P, dtype=torch.float64, device=DEVICE), torch.zeros(2, dtype=torch.float64, device=DEVICE))
+        else:
+            shift = np.zeros((P, s["beams"], 6), dtype=np.int32)
+            shift[:, :, 4], shift[:, :, 5] = eng.maps[0].cols, eng.maps[0].rows
+            eng.grid_update(d_pose, 3, d_rng, eng.to_device(shift, dtype=np.int32) if mode == "stale_index" else None)
+        flags = eng.take_flags(fatal=0)
+        for p, kind in enumerate(kinds):
+            x, y, th = poses[p]
+            og = se.grid_of(s, lut)
+            if kind.endswith("_x"):
+                assert flags[p] == E._lib.F_UPDATE_OUTSIDE_MAP, (mode, p, flags)
+            else:
+                assert flags[p] == 0, (mode, p, flags)
+                og.update_cell_major({"x": x, "y": y, "theta": th, "range": ranges})
+            _assert_counts(eng.maps[p], og, f"{mode}: particle {p} ({kind}) pose {poses[p]}")
