@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Global re-localisation in a finished map with ScanMatcher.scorePoses: where in the map was this scan taken?
 
-    python examples/relocalise.py [--scans 3] [--step 0.1] [--headings 120] [--level fine]
+    python examples/relocalise.py [--scans 3] [--step 0.1] [--headings 120] [--level fine] [--on-device]
 
 Maps a seeded walk of 40 scans through a synthetic world (OccupancyGrid.update_many at the walk's poses), then for a few of
 the walk's scans scores a whole lattice of candidate poses -- x, y every --step metres over the map, --headings headings: 3.1
 million poses by default -- in ONE launch each, prints the best candidate by `beam_score` beside the pose the scan was taken at, and refines it with matchScan.  The lattice search lives here, not in the library: scorePoses answers "how
 well does this scan fit at these poses", for any pose set.
+
+With --on-device the lattice search runs in the library instead (ScanMatcher.searchPoses, slam2d_search_lattice): no pose is
+uploaded, the best heading and its cost per position come back -- an image of 161 x 161 words instead of 3.1 million rows --
+and the well-separated runner-up positions are printed beside the best.
 
 `beam_score` (the field's cost summed over every beam) ranks the candidates, not `score` (summed over the set of cells the beams
 end in, the reference's own score): the latter rewards a pose that folds the scan into few cells.  The peak at the true pose is
@@ -57,6 +61,7 @@ def main():
     ap.add_argument("--step", type=float, default=0.1, help="lattice spacing in metres")
     ap.add_argument("--headings", type=int, default=120)
     ap.add_argument("--level", choices=("coarse", "fine"), default="fine")
+    ap.add_argument("--on-device", action="store_true", help="search the lattice with ScanMatcher.searchPoses")
     args = ap.parse_args()
     pkg = importlib.import_module("slam-2d-lidar-scan_amd")
     og, readings, window = synthetic(pkg, args.scans)
@@ -65,18 +70,33 @@ def main():
     print(f"{len(poses)} candidate poses: a lattice of {args.step:g} m over {2 * window[2]:g} m x {2 * window[2]:g} m, {args.headings} headings; "
           f"{len(readings[0]['range'])} beams; the {args.level} level")
     sm.scorePoses(poses[:8], readings[0], level=args.level, window=window)           # (warm-up: level allocation, first launches)
+    if args.on_device:
+        sm.searchPoses(readings[0], window, step=args.step, headings=args.headings, level=args.level)
     for r in readings:
         t0 = time.perf_counter()
-        s = sm.scorePoses(poses, r, level=args.level, window=window)
-        dt = time.perf_counter() - t0
-        best = int(np.argmax(np.where(s["inside"] > 0, s["beam_score"], -np.inf)))
-        bx, by, bth = poses[best]
+        if args.on_device:
+            found = sm.searchPoses(r, window, step=args.step, headings=args.headings, level=args.level, top=4)
+            dt = time.perf_counter() - t0
+            p = found["peaks"][0]
+            iy, ix = int(np.argmin(np.abs(found["ys"] - p.y))), int(np.argmin(np.abs(found["xs"] - p.x)))
+            best = (iy * len(found["xs"]) + ix) * args.headings + int(found["heading"][iy, ix])
+            bx, by, bth = p.x, p.y, p.theta
+            s = sm.scorePoses([(bx, by, bth)], r, level=args.level, window=window)      # (the best pose's own row, for the line below)
+            s = {k: {best: v[0]} for k, v in s.items()}
+        else:
+            s = sm.scorePoses(poses, r, level=args.level, window=window)
+            dt = time.perf_counter() - t0
+            best = int(np.argmax(np.where(s["inside"] > 0, s["beam_score"], -np.inf)))
+            bx, by, bth = poses[best]
         guess = {"x": float(bx), "y": float(by), "theta": float(bth), "range": r["range"]}
         matched, conf = sm.matchScan(guess, 0.0, None, 2, matchMax=True)
         dth = (matched["theta"] - r["theta"] + np.pi) % (2 * np.pi) - np.pi
         print(f"true ({r['x']:7.2f}, {r['y']:7.2f}, {r['theta']:6.3f})  lattice best ({bx:7.2f}, {by:7.2f}, {bth:6.3f}) beam_score {s['beam_score'][best]:9.2f} "
               f"over {s['cells'][best]} cells  refined ({matched['x']:7.2f}, {matched['y']:7.2f}, {matched['theta']:6.3f})  "
               f"off by {np.hypot(matched['x'] - r['x'], matched['y'] - r['y']):.2f} m, {abs(dth):.3f} rad  [{1e3 * dt:.1f} ms for the lattice, build and download included]")
+        if args.on_device:
+            for q in found["peaks"][1:]:
+                print(f"     runner-up ({q.x:7.2f}, {q.y:7.2f}, {q.theta:6.3f}) score {q.score:9.2f}")
 
 
 if __name__ == "__main__":

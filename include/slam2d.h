@@ -517,6 +517,39 @@ int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32
                        const double* d_ranges, int32_t ranges_stride,
                        double* d_out, void* stream);
 
+/* The best heading and its cost at every position of a lattice of poses, for one scan in a level's field: the global search
+ * built on slam2d_score_poses' definition, on the device from the lattice's nine numbers to a [ny][nx] image -- no pose is
+ * uploaded, nothing is stored per pose (an added symbol: no struct and no existing signature changed, the ABI number stays).
+ * PRECONDITION: that of slam2d_score_poses (the FULL slam2d_field_build has run for slot p_field of `level`, ordered in front
+ * of this call); the same members of `level` and `lidar` are read.  Lattice pose (it, iy, ix), 0 <= it < nth, 0 <= iy < ny,
+ * 0 <= ix < nx:
+ *   x = x0 + (double)ix * dx,  y = y0 + (double)iy * dy,  theta = th0 + (double)it * dth
+ * each a rounded product, then an add (no contraction: NumPy's x0 + np.arange(nx) * dx has the same bits).  For that pose and
+ * the ONE scan d_ranges[beams], steps 1-5 of slam2d_score_poses define sum_b, the number of INSIDE beams and of beams IN RANGE,
+ * identical in every operation and their order (the true division (px - xlo) / step and the 1e9 guard included); sum_u and |U|
+ * are not computed.
+ *   cost(it, iy, ix) = sum_b + (uint64)(in_range - inside) * outside_cost       (below 2^44 at 2048 beams)
+ * -- without the second term a pose whose beams leave the field would pay nothing for them and win --
+ *   d_out[iy * nx + ix] = (min over it of cost) << 16 | it_min,   it_min the LOWEST heading index that attains the minimum,
+ * i.e. the 64-bit minimum of (cost << 16 | it) over it: independent of the order in which headings are visited.
+ *   d_work: slam2d_search_lattice_work(lidar, nx, ny, nth) 8-byte words of scratch (the beams' endpoint offsets cos(a) * r,
+ *           sin(a) * r per heading: cos / sin are evaluated nth * beams times, not once per pose and beam)
+ * The same inputs give the same bits on every call; the caller need not initialise d_out or d_work.  A non-finite x0, y0 or th0
+ * leaves no inside beam (cost = in_range * outside_cost, heading 0) and never reaches a conversion to an integer; no field access
+ * leaves [0, fh) x [0, fw).  No fault bit is raised and nothing is allocated: the call enqueues two launches on `stream` (the
+ * table and the initial d_out; the search, which joins its heading chunks with a 64-bit integer atomicMin on d_out) and does not
+ * synchronise.  SLAM2D_E_BADARG, before any HIP call: a NULL lidar, level, d_ranges or d_out, a NULL d_work where the work size
+ * is > 0, a level without field or frames, p_field < 0, nx, ny or nth < 1, nth > 65536, a non-finite dx, dy or dth, beams < 1 or
+ * > SLAM2D_MAX_BEAMS, !(max_range > 0), !(step > 0), !(cost_scale > 0), fmax <= 0 or fpitch < fmax; SLAM2D_E_TOOLARGE:
+ * nx * ny >= 2^31, a work size beyond 2^31 words (2 * nth * beams: at most 2^28 within the limits above), fmax * fpitch >= 2^29.
+ * slam2d_search_lattice_work makes no HIP call; < 0 means SLAM2D_E_* (the lidar, nx, ny, nth cases above). */
+int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field,
+                          int32_t nx, int32_t ny, int32_t nth,
+                          double x0, double dx, double y0, double dy, double th0, double dth,
+                          const double* d_ranges, uint32_t outside_cost,
+                          uint64_t* d_work, uint64_t* d_out, void* stream);
+int64_t slam2d_search_lattice_work(const Slam2dLidar* lidar, int32_t nx, int32_t ny, int32_t nth);
+
 /* Particle.updateEstimatedPose for P particles (Algorithm/FastSlam.py:77-106): the pose prior of the
  * next scan from the previous matched poses and the raw odometry increment.
  *   d_prev_pose[p*3 + 0..2]  previous matched pose (prevMatchedReading)

@@ -55,8 +55,10 @@ BNB_MARGIN = 30.0
 MOMENTS_STRIDE = 16                  # doubles per particle of slam2d_match_moments' output row
 PREDICT_STRIDE = 4                   # doubles per (pose, beam) of slam2d_predict_scan's output: r_hit, r_far, n_hit, 0
 SCORE_STRIDE = 8                     # doubles per pose of slam2d_score_poses' output: score, |U|, beam score, inside, in range, sum_u, sum_b, 0
+SEARCH_CHUNK = 8                     # headings per block row of slam2d_search_lattice's search launch, at least (csrc: SEARCH_CHUNK)
+SEARCH_WAVES = 4096                  # ... and more where fewer than this many waves of 64 positions would not fill the card otherwise
 
-STAGE_SWEEP, STAGE_BLUR, STAGE_SCATTER, STAGE_UPDATE, STAGE_SELECT, STAGE_ENDPOINTS, STAGE_BOUND, STAGE_EXACT = range(8)
+STAGE_SWEEP,STAGE_BLUR, STAGE_SCATTER, STAGE_UPDATE, STAGE_SELECT, STAGE_ENDPOINTS, STAGE_BOUND, STAGE_EXACT = range(8)
 STAGE_NAMES = {STAGE_SWEEP: "k_sweep", STAGE_BLUR: "k_blur_clamp", STAGE_SCATTER: "k_occ_scatter",
                STAGE_UPDATE: "k_grid_update", STAGE_SELECT: "k_select", STAGE_ENDPOINTS: "k_endpoints",
                STAGE_BOUND: "k_bound", STAGE_EXACT: "k_exact"}
@@ -168,6 +170,9 @@ SIGNATURES = {
     "slam2d_grid_update": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "slam2d_predict_scan": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_double, C.c_double, _vp, _vp]),
     "slam2d_score_poses": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
+    "slam2d_search_lattice": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "slam2d_search_lattice_work": (C.c_int64, [C.POINTER(Slam2dLidar), C.c_int32, C.c_int32, C.c_int32]),
     "slam2d_occ_extent": (C.c_int, [C.POINTER(Slam2dLidar), C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "slam2d_map_scans": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "slam2d_prior": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int32, C.c_double, _vp, C.c_int32, _vp, _vp, _vp]),

@@ -4296,6 +4296,18 @@ __device__ __forceinline__ unsigned long long wave64_sum_u64(const unsigned long
     return s;
 }
 
+// The beam-to-cell step of slam2d_score_poses and slam2d_search_lattice (include/slam2d.h, steps 3-4 of the former): the field
+// cell an endpoint falls in, and whether the beam is INSIDE.  The true division; a quotient that fails the guard -- a NaN fails
+// it -- never reaches the conversion; truncation as astype(int) has it.
+__device__ __forceinline__ bool score_cell(const double px, const double py, const double xlo, const double ylo, const double step,
+                                           const int fw, const int fh, int& cx, int& cy) {
+    const double qx = (px - xlo) / step, qy = (py - ylo) / step;                 // :174-175
+    if (!(fabs(qx) < 1e9 && fabs(qy) < 1e9)) return false;
+    cx = (int)qx;
+    cy = (int)qy;
+    return cx >= 0 && cx < fw && cy >= 0 && cy < fh;
+}
+
 // One wave per pose, blockDim.x / 64 poses per block, beams interleaved over the lanes (beam = 64 i + lane: a wave's range loads
 // are contiguous).  out[n * SLAM2D_SCORE_STRIDE + 0..7] as include/slam2d.h lists them.  The hash set holds keys only: the lane
 // whose atomicCAS finds a slot empty owns the cell and adds its cost to sum_u, every inside beam adds to sum_b.  The wave's
@@ -4334,14 +4346,11 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar li
         if (in_range) {
             const double a = B == 1 ? a0 : (b == B - 1) ? a1 : (double)b * astep + a0;
             const double px = x + cos(a) * r, py = y + sin(a) * r;               // :87-88
-            const double qx = (px - fr.xlo) / lv.step, qy = (py - fr.ylo) / lv.step;   // :174-175
-            if (fabs(qx) < 1e9 && fabs(qy) < 1e9) {                              // (the negated forms keep a NaN from the conversion)
-                const int cx = (int)qx, cy = (int)qy;                            // astype(int): truncation
-                if (cx >= 0 && cx < fw && cy >= 0 && cy < fh) {
-                    inside = true;
-                    key = (cy << 16) | cx;
-                    cost = field[(size_t)cy * lv.fpitch + cx];
-                }
+            int cx, cy;
+            if (score_cell(px, py, fr.xlo, fr.ylo, lv.step, fw, fh, cx, cy)) {
+                inside = true;
+                key = (cy << 16) | cx;
+                cost = field[(size_t)cy * lv.fpitch + cx];
             }
         }
         bool owns = false;
@@ -4368,6 +4377,92 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar li
         o[0] = -((double)sum_u * inv); o[1] = (double)n_u; o[2] = -((double)sum_b * inv); o[3] = (double)n_in;
         o[4] = (double)n_rng; o[5] = (double)sum_u; o[6] = (double)sum_b; o[7] = 0.0;
     }
+}
+
+// ---- the best heading and its cost at every position of a lattice of poses (slam2d_search_lattice) ----
+#define SEARCH_CHUNK 8               // headings one block row takes at least (tests/test_gpu_search.py names it)
+#define SEARCH_UNROLL 4              // beams of one trip of the search's inner loop: their table entries and gathers are in flight together
+#define SEARCH_WAVES 4096            // waves that fill the card: 256 CUs x 4 SIMDs x 4; windows with fewer split their headings further
+
+// headings per block row (gridDim.y rows): at least SEARCH_CHUNK, more where the positions alone fill the card
+__host__ __device__ __forceinline__ int search_chunk(const long long positions, const int nth) {
+    const long long waves = (positions + WAVE - 1) / WAVE;
+    const long long rows = (SEARCH_WAVES + waves - 1) / waves;                   // (>= 1)
+    const long long hc = ((long long)nth + rows - 1) / rows;
+    return hc > SEARCH_CHUNK ? (int)hc : SEARCH_CHUNK;
+}
+
+// First launch: E[it][k] = (cos(a_b) * r_b, sin(a_b) * r_b) of heading it and the k-th beam IN RANGE, b -- the only cos / sin of the
+// search, the angles as k_score_poses forms them, the products rounded here so that x + e is x + cos(a) * r bit for bit (no
+// contraction).  Which beams are in range does not depend on the pose: every heading's row is compacted alike, k = the number of
+// beams in range below b (the lanes of a wave read ranges[j] at one address), and the search sums integers, in any order.  Also
+// d_out = all ones, the identity of the search launch's atomicMin.
+__global__ __launch_bounds__(256) void k_search_table(Slam2dLidar lid, int nth, double th0, double dth, const double* __restrict__ ranges,
+                                                      double2* __restrict__ E, unsigned long long* __restrict__ out, int positions) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;                           // (positions < 2^31: no wrap)
+    const int B = lid.beams;
+    if (i < (unsigned)positions) out[i] = ~0ull;
+    if (i >= (unsigned)(nth * B)) return;
+    const int it = (int)i / B, b = (int)i - it * B;
+    const double r = ranges[b];
+    if (!(r < lid.max_range)) return;                                            // :84 (NaN and +inf are out, 0 and negatives in)
+    int k = 0;
+    for (int j = 0; j < b; ++j) k += ranges[j] < lid.max_range;
+    const double th = th0 + (double)it * dth;
+    const double a0 = th - lid.fov / 2, a1 = th + lid.fov / 2;                   // np.linspace(theta - fov/2, theta + fov/2, num=B) (:82-83)
+    const double astep = (a1 - a0) / (double)(B - 1);
+    const double a = B == 1 ? a0 : (b == B - 1) ? a1 : (double)b * astep + a0;
+    E[(size_t)it * B + k] = make_double2(cos(a) * r, sin(a) * r);                // :87-88
+}
+
+// Search launch: one thread per position (flat index iy * nx + ix: neighbouring lanes read neighbouring field cells), blockIdx.y
+// takes headings [y * hc, y * hc + hc).  The loops over headings and beams are the same for every lane and E is read at a
+// wave-uniform address.  Each lane sums the inside beams' costs and counts them in registers -- a beam that is not inside loads
+// cell 0 of the image and adds nothing: no branch in the loop, so the gathers of several beams are in flight together --, folds
+// cost << 16 | it into a 64-bit minimum per heading and joins the block rows with one integer atomicMin on d_out, which
+// k_search_table set to all ones in front of this launch on the same stream: a minimum of integers, whatever the order.  Reads
+// frames[p_field], the slot's field, E and the ranges; no fault bit.
+__global__ __launch_bounds__(256) void k_search_lattice(Slam2dLidar lid, Slam2dLevel lv, int p_field, int nx, int positions, int nth, int hc,
+                                                        double x0, double dx, double y0, double dy, const double* __restrict__ ranges,
+                                                        const double2* __restrict__ E, unsigned outside_cost,
+                                                        unsigned long long* __restrict__ out) {
+    const unsigned p = blockIdx.x * 256u + threadIdx.x;                           // (positions < 2^31: no wrap)
+    if (p >= (unsigned)positions) return;
+    const Slam2dFrame fr = lv.frames[p_field];
+    // (a frame is at most fmax x fmax: whatever the frame record holds, no access leaves the slot's image)
+    const int fw = min(fr.fw, min(lv.fmax, lv.fpitch)), fh = min(fr.fh, lv.fmax);
+    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const int B = lid.beams;
+    const int iy = (int)p / nx, ix = (int)p - iy * nx;
+    const double x = x0 + (double)ix * dx, y = y0 + (double)iy * dy;
+    int n_rng = 0;                                                               // beams in range: the same at every pose
+    for (int b = 0; b < B; ++b) n_rng += ranges[b] < lid.max_range;
+    const int it0 = blockIdx.y * hc, it1 = min(nth, it0 + hc);
+    unsigned long long best = ~0ull;
+    for (int it = it0; it < it1; ++it) {
+        const double2* __restrict__ e = E + (size_t)it * B;
+        unsigned long long sum_b = 0ull;
+        int n_in = 0;
+        const auto beam = [&](const double2 d) {
+            int cx, cy;
+            const bool inside = score_cell(x + d.x, y + d.y, fr.xlo, fr.ylo, lv.step, fw, fh, cx, cy);
+            const uint32_t cost = field[inside ? cy * lv.fpitch + cx : 0];       // (fmax * fpitch < 2^29)
+            sum_b += inside ? cost : 0u;
+            n_in += inside;
+        };
+        int k = 0;
+        for (; k + SEARCH_UNROLL <= n_rng; k += SEARCH_UNROLL) {                 // (the table entries first: one wait for all of them)
+            double2 d[SEARCH_UNROLL];
+#pragma unroll
+            for (int u = 0; u < SEARCH_UNROLL; ++u) d[u] = e[k + u];
+#pragma unroll
+            for (int u = 0; u < SEARCH_UNROLL; ++u) beam(d[u]);
+        }
+        for (; k < n_rng; ++k) beam(e[k]);
+        const unsigned long long cost = sum_b + (unsigned long long)(n_rng - n_in) * outside_cost;
+        best = min(best, (cost << 16) | (unsigned long long)it);
+    }
+    atomicMin(&out[p], best);
 }
 
 // Sharded normaliser, merge half: every rank folds the gathered [world][3] partials in rank order
@@ -5204,6 +5299,48 @@ int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32
     if (blocks * (64 * waves) > 0xffffffffll) return SLAM2D_E_TOOLARGE;           // (a launch holds fewer than 2^32 threads)
     k_score_poses<<<(unsigned)blocks, 64 * waves, (size_t)waves * hsize * sizeof(int), (hipStream_t)stream>>>(
         *lidar, *level, p_field, N, hsize, d_pose, pose_stride, d_ranges, ranges_stride, d_out);
+    return launch_status();
+}
+
+// the checks slam2d_search_lattice and its work size share; *words: the 8-byte words of d_work (the endpoint table)
+static int check_search_lattice(const Slam2dLidar* lidar, int nx, int ny, int nth, long long* words) {
+    if (!lidar || nx < 1 || ny < 1 || nth < 1 || nth > 65536) return SLAM2D_E_BADARG;
+    if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_BADARG;
+    if ((long long)nx * ny >= (1ll << 31)) return SLAM2D_E_TOOLARGE;
+    *words = 2ll * nth * lidar->beams;                                            // (at most 2^28)
+    if (*words > (1ll << 31)) return SLAM2D_E_TOOLARGE;
+    return 0;
+}
+
+int64_t slam2d_search_lattice_work(const Slam2dLidar* lidar, int32_t nx, int32_t ny, int32_t nth) {
+    long long words = 0;
+    const int rc = check_search_lattice(lidar, nx, ny, nth, &words);
+    return rc ? rc : words;
+}
+
+int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t nx, int32_t ny, int32_t nth,
+                          double x0, double dx, double y0, double dy, double th0, double dth, const double* d_ranges,
+                          uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out, void* stream) {
+    if (!lidar || !level || !d_ranges || !d_out || !level->field || !level->frames || p_field < 0) return SLAM2D_E_BADARG;
+    if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
+    if (!(lidar->max_range > 0.0) || !(level->step > 0.0) || !(level->cost_scale > 0.0)) return SLAM2D_E_BADARG;   // (the negated forms refuse a NaN)
+    if (level->fmax <= 0 || level->fpitch < level->fmax) return SLAM2D_E_BADARG;
+    long long words = 0;
+    const int rc = check_search_lattice(lidar, nx, ny, nth, &words);
+    if (rc == SLAM2D_E_BADARG) return rc;
+    if (words > 0 && !d_work) return SLAM2D_E_BADARG;
+    if (rc) return rc;
+    if ((long long)level->fmax * level->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;
+    const int positions = nx * ny;
+    const int hc = search_chunk(positions, nth);
+    const long long blocks = ((long long)positions + 255) / 256, rows = cdiv(nth, hc);
+    // (heading chunks exist only below SEARCH_WAVES waves of positions, at most 8192 of them: the launch stays below 2^32 threads)
+    hipStream_t s = (hipStream_t)stream;
+    double2* E = reinterpret_cast<double2*>(d_work);
+    const long long first = positions > words / 2 ? positions : words / 2;
+    k_search_table<<<(unsigned)((first + 255) / 256), 256, 0, s>>>(*lidar, nth, th0, dth, d_ranges, E, (unsigned long long*)d_out, positions);
+    k_search_lattice<<<dim3((unsigned)blocks, (unsigned)rows), 256, 0, s>>>(*lidar, *level, p_field, nx, positions, nth, hc, x0, dx, y0, dy,
+                                                                           d_ranges, E, outside_cost, (unsigned long long*)d_out);
     return launch_status();
 }
 

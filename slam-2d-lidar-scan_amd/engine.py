@@ -9,6 +9,7 @@ host<->device copies and for the stream handle.
 
 ``file:line`` citations are relative to the reference repository root.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -29,6 +30,24 @@ PLAN_DTYPE = np.dtype([("lim_x0", "f8"), ("lim_y0", "f8"), ("dc", "i4"), ("dr", 
                        ("cols", "i4"), ("rows", "i4")])                  # Slam2dBeamPlan
 assert _MATCH_DTYPE.itemsize == C.sizeof(Slam2dMatch) and _FRAME_DTYPE.itemsize == C.sizeof(Slam2dFrame)
 assert PLAN_DTYPE.itemsize == C.sizeof(Slam2dBeamPlan)
+
+
+class Lattice(collections.namedtuple("Lattice", "nx ny nth x0 dx y0 dy th0 dth")):
+    """The nine numbers of slam2d_search_lattice's pose lattice (include/slam2d.h): pose (it, iy, ix) is
+    (x0 + ix * dx, y0 + iy * dy, th0 + it * dth)."""
+    __slots__ = ()
+
+    @property
+    def xs(self):
+        return self.x0 + np.arange(self.nx) * self.dx
+
+    @property
+    def ys(self):
+        return self.y0 + np.arange(self.ny) * self.dy
+
+    @property
+    def thetas(self):
+        return self.th0 + np.arange(self.nth) * self.dth
 
 
 def require_gpu(device):
@@ -1131,6 +1150,38 @@ class ParticleEngine:
         inside, in_range = r[:, 3].astype(np.int64), r[:, 4].astype(np.int64)
         return dict(score=r[:, 0].copy(), cells=r[:, 1].astype(np.int64), beam_score=r[:, 2].copy(), inside=inside, in_range=in_range,
                     outside=in_range - inside)
+
+    def search_lattice(self, level, p_field, lattice, d_ranges, outside_cost):
+        """The best heading and its cost at every position of ``lattice`` (a ``Lattice``) for the one scan ``d_ranges[0..beams)``
+        in the field that ``field_build`` left in slot ``p_field`` of ``level`` (include/slam2d.h, slam2d_search_lattice):
+        ``[ny, nx]`` int64 words on the device, cost << 16 | heading.  A pose whose in-range beam ends outside the field pays
+        ``outside_cost`` for it.  Two launches on the current stream; the scratch is kept and grown; ``search_host`` decodes."""
+        if not 0 <= p_field < level.P:
+            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        lat = Lattice(*lattice)
+        n = int(self.L.slam2d_search_lattice_work(C.byref(self.lidar_c), lat.nx, lat.ny, lat.nth))
+        if n < 0:
+            check(n, "slam2d_search_lattice_work")
+        work = getattr(self, "_search_work", None)
+        if work is None or work.numel() < n:
+            work = self._search_work = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        out = torch.empty((lat.ny, lat.nx), dtype=torch.int64, device=self.device)
+        check(self.L.slam2d_search_lattice(C.byref(self.lidar_c), C.byref(level.c), p_field, lat.nx, lat.ny, lat.nth,
+                                           float(lat.x0), float(lat.dx), float(lat.y0), float(lat.dy), float(lat.th0), float(lat.dth),
+                                           _ptr(d_ranges), int(outside_cost), _ptr(work), _ptr(out), _stream()), "slam2d_search_lattice")
+        return out
+
+    @staticmethod
+    def search_host(words, lattice, cost_scale):
+        """The image of ``search_lattice`` as a dict of host arrays: ``cost`` (uint64 [ny, nx], the best heading's cost),
+        ``heading`` (int [ny, nx], its index: the lowest among equals), ``score`` = -(cost * (1 / cost_scale)), and the lattice's
+        axes ``xs`` [nx], ``ys`` [ny], ``thetas`` [nth]."""
+        lat = Lattice(*lattice)
+        w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
+        w = np.ascontiguousarray(w).view(np.uint64).reshape(lat.ny, lat.nx)
+        cost = w >> np.uint64(16)
+        return dict(cost=cost, heading=(w & np.uint64(0xffff)).astype(np.int64), score=-(cost.astype(np.float64) * (1.0 / cost_scale)),
+                    xs=lat.xs, ys=lat.ys, thetas=lat.thetas)
 
     def grid_update(self, d_pose, stride, d_ranges, d_beam_shift=None):
         self._before_update()

@@ -6,6 +6,7 @@ sweep on the GPU for one particle.
 before its next statement).  The batched, all-particles path is
 ``filter.ParticleFilter``.
 """
+import collections
 import copy
 import math
 
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import MATCH_DOUBLES, _MATCH_DTYPE, ParticleEngine, SearchLevel, pinned_stream
+from .engine import MATCH_DOUBLES, _MATCH_DTYPE, Lattice, ParticleEngine, SearchLevel, encode_cost, pinned_stream
 
 _level_cache = {}
 
@@ -142,6 +143,50 @@ def covering_radius(half, max_range, step, unit):
             return ctor
     raise ValueError(f"window: a half-edge of {half:g} m at a step of {step:g} m needs "
                      f"{field_build_limits(1.1 * max_range + exact, step, unit)}; score a smaller window or use the coarse level")
+
+
+# ---- the lattice of ScanMatcher.searchPoses and the peaks of its image, on the host ----
+Peak = collections.namedtuple("Peak", "x y theta score cost")
+
+
+def window_lattice(window, step, headings):
+    """The ``Lattice`` of ``searchPoses``: positions every ``step`` metres over the square ``window = (cx, cy, half)``, the centre
+    among them, and ``headings`` headings from -pi in steps of 2 pi / headings."""
+    cx, cy, half = covering_window(None, window)
+    step, headings = float(step), int(headings)
+    if not (math.isfinite(step) and step > 0):
+        raise ValueError(f"step wants a positive number, not {step!r}")
+    if not 1 <= headings <= 65536:
+        raise ValueError(f"headings wants 1 .. 65536, not {headings!r}")
+    n = int(math.floor(half / step + 1e-9))
+    return Lattice(2 * n + 1, 2 * n + 1, headings, cx - n * step, step, cy - n * step, step, -math.pi, 2 * math.pi / headings)
+
+
+def lattice_peaks(cost, heading, top, separation_cells):
+    """The ``top`` lowest-cost positions of a ``[ny, nx]`` cost image, well separated: taken greedily from the lowest cost up, a
+    position only if no position already taken lies within ``separation_cells`` of it in Chebyshev distance (0: only the
+    position itself); equal costs in the order of the flat index iy * nx + ix.  Returns int64 ``[k, 3]`` rows (iy, ix,
+    heading[iy, ix]), k <= top."""
+    cost = np.asarray(cost)
+    heading = np.asarray(heading)
+    if cost.ndim != 2 or heading.shape != cost.shape:
+        raise ValueError(f"cost {cost.shape} and heading {heading.shape}: want two [ny, nx] images")
+    sep = int(separation_cells)
+    if sep < 0:
+        raise ValueError("separation_cells wants >= 0")
+    ny, nx = cost.shape
+    free = np.ones(cost.shape, dtype=bool)
+    order = np.argsort(cost, axis=None, kind="stable")                          # (stable: equal costs keep the flat order)
+    peaks = []
+    for flat in order:
+        if len(peaks) >= top:
+            break
+        iy, ix = divmod(int(flat), nx)
+        if not free[iy, ix]:
+            continue
+        peaks.append((iy, ix, int(heading[iy, ix])))
+        free[max(0, iy - sep):iy + sep + 1, max(0, ix - sep):ix + sep + 1] = False
+    return np.array(peaks, dtype=np.int64).reshape(-1, 3)
 
 
 class ScanMatcher:
@@ -330,6 +375,47 @@ class ScanMatcher:
             self.last_flags = bits
             self.last_cover = dict(level=lv, window=(cx, cy, half))
             return eng.score_host(host[:-1])
+
+    def searchPoses(self, reading_or_ranges, window, step=None, headings=120, level="fine", top=5, separation=None, outside_cost=None):
+        """Where in ``window = (cx, cy, half)`` could this scan have been taken (include/slam2d.h, slam2d_search_lattice): the
+        best heading and its cost at every position of a lattice -- ``step`` metres apart (default: the level's step),
+        ``headings`` headings over the full turn -- searched on the device: nothing but the scan is uploaded, one 8-byte word
+        per POSITION comes back.  The field is the covering level of ``scorePoses`` for this window, built in full.  The cost
+        of a pose is ``beam_score`` of ``scorePoses`` in the field's integers plus ``outside_cost`` for every in-range beam
+        that ends outside the field (default: the level's free-space value as the field encodes it).  Returns the arrays of
+        ``ParticleEngine.search_host`` -- ``cost``, ``heading``, ``score`` [ny, nx], ``xs``, ``ys``, ``thetas`` -- and
+        ``peaks``: up to ``top`` ``Peak(x, y, theta, score, cost)``, lowest cost first, no two within ``separation`` metres
+        (default: ten lattice steps) of each other on either axis (``lattice_peaks``).  ``self.last_cover`` keeps the level,
+        its window and the ``Lattice``."""
+        rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
+        rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
+        if rng.shape != (self.og.numSamplesPerRev,):
+            raise ValueError(f"ranges of shape {rng.shape}: want ({self.og.numSamplesPerRev},)")
+        cx, cy, half = covering_window(None, window)
+        lv = self.covering_level(level, half)
+        lat = window_lattice((cx, cy, half), lv.step if step is None else step, headings)
+        sep = 10 if separation is None else int(round(float(separation) / lat.dx))
+        if outside_cost is None:
+            outside_cost = int(encode_cost(lv.floor_value, lv.cost_scale))
+        with _Exclusive(lv), pinned_stream():
+            og = self.og
+            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = og.engine()
+            eng.field_build(lv, eng.to_device([[cx, cy]]), 2)
+            words = eng.search_lattice(lv, 0, lat, eng.to_device(rng), outside_cost)
+            # one download: the image and the build's fault word
+            host = torch.cat([words.reshape(-1), eng.flags[:1].to(torch.int64)]).cpu().numpy()
+            bits = int(host[-1]) & 0xffffffff
+            if bits:
+                eng.flags.zero_()
+                if bits & _lib.FATAL_FLAGS:
+                    raise _lib.Slam2dError(f"searchPoses: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
+            self.last_flags = bits
+            self.last_cover = dict(level=lv, window=(cx, cy, half), lattice=lat)
+            res = eng.search_host(host[:-1], lat, lv.cost_scale)
+        res["peaks"] = [Peak(float(res["xs"][ix]), float(res["ys"][iy]), float(res["thetas"][it]), float(res["score"][iy, ix]),
+                             int(res["cost"][iy, ix])) for iy, ix, it in lattice_peaks(res["cost"], res["heading"], top, sep)]
+        return res
 
     def searchToMatch(self, probSP, estimatedX, estimatedY, estimatedTheta, rMeasure, xRangeList, yRangeList,
                       searchRadius, searchHalfRad, unitLength, estMovingDist, estMovingTheta, fineSearch=False,
