@@ -233,6 +233,187 @@ __device__ __forceinline__ int trunc_div_fast(const double v, const double step,
 }
 
 // ------------------------------------------------------------------------------------
+// The exact-score core: what the sweep, tile, moments and select kernels (K1c-K1e, k_moments) share.  The project's
+// invariants live here once -- the cube's shape, exact 64-bit integer cost sums, the one fp64 score expression, np.argmax's
+// NaN-first order, the Slam2dMatch record.
+// ------------------------------------------------------------------------------------
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// The pose cube of a level: nx x nx poses per angle; a plane is cut into nslot "slots" of 4 consecutive dx of one dy
+// (nq per row, the last one partly padding) for the sweep and into nbt x nbt tiles of 4 x 4 poses for branch and bound,
+// whose tile rows are padded to nbq4 (a multiple of 4) entries.
+struct Cube { int nx, npose, nq, nslot, nbt, nbq4; };
+__host__ __device__ __forceinline__ Cube cube_of(const Slam2dLevel& lv) {
+    const int nx = 2 * lv.ncell + 1, nq = (nx + 3) >> 2;
+    return Cube{nx, nx * nx, nq, nx * nq, nq, ((nq + 3) >> 2) << 2};
+}
+// Slot u of a plane: its row, first column, byte offset into a field of pitch fpitch, first pose index and valid poses
+// (0 for u >= nslot, whose other members are slot 0's: safe to address with)
+struct Slot { int iy, dx, off, q0, nv; };
+__device__ __forceinline__ Slot slot_of(const Cube& c, const int fpitch, const int u) {
+    const int uu = u < c.nslot ? u : 0;
+    const int iy = uu / c.nq, dx = (uu - iy * c.nq) * 4;
+    return Slot{iy, dx, (iy * fpitch + dx) * 4, iy * c.nx + dx, u < c.nslot ? min(4, c.nx - dx) : 0};
+}
+
+// Four exact 64-bit integer sums as 32-bit halves (the sum does not depend on the order: argmax ties in the reference stay ties).
+// The halves are two 4-vectors, not eight scalars, on purpose: the compiler then carries them through a gather loop as two
+// values, and an unrolled loop (k_moments) keeps its remainder iterations ahead of the main loop -- with scalars it moves them
+// behind it and needs 83 VGPRs instead of 77, 5 waves per SIMD instead of 6, and 8 % more time for the call.
+struct Acc4 {
+    u32x4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+    __device__ __forceinline__ void add(const u32x4 v) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned s = lo[e] + v[e];
+            hi[e] += s < v[e] ? 1u : 0u;
+            lo[e] = s;
+        }
+    }
+    __device__ __forceinline__ unsigned long long get(const int e) const { return ((unsigned long long)hi[e] << 32) | lo[e]; }
+    __device__ __forceinline__ void add_u64(const int e, const unsigned long long t) {
+        const unsigned long long s = get(e) + t;
+        hi[e] = (unsigned)(s >> 32); lo[e] = (unsigned)s;
+    }
+};
+
+// Buffer addressing (SRSRC): address = base + per-lane VGPR byte offset + wave-uniform SGPR byte offset -- no vector
+// address arithmetic in a gather loop, and offsets beyond `bytes` read 0 (stores: are dropped) instead of faulting.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const void* base, const size_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t field_rsrc(const Slam2dLevel& lv, const int p) {
+    const size_t image = (size_t)lv.fmax * lv.fpitch;
+    return image_rsrc(lv.field + (size_t)p * image, image * sizeof(uint32_t));
+}
+
+// Blocks of one particle are pinned to one XCD (block b runs on XCD b % 8), so that the particle's field stays in that
+// XCD's 4 MiB L2: block b -> particle p (may be >= P: the grid is rounded up to 8 particles) and its w-th of `per` blocks.
+__device__ __forceinline__ void xcd_particle(const int b, const int per, int* p, int* w) {
+    const int xcd = b & 7, slot = b >> 3;
+    *p = (slot / per) * 8 + xcd;
+    *w = slot % per;
+}
+
+// The score of a pose (Utils/ScanMatcher_OGBased.py:131): its exact cost sum, rv and thetaWeight, in this association
+__device__ __forceinline__ double pose_score(const unsigned long long acc, const double inv, const double prv, const double ptw) {
+    return (-((double)acc * inv) + prv) + ptw;
+}
+// both prior planes of a slot's poses in one batch of loads (one round trip, not eight); pr: the particle's planes
+__device__ __forceinline__ void slot_priors(const double* __restrict__ pr, const Cube& c, const int q0, double (&prv)[4], double (&ptw)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int q = min(q0 + e, c.npose - 1);
+        prv[e] = pr[q];
+        ptw[e] = pr[c.npose + q];
+    }
+}
+
+struct Best { double v; int i; int nan; };
+__device__ __forceinline__ bool better(const Best& a, const Best& b) {
+    // np.argmax semantics: first NaN wins; otherwise the largest value, lowest index on ties
+    if (a.nan != b.nan) return a.nan > b.nan;
+    if (a.nan) return a.i < b.i;
+    return a.v > b.v || (a.v == b.v && a.i < b.i);
+}
+__device__ __forceinline__ Best wave_best(Best me) {
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        Best ot{__shfl_xor(me.v, o), __shfl_xor(me.i, o), __shfl_xor(me.nan, o)};
+        if (better(ot, me)) me = ot;
+    }
+    return me;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+    // fixed order: DPP butterflies inside the four rows of 16 lanes, then (row 0 + row 1) + (row 2 + row 3) -- deterministic,
+    // and no LDS-crossbar round trips (all 64 lanes must be active)
+    v += dpp_f64<0xB1>(v); v += dpp_f64<0x4E>(v); v += dpp_f64<0x141>(v); v += dpp_f64<0x140>(v);
+    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+// wave_best without the 6-step butterfly of three values (24 ds_bpermute) in the common case: DPP maximum, one ballot; only
+// when several lanes tie for the maximum, or a NaN is present, the full comparison decides.  Same result as wave_best.  All 64
+// lanes must be active.
+__device__ __forceinline__ Best wave_best_fast(const Best me) {
+    if (__ballot(me.nan != 0)) return wave_best(me);
+    const double m = wave64_max(me.i != INT_MAX ? me.v : -INFINITY);
+    const unsigned long long eq = __ballot(me.v == m && me.i != INT_MAX);
+    if (!eq) return Best{-INFINITY, INT_MAX, 0};
+    if ((eq & (eq - 1)) == 0ull) return Best{m, __builtin_amdgcn_readlane(me.i, __ffsll((long long)eq) - 1), 0};
+    return wave_best(me);
+}
+// wave_best for candidates whose index ascends with the lane (so "lowest index" = lowest lane): ballots and readlanes
+// instead of a 6-step butterfly of three values.  np.argmax semantics as `better`.  All 64 lanes must be active.
+__device__ __forceinline__ Best wave_best_ordered(const Best me) {
+    const unsigned long long nanm = __ballot(me.nan != 0);
+    if (nanm) {
+        const int l = __ffsll((long long)nanm) - 1;
+        return Best{NAN, __builtin_amdgcn_readlane(me.i, l), 1};
+    }
+    const double m = wave64_max(me.v);
+    const unsigned long long eq = __ballot(me.v == m && me.i != INT_MAX);
+    if (!eq) return Best{-INFINITY, INT_MAX, 0};
+    return Best{m, __builtin_amdgcn_readlane(me.i, __ffsll((long long)eq) - 1), 0};
+}
+
+// The Slam2dPartial of a plane, or of one 64-slot chunk of it, by one wave: lane = one slot with the scores sc[0 .. nv) (the
+// lane's best of them in `me`; flat indices ascend with the lane): max / argmax in np.argmax order, sum exp(score - max).
+__device__ __forceinline__ Slam2dPartial plane_partial(Best me, const double (&sc)[4], const int nv) {
+    me = wave_best_ordered(me);
+    double ex = 0.0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (e < nv) ex += exp(sc[e] - me.v);
+    ex = wave_sum(ex);
+    Slam2dPartial pt;
+    pt.max = me.v; pt.sumexp = ex; pt.argmax = me.i; pt.has_nan = me.nan;
+    return pt;
+}
+
+// A particle's nW partials to the cube's maximum and total = sum_w sumexp_w * exp(max_w - M), by one wave: `best` in
+// np.argmax order; every lane owns a contiguous run of partials, whose share of the total is `mine` and whose inclusive
+// scan over the lanes is `incl` (the soft-max draw walks it).  part(w): the w-th partial, however it has to be loaded.
+struct PartialsTotal { Best best; double mine, incl, total; };
+template <typename Load>
+__device__ __forceinline__ PartialsTotal partials_total(const int nW, const Load part) {
+    const int lane = threadIdx.x & 63;
+    Best me{-INFINITY, INT_MAX, 0};
+    for (int w = lane; w < nW; w += WAVE) {
+        const Slam2dPartial pt = part(w);
+        Best cand{pt.max, pt.argmax, pt.has_nan};
+        if (better(cand, me)) me = cand;
+    }
+    me = wave_best_fast(me);
+    const double M = me.v;
+    const int per = (nW + WAVE - 1) / WAVE;
+    const int w0 = lane * per, w1 = min(nW, w0 + per);
+    double mine = 0.0;
+    for (int w = w0; w < w1; ++w) { const Slam2dPartial pt = part(w); mine += pt.sumexp * exp(pt.max - M); }
+    const double incl = wave_scan_incl_f64(mine);     // inclusive scan over lanes
+    return PartialsTotal{me, mine, incl, readlane_f64(incl, WAVE - 1)};
+}
+
+// The match record of particle p (one lane): pose of flat cube index `pick` (theta_of_pick: its angle offset) around the
+// estimate (ex, ey, eth), confidence from the maximum M and the total; then the level's arrival count.
+__device__ __forceinline__ void store_match(const Slam2dLevel& lv, const int p, const double ex, const double ey, const double eth,
+                                            const double theta_of_pick, const int pick, const int argmax, const double M,
+                                            const double total, Slam2dMatch* out) {
+    const Cube c = cube_of(lv);
+    Slam2dMatch m;
+    const int it = pick / c.npose, rem = pick - it * c.npose;
+    const int iy = rem / c.nx, ix = rem - iy * c.nx;
+    m.x = ex + (double)(ix - lv.ncell) * lv.step;                               // :142-143
+    m.y = ey + (double)(iy - lv.ncell) * lv.step;
+    m.theta = eth + theta_of_pick;
+    m.confidence = exp(M) * total;                                              // :141
+    m.log_confidence = M + log(total);
+    m.best_score = M;
+    m.pick = pick;
+    m.argmax = argmax;
+    out[p] = m;
+    if (lv.arrive) __hip_atomic_fetch_add(lv.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (Slam2dScan.match_seq)
+}
+
+// ------------------------------------------------------------------------------------
 // K2a  frame geometry                      (Utils/ScanMatcher_OGBased.py:21-28)
 // ------------------------------------------------------------------------------------
 // Frame geometry of one particle (every thread of k_frame_axis evaluates it redundantly: a few fp64
@@ -352,10 +533,8 @@ __global__ __launch_bounds__(256) void k_occ_scatter(Slam2dLevel lv, const Slam2
     if (col_base < fr.mx0) edge &= ~0u << (fr.mx0 - col_base);                    // window edges
     if (col_base + 32 > fr.mx1) edge &= ~0u >> (col_base + 32 - fr.mx1);
     const int fpad = flag_pitch(lv);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.occ + (size_t)p * lv.fmax * lv.fpitch), (short)0, (int)((size_t)lv.fmax * lv.fpitch), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.tilemask + (size_t)p * flag_bytes(lv)), (short)0, (int)flag_bytes(lv), 0x00020000);   // flags of 8 x 8-cell blocks, [2 tmax][flag_pitch]
+    const __amdgpu_buffer_rsrc_t ro = image_rsrc(lv.occ + (size_t)p * lv.fmax * lv.fpitch, (size_t)lv.fmax * lv.fpitch);
+    const __amdgpu_buffer_rsrc_t rt = image_rsrc(lv.tilemask + (size_t)p * flag_bytes(lv), flag_bytes(lv));   // flags of 8 x 8-cell blocks, [2 tmax][flag_pitch]
     const uint8_t stamp = occ_stamp(lv);
     const int half = lane >> 5, bit = lane & 31;
     const int lbase = (w0 << 5) + bit - fr.mx0;            // the lane's column of word w0, relative to the window
@@ -447,10 +626,8 @@ __device__ __forceinline__ void scatter_role(const Slam2dLidar& lid, const Slam2
     // (buffer stores: the row's byte offset rides in the scalar offset, the column in the lane's -- no 64-bit address
     // arithmetic per set bit; the kernel's launch is bound by its vector instructions)
     const int fpad = flag_pitch(lv);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.occ + (size_t)p * lv.fmax * lv.fpitch), (short)0, (int)((size_t)lv.fmax * lv.fpitch), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.tilemask + (size_t)p * flag_bytes(lv)), (short)0, (int)flag_bytes(lv), 0x00020000);   // flags of 8 x 8-cell blocks, [2 tmax][flag_pitch]
+    const __amdgpu_buffer_rsrc_t ro = image_rsrc(lv.occ + (size_t)p * lv.fmax * lv.fpitch, (size_t)lv.fmax * lv.fpitch);
+    const __amdgpu_buffer_rsrc_t rt = image_rsrc(lv.tilemask + (size_t)p * flag_bytes(lv), flag_bytes(lv));   // flags of 8 x 8-cell blocks, [2 tmax][flag_pitch]
     const uint8_t stamp = occ_stamp(lv);
     const int half = lane >> 5, bit = lane & 31;
     const int lbase = (w0 << 5) + bit - fr.mx0;            // the lane's column of word w0, relative to the window
@@ -1180,7 +1357,8 @@ __device__ __forceinline__ void write_priors(const Slam2dLevel& lv, const int p,
                                              const double* __restrict__ psi_cs, const int prune) {
     __shared__ int ring_cnt[4];
     __shared__ int ring_base;
-    const int nx = 2 * lv.ncell + 1, np_ = nx * nx;
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx, np_ = cube.npose;
     double* out = lv.prior + (size_t)p * 2 * np_;
     const double cpsi = psi_cs ? psi_cs[2 * p] : NAN;
     const double spsi = psi_cs ? psi_cs[2 * p + 1] : NAN;
@@ -1211,7 +1389,7 @@ __device__ __forceinline__ void write_priors(const Slam2dLevel& lv, const int p,
         // largest rv + thetaWeight of every 4x4 pose tile (+inf when one of them is NaN: np.argmax returns the first
         // NaN, so such a tile is always scored); padding tiles get -inf
         __syncthreads();                                   // the planes above were written by this block
-        const int nbt = (nx + 3) >> 2, nbq4 = ((nbt + 3) >> 2) << 2;
+        const int nbt = cube.nbt, nbq4 = cube.nbq4;
         double* pm = lv.tile_pmax + (size_t)p * nbt * nbq4;
         for (int t = threadIdx.x; t < nbt * nbq4; t += blockDim.x) {
             const int by = t / nbq4, bx = t - by * nbq4;
@@ -1231,7 +1409,7 @@ __device__ __forceinline__ void write_priors(const Slam2dLevel& lv, const int p,
     if (threadIdx.x == 0) lv.prune_state[p] = need_full;
     if (p != 0) return;
     // the ring as an ascending list of sweep slots (4 consecutive dx of one dy), shared by all particles
-    const int nq = (nx + 3) >> 2, nslot = nx * nq;
+    const int nslot = cube.nslot;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) ring_base = 0;
     __syncthreads();
@@ -1239,7 +1417,7 @@ __device__ __forceinline__ void write_priors(const Slam2dLevel& lv, const int p,
         const int u = s0 + threadIdx.x;
         bool in = false;
         if (u < nslot) {
-            const int iy = u / nq, dx = (u - iy * nq) * 4;
+            const int iy = u / cube.nq, dx = (u - iy * cube.nq) * 4;
             for (int e = 0; e < 4 && dx + e < nx; ++e) in = in || prune_ring(lv, dx + e - lv.ncell, iy - lv.ncell, est_dist);
         }
         const unsigned long long mask = __ballot(in);
@@ -1545,59 +1723,10 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
 //      flattened (dy, dx/4) plane, so every gather of a wave is a few contiguous row segments of the
 //      fixed-point uint32 field; its 4 waves split the unique-cell list.  The list is wave-uniform: it is
 //      read with scalar loads and the field through a buffer resource as (per-lane constant VGPR offset) +
-//      (scalar cell offset), 16 bytes per lane.  Costs are summed exactly in 64-bit integers (as lo / hi
-//      halves), so the sum does not depend on the order and argmax ties in the reference stay ties here.
-//      Blocks of one particle are pinned to one XCD (block b runs on XCD b % 8) so that
-//      particle's field stays in that XCD's 4 MiB L2 while its cube is swept.
+//      (scalar cell offset), 16 bytes per lane.  The cube's shape and slots, the exact sums (Acc4), the score
+//      expression, the plane's partial, the XCD pinning and the match record come from the exact-score core above
+//      (cube_of .. store_match), which K1d, K1e and k_moments read as well.
 // ------------------------------------------------------------------------------------
-struct Best { double v; int i; int nan; };
-__device__ __forceinline__ bool better(const Best& a, const Best& b) {
-    // np.argmax semantics: first NaN wins; otherwise the largest value, lowest index on ties
-    if (a.nan != b.nan) return a.nan > b.nan;
-    if (a.nan) return a.i < b.i;
-    return a.v > b.v || (a.v == b.v && a.i < b.i);
-}
-__device__ __forceinline__ Best wave_best(Best me) {
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        Best ot{__shfl_xor(me.v, o), __shfl_xor(me.i, o), __shfl_xor(me.nan, o)};
-        if (better(ot, me)) me = ot;
-    }
-    return me;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    // fixed order: DPP butterflies inside the four rows of 16 lanes, then (row 0 + row 1) + (row 2 + row 3) -- deterministic,
-    // and no LDS-crossbar round trips (all 64 lanes must be active)
-    v += dpp_f64<0xB1>(v); v += dpp_f64<0x4E>(v); v += dpp_f64<0x141>(v); v += dpp_f64<0x140>(v);
-    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-// wave_best without the 6-step butterfly of three values (24 ds_bpermute) in the common case: DPP maximum, one ballot; only
-// when several lanes tie for the maximum, or a NaN is present, the full comparison decides.  Same result as wave_best.  All 64
-// lanes must be active.
-__device__ __forceinline__ Best wave_best_fast(const Best me) {
-    if (__ballot(me.nan != 0)) return wave_best(me);
-    const double m = wave64_max(me.i != INT_MAX ? me.v : -INFINITY);
-    const unsigned long long eq = __ballot(me.v == m && me.i != INT_MAX);
-    if (!eq) return Best{-INFINITY, INT_MAX, 0};
-    if ((eq & (eq - 1)) == 0ull) return Best{m, __builtin_amdgcn_readlane(me.i, __ffsll((long long)eq) - 1), 0};
-    return wave_best(me);
-}
-// wave_best for candidates whose index ascends with the lane (so "lowest index" = lowest lane): ballots and readlanes
-// instead of a 6-step butterfly of three values.  np.argmax semantics as `better`.  All 64 lanes must be active.
-__device__ __forceinline__ Best wave_best_ordered(const Best me) {
-    const unsigned long long nanm = __ballot(me.nan != 0);
-    if (nanm) {
-        const int l = __ffsll((long long)nanm) - 1;
-        return Best{NAN, __builtin_amdgcn_readlane(me.i, l), 1};
-    }
-    const double m = wave64_max(me.v);
-    const unsigned long long eq = __ballot(me.v == m && me.i != INT_MAX);
-    if (!eq) return Best{-INFINITY, INT_MAX, 0};
-    return Best{m, __builtin_amdgcn_readlane(me.i, __ffsll((long long)eq) - 1), 0};
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 // A "slot" is 4 consecutive dx of one dy row (the last slot of a row is partly padding); one lane
 // scores one slot, i.e. each gather is one 16-byte buffer load -- a quarter of the vector-memory
 // instructions of a dword-per-lane sweep for the same bytes.
@@ -1614,9 +1743,9 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define SWEEP_DEPTH 8
 #endif
 #define SWEEP_DEEP_MAX_BLOCKS 64     // blocks per particle up to which the launch is about one round of blocks (latency-bound): the deep loop
-// arg-max, confidence and matched pose of particle p from the sweep's partials (k_select<0> without the soft-max draw: the very
-// expressions and summation order), by ONE wave -- the sweep's last-arriving block of the particle (k_sweep, sel_out).  The
-// partials were published with write-through stores by other blocks: they are read past this CU's L1.
+// arg-max, confidence and matched pose of particle p from the sweep's partials (k_select<0> without the soft-max draw), by ONE
+// wave -- the sweep's last-arriving block of the particle (k_sweep, sel_out).  The partials were published with write-through
+// stores by other blocks: they are read past this CU's L1.
 __device__ __forceinline__ Slam2dPartial load_partial_through(const Slam2dPartial* src) {
     const unsigned long long* u = reinterpret_cast<const unsigned long long*>(src);
     const unsigned long long a = __hip_atomic_load(u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1629,39 +1758,11 @@ __device__ __forceinline__ Slam2dPartial load_partial_through(const Slam2dPartia
 }
 __device__ __forceinline__ void select_argmax_from_partials(const Slam2dLevel& lv, const int p, const int nW, const double* __restrict__ est,
                                                             const int estride, Slam2dMatch* out) {
-    const int lane = threadIdx.x & 63;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
     const Slam2dPartial* pt0 = lv.partials + (size_t)p * lv.npartial;
-    Best me{-INFINITY, INT_MAX, 0};
-    for (int w = lane; w < nW; w += WAVE) {
-        const Slam2dPartial pt = load_partial_through(pt0 + w);
-        Best cand{pt.max, pt.argmax, pt.has_nan};
-        if (better(cand, me)) me = cand;
-    }
-    me = wave_best_fast(me);
-    const double M = me.v;
-    const int per = (nW + WAVE - 1) / WAVE;
-    const int w0 = lane * per, w1 = min(nW, w0 + per);
-    double mine = 0.0;
-    for (int w = w0; w < w1; ++w) { const Slam2dPartial pt = load_partial_through(pt0 + w); mine += pt.sumexp * exp(pt.max - M); }
-    const double incl = wave_scan_incl_f64(mine);
-    const double total = readlane_f64(incl, WAVE - 1);
-    if (lane == 0) {
-        const int pick = me.i;
-        Slam2dMatch m;
-        const int it = pick / npose, rem = pick - it * npose;
-        const int iy = rem / nx, ix = rem - iy * nx;
-        const double ex = est[(size_t)p * estride], ey = est[(size_t)p * estride + 1], eth = est[(size_t)p * estride + 2];
-        m.x = ex + (double)(ix - lv.ncell) * lv.step;                               // :142-143
-        m.y = ey + (double)(iy - lv.ncell) * lv.step;
-        m.theta = eth + lv.thetas[it];
-        m.confidence = exp(M) * total;                                              // :141
-        m.log_confidence = M + log(total);
-        m.best_score = M;
-        m.pick = pick;
-        m.argmax = me.i;
-        out[p] = m;
-        if (lv.arrive) __hip_atomic_fetch_add(lv.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (Slam2dScan.match_seq)
+    const PartialsTotal t = partials_total(nW, [&](const int w) { return load_partial_through(pt0 + w); });
+    if ((threadIdx.x & 63) == 0) {
+        const double* e = est + (size_t)p * estride;
+        store_match(lv, p, e[0], e[1], e[2], lv.thetas[t.best.i / cube_of(lv).npose], t.best.i, t.best.i, t.best.v, t.total, out);
     }
 }
 
@@ -1677,9 +1778,8 @@ __global__ __launch_bounds__(256, (mode == 0 && !SKIP) ? 8 : 1) void k_sweep(Sla
     // (integer sums: exact).  ~29 % of the loads at config 2.
     __shared__ unsigned long long part_s[3][WAVE * 4];
     __shared__ unsigned long long free_s[64];
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;
-    const int p = (slot / bpp) * 8 + xcd;
+    int p, w;
+    xcd_particle(blockIdx.x, bpp, &p, &w);
     if (p >= P) return;
     if (mode == 2 && lv.prune_state[p] == 0) return;
     if (mode == 1 && lv.prune_state[p] != 0) return;
@@ -1691,33 +1791,25 @@ __global__ __launch_bounds__(256, (mode == 0 && !SKIP) ? 8 : 1) void k_sweep(Sla
     const int lane = threadIdx.x & 63;
     // modes 0 / 1: one block per (theta, chunk).  mode 2: one block per (theta, SWEEP_REST_CHUNKS chunks), so that
     // the launch -- empty for every settled particle -- is a quarter of the blocks
-    const int w = slot % bpp;
     constexpr int CPB = mode == 2 ? SWEEP_REST_CHUNKS : (mode == 0 ? SWEEP_MAIN_CHUNKS : 1);      // chunks per block
     const int groups = (chunks + CPB - 1) / CPB;
     const int it = w / groups;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
-    const int nq = (nx + 3) >> 2, nslot = nx * nq;
-    const uint32_t* __restrict__ F = lv.field + (size_t)p * lv.fmax * lv.fpitch;
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx, npose = cube.npose, nq = cube.nq, nslot = cube.nslot;
     const int* __restrict__ cl = lv.cells + ((size_t)p * lv.ntheta + it) * lv.kmax;
     const int K = lv.kcount[p * lv.ntheta + it];
     const int nring = mode == 1 ? lv.ring[0] : 0;
     if (mode == 1 && (w - it * groups) * WAVE >= nring) return;     // also nring = -1: the ring did not fit
-    // Buffer addressing (SRSRC): address = field base + per-lane VGPR byte offset (constant
-    // over k) + wave-uniform SGPR byte offset (the cell) -- no vector address arithmetic in
-    // the loop, and out-of-range offsets read 0 instead of faulting.
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)F, (short)0, (int)((size_t)lv.fmax * lv.fpitch * sizeof(uint32_t)), 0x00020000);
+    // address = field base + per-lane byte offset (constant over k) + wave-uniform byte offset (the cell)
+    const __amdgpu_buffer_rsrc_t rsrc = field_rsrc(lv, p);
     const int dbg0 = lv.fine ? 44 : 32;
     auto sweep_chunk = [&](const int ch) {
     DBG_CLOCK(dbg0, p == 0 && it == 0 && ch == 0);
     int u = ch * WAVE + lane;             // the lane's slot
     if (mode == 1) u = u < nring ? lv.ring[1 + u] : nslot;
-    const int uu = u < nslot ? u : 0;
-    const int iy = uu / nq, dx = (uu - iy * nq) * 4;
-    const int off = (iy * lv.fpitch + dx) * 4;            // byte offset, first pose index, valid poses (0..4) of the slot
-    const int q0 = iy * nx + dx;
-    const int nv = u < nslot ? min(4, nx - dx) : 0;
-    unsigned lo[4] = {0u, 0u, 0u, 0u}, hi[4] = {0u, 0u, 0u, 0u};      // exact 64-bit integer sums as 32-bit halves
+    const Slot sl = slot_of(cube, lv.fpitch, u);
+    const int off = sl.off, q0 = sl.q0, nv = sl.nv;
+    Acc4 acc;
     unsigned nfree = 0u;
     if constexpr (SKIP) {
         // This wave's cells (k = wave, wave + 4, ...) 64 at a time, one per lane; the loop then pops cells off a
@@ -1759,13 +1851,7 @@ __global__ __launch_bounds__(256, (mode == 0 && !SKIP) ? 8 : 1) void k_sweep(Sla
 #pragma unroll
                 for (int i = 0; i < SWEEP_DEPTH; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, c[i], 0);
 #pragma unroll
-                for (int i = 0; i < SWEEP_DEPTH; ++i)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const unsigned s2 = lo[e] + v[i][e];
-                        hi[e] += s2 < v[i][e] ? 1u : 0u;
-                        lo[e] = s2;
-                    }
+                for (int i = 0; i < SWEEP_DEPTH; ++i) acc.add(v[i]);
             }
         }
     } else if (deep) {
@@ -1785,41 +1871,26 @@ __global__ __launch_bounds__(256, (mode == 0 && !SKIP) ? 8 : 1) void k_sweep(Sla
 #pragma unroll
                 for (int i = 0; i < SWEEP_DEPTH; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, j0 + i < n ? c[i] : 0x7ffffff0, 0);
 #pragma unroll
-                for (int i = 0; i < SWEEP_DEPTH; ++i)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const unsigned s2 = lo[e] + v[i][e];
-                        hi[e] += s2 < v[i][e] ? 1u : 0u;
-                        lo[e] = s2;
-                    }
+                for (int i = 0; i < SWEEP_DEPTH; ++i) acc.add(v[i]);
             }
         }
     } else {
 #pragma unroll 2
     for (int k = wave; k < K; k += 4) {
         const int cell = cl[k] * 4;
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, cell, 0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const unsigned s = lo[e] + v[e];
-            hi[e] += s < v[e] ? 1u : 0u;
-            lo[e] = s;
-        }
+        acc.add(__builtin_amdgcn_raw_buffer_load_b128(rsrc, off, cell, 0));
     }
     }
     if constexpr (SKIP) {                                  // the skipped cells: each adds the free-space cost
         const double fv = lv.floor_value;
         const unsigned long long add = (unsigned long long)nfree * (fv > 0.5 * fv ? 0u : (uint32_t)rint(-fv * lv.cost_scale));
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const unsigned long long t = (((unsigned long long)hi[e] << 32) | lo[e]) + add;
-            hi[e] = (unsigned)(t >> 32); lo[e] = (unsigned)t;
-        }
+        for (int e = 0; e < 4; ++e) acc.add_u64(e, add);
     }
     DBG_CLOCK(dbg0 + 1, p == 0 && it == 0 && ch == 0);
     if (wave > 0) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) part_s[wave - 1][e * WAVE + lane] = ((unsigned long long)hi[e] << 32) | lo[e];
+        for (int e = 0; e < 4; ++e) part_s[wave - 1][e * WAVE + lane] = acc.get(e);
     }
     __syncthreads();
     DBG_CLOCK(dbg0 + 2, p == 0 && it == 0 && ch == 0);
@@ -1828,44 +1899,27 @@ __global__ __launch_bounds__(256, (mode == 0 && !SKIP) ? 8 : 1) void k_sweep(Sla
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int ix = e * WAVE + lane;
-        const unsigned long long tot = (((unsigned long long)hi[e] << 32) | lo[e]) + part_s[0][ix] + part_s[1][ix] + part_s[2][ix];
-        hi[e] = (unsigned)(tot >> 32); lo[e] = (unsigned)tot;
+        acc.add_u64(e, part_s[0][ix] + part_s[1][ix] + part_s[2][ix]);
     }
-    const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
     double* __restrict__ out = lv.cube + ((size_t)p * lv.ntheta + it) * npose;
     const double inv = 1.0 / lv.cost_scale;
     double sc[4], prv[4], ptw[4];
     Best me{-INFINITY, INT_MAX, 0};
-    // both prior planes of the lane's poses in one batch of loads (one round trip, not eight)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int q = min(q0 + e, npose - 1);
-        prv[e] = pr[q];
-        ptw[e] = pr[npose + q];
-    }
+    slot_priors(lv.prior + (size_t)p * 2 * npose, cube, q0, prv, ptw);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         sc[e] = -INFINITY;
         if (e < nv) {
             const int q = q0 + e;
-            const unsigned long long acc = ((unsigned long long)hi[e] << 32) | lo[e];
-            const double sum = -((double)acc * inv);                               // sum of probSP values
-            sc[e] = (sum + prv[e]) + ptw[e];                                       // :131
+            sc[e] = pose_score(acc.get(e), inv, prv[e], ptw[e]);
             out[q] = sc[e];
             Best cand{sc[e], it * npose + q, isnan(sc[e]) ? 1 : 0};
             if (better(cand, me)) me = cand;
         }
     }
-    // per-wave reduction for k_select: max / argmax / sum exp(score - max)
-    me = wave_best_ordered(me);                            // lane = one slot: indices ascend with the lane
-    double ex = 0.0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (e < nv) ex += exp(sc[e] - me.v);
-    ex = wave_sum(ex);
+    // the chunk's partial for k_select (lane = one slot: indices ascend with the lane)
+    const Slam2dPartial pt = plane_partial(me, sc, nv);
     if (lane == 0) {
-        Slam2dPartial pt;
-        pt.max = me.v; pt.sumexp = ex; pt.argmax = me.i; pt.has_nan = me.nan;
         Slam2dPartial* dst = lv.partials + (size_t)p * lv.npartial + it * chunks + ch;
         if (mode == 0 && sel_out != nullptr) {             // (the particle's last block reads it in this launch: write-through)
             unsigned long long* u = reinterpret_cast<unsigned long long*>(dst);
@@ -1923,22 +1977,20 @@ template <int NWAVES>
 __device__ __forceinline__ Best sweep_small_plane(const Slam2dLevel& lv, const int p, const int it, unsigned long long* small_lds,
                                                   const bool write) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
-    const int nq = (nx + 3) >> 2, nslot = nx * nq;             // <= 32 (checked by the host)
+    const Cube cube = cube_of(lv);
+    const int npose = cube.npose, nslot = cube.nslot;           // nslot <= 32 (checked by the host)
     const int S = WAVE / nslot;                                 // cell slices per wave
     const int K = lv.kcount[p * lv.ntheta + it];
     const int* __restrict__ cl = lv.cells + ((size_t)p * lv.ntheta + it) * lv.kmax;
     int* cells_s = reinterpret_cast<int*>(small_lds + NWAVES * WAVE * 4);
     for (int k = threadIdx.x; k < K; k += NWAVES * WAVE) cells_s[k] = cl[k];
-    const size_t image = (size_t)lv.fmax * lv.fpitch;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.field + (size_t)p * image), (short)0, (int)(image * sizeof(uint32_t)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = field_rsrc(lv, p);
     const bool active = lane < S * nslot;
-    const int u = lane % nslot, sl = lane / nslot;
-    const int iy = u / nq, dx = (u - iy * nq) * 4;
-    const int off = (iy * lv.fpitch + dx) * 4;
+    const int sl = lane / nslot;
+    const Slot slot = slot_of(cube, lv.fpitch, lane % nslot);
+    const int off = slot.off;
     const int ST = S * NWAVES;                                  // slices of the whole block
-    unsigned lo[4] = {0u, 0u, 0u, 0u}, hi[4] = {0u, 0u, 0u, 0u};
+    Acc4 acc4;
     __syncthreads();
     for (int k = sl + S * wave; k < K; k += 8 * ST) {           // 8 gathers in flight
         int o[8];
@@ -1948,24 +2000,18 @@ __device__ __forceinline__ Best sweep_small_plane(const Slam2dLevel& lv, const i
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o[i], 0, 0);
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned s2 = lo[e] + v[i][e];
-                hi[e] += s2 < v[i][e] ? 1u : 0u;
-                lo[e] = s2;
-            }
+        for (int i = 0; i < 8; ++i) acc4.add(v[i]);
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) small_lds[(wave * 4 + e) * WAVE + lane] = ((unsigned long long)hi[e] << 32) | lo[e];
+    for (int e = 0; e < 4; ++e) small_lds[(wave * 4 + e) * WAVE + lane] = acc4.get(e);
     __syncthreads();
     Best me{-INFINITY, INT_MAX, 0};
     if (NWAVES > 1 && wave != 0) return me;
-    const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
     double* __restrict__ out = lv.cube + ((size_t)p * lv.ntheta + it) * npose;
     const double inv = 1.0 / lv.cost_scale;
-    const int nv = lane < nslot ? min(4, nx - dx) : 0, q0 = iy * nx + dx;
-    double sc[4];
+    const int nv = lane < nslot ? slot.nv : 0, q0 = slot.q0;
+    double sc[4], prv[4], ptw[4];
+    slot_priors(lv.prior + (size_t)p * 2 * npose, cube, q0, prv, ptw);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         sc[e] = -INFINITY;
@@ -1974,34 +2020,24 @@ __device__ __forceinline__ Best sweep_small_plane(const Slam2dLevel& lv, const i
             for (int w2 = 0; w2 < NWAVES; ++w2)
                 for (int s2 = 0; s2 < S; ++s2) acc += small_lds[(w2 * 4 + e) * WAVE + lane + s2 * nslot];
             const int q = q0 + e;
-            sc[e] = (-((double)acc * inv) + pr[q]) + pr[npose + q];                 // :131, as k_sweep
+            sc[e] = pose_score(acc, inv, prv[e], ptw[e]);
             if (write) out[q] = sc[e];
             Best cand{sc[e], it * npose + q, isnan(sc[e]) ? 1 : 0};
             if (better(cand, me)) me = cand;
         }
     }
-    me = wave_best_ordered(me);
-    if (!write) return me;
-    double ex = 0.0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (e < nv) ex += exp(sc[e] - me.v);
-    ex = wave_sum(ex);
-    if (lane == 0) {
-        Slam2dPartial pt;
-        pt.max = me.v; pt.sumexp = ex; pt.argmax = me.i; pt.has_nan = me.nan;
-        lv.partials[(size_t)p * lv.npartial + it] = pt;
-    }
-    return me;
+    if (!write) return wave_best_ordered(me);
+    const Slam2dPartial pt = plane_partial(me, sc, nv);
+    if (lane == 0) lv.partials[(size_t)p * lv.npartial + it] = pt;
+    return Best{pt.max, pt.argmax, pt.has_nan};
 }
 // pruned != 0 (Slam2dLevel.bnb == 3, "angle bounds"): a plane whose upper bound (k_abound) lies more than SLAM2D_BNB_MARGIN
 // below the particle's seed score (k_aseed) is not scored -- it cannot hold the arg-max and all such planes together change
 // the confidence by < ntheta * 25 * exp(-30) relative; its partial says "nothing here".
 __global__ __launch_bounds__(64) void k_sweep_small(Slam2dLevel lv, int P, int pruned) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long small_lds[];   // [64 * 4] partial sums, then [kmax] cells
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;
-    const int p = (slot / lv.ntheta) * 8 + xcd, it = slot % lv.ntheta;
+    int p, it;
+    xcd_particle(blockIdx.x, lv.ntheta, &p, &it);
     if (p >= P) return;
     if (pruned && !(lv.bounds[(size_t)p * lv.ntheta + it] >= unorder_bits(lv.bnb_best[p]) - SLAM2D_BNB_MARGIN)) {
         if (threadIdx.x == 0) {
@@ -2030,18 +2066,17 @@ __global__ __launch_bounds__(64) void k_sweep_small(Slam2dLevel lv, int P, int p
 #define ABOUND_WAVES 16
 #endif
 __global__ __launch_bounds__(64 * ABOUND_WAVES) void k_abound(Slam2dLevel lv, int P) {
-    const int b = blockIdx.x;
     const int ngrp = (lv.ntheta + ABOUND_WAVES - 1) / ABOUND_WAVES;
-    const int xcd = b & 7, slot = b >> 3;
-    const int p = (slot / ngrp) * 8 + xcd, it = (slot % ngrp) * ABOUND_WAVES + (threadIdx.x >> 6);
+    int p, grp;
+    xcd_particle(blockIdx.x, ngrp, &p, &grp);
+    const int it = grp * ABOUND_WAVES + (threadIdx.x >> 6);
     if (p >= P || it >= lv.ntheta) return;
     const int lane = threadIdx.x & 63;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
+    const int npose = cube_of(lv).npose;
     const int gp = lv.tmax << 2;
     const int K = lv.kcount[p * lv.ntheta + it];
     const int* __restrict__ pcl = lv.pcells + ((size_t)p * lv.ntheta + it) * lv.kmax;
-    const __amdgpu_buffer_rsrc_t rg2 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.gmin2 + (size_t)p * gp * gp), (short)0, (int)((size_t)gp * gp * sizeof(uint32_t)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rg2 = image_rsrc(lv.gmin2 + (size_t)p * gp * gp, (size_t)gp * gp * sizeof(uint32_t));
     // (Every term of the bound is <= 0, so leaving cells out keeps it an upper bound -- but using every 4th cell of the list
     // already made it too loose to prune anything at config 5: the exact sweep went from 32 back to 156 us.  Stride 1.)
     unsigned sum = 0u;                                     // 20-bit values, <= 2048 cells: no carry
@@ -2099,7 +2134,8 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const
     // mode as in k_sweep.  In mode 1 only the first ceil(ring length / 64) chunks of every theta hold
     // partials; the partial of (theta it, chunk ch) sits at it * chunks + ch in every mode.
     const int p = blockIdx.x, lane = threadIdx.x;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx, npose = cube.npose;
     if (mode == 2 && lv.prune_state[p] == 0) return;
     if (mode == 1 && lv.prune_state[p] != 0) return;
     const int nring = mode == 1 ? lv.ring[0] : 0;
@@ -2109,14 +2145,10 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const
     const Slam2dPartial* __restrict__ pt0 = lv.partials + (size_t)p * lv.npartial;
     auto part = [&](const int v) -> const Slam2dPartial& { return pt0[(v / vch) * chunks + (v % vch)]; };
     const double* __restrict__ c = lv.cube + (size_t)p * lv.ntheta * npose;
-    // global max / argmax
-    Best me{-INFINITY, INT_MAX, 0};
-    for (int w = lane; w < nW; w += WAVE) {
-        Best cand{part(w).max, part(w).argmax, part(w).has_nan};
-        if (better(cand, me)) me = cand;
-    }
-    me = wave_best_fast(me);
-    const double M = me.v;
+    // global max / argmax; total = sum_w sumexp_w * exp(max_w - M)
+    const PartialsTotal pt = partials_total(nW, part);
+    const Best me = pt.best;
+    const double M = me.v, mine = pt.mine, incl = pt.incl, total = pt.total;
     if (mode == 1) {
         // a pose outside the ring scores rv + (field sum) + thetaWeight <= -100 + K * (largest field value);
         // K = cells of its theta, so the fewest cells of any theta give the bound for all of them
@@ -2129,13 +2161,7 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const
             return;
         }
     }
-    // total = sum_w sumexp_w * exp(max_w - M): each lane owns a contiguous run of partials
-    const int per = (nW + WAVE - 1) / WAVE;
-    const int w0 = lane * per, w1 = min(nW, w0 + per);
-    double mine = 0.0;
-    for (int w = w0; w < w1; ++w) mine += part(w).sumexp * exp(part(w).max - M);
-    const double incl = wave_scan_incl_f64(mine);     // inclusive scan over lanes
-    const double total = readlane_f64(incl, WAVE - 1);
+    const int per = (nW + WAVE - 1) / WAVE;           // partials per lane
     int pick = me.i;
     if (uniform != nullptr && !isnan(total)) {
         // np.random.choice(n, 1, p): first index whose normalised cdf exceeds u (:137-138)
@@ -2151,14 +2177,13 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const
             run += t;
         }
         const int it = wsel / vch, ch = wsel - it * vch;
-        const int nq = (nx + 3) >> 2, nslot = nx * nq;
+        const int nslot = cube.nslot;
         if (mode == 1) {
             // ring chunk: lane l owns slot ring[ch*64 + l] = up to 4 consecutive poses; slots ascend with l,
             // so the lanes walk the chunk's poses in cube order
             const int idx = ch * WAVE + lane;
-            const int u = idx < nring ? lv.ring[1 + idx] : nslot;
-            const int iy = u / nq, dx = (u - iy * nq) * 4;
-            const int q0 = iy * nx + dx, nvl = u < nslot ? min(4, nx - dx) : 0;
+            const Slot sl = slot_of(cube, lv.fpitch, idx < nring ? lv.ring[1 + idx] : nslot);
+            const int q0 = sl.q0, nvl = sl.nv;
             double lsum = 0.0;
             for (int e = 0; e < nvl; ++e) lsum += exp(c[(size_t)it * npose + q0 + e] - M);
             const double linc = wave_scan_incl_f64(lsum);
@@ -2179,9 +2204,8 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const
         } else {
         // inside chunk wsel: it covers slots [ch*64, ...) = a contiguous pose range [qlo, qhi);
         // lane l owns a contiguous run of `per2` poses of it
-        const int s0c = min(nslot, ch * WAVE), s1c = min(nslot, (ch + 1) * WAVE);
-        const int qlo = (s0c / nq) * nx + min(nx, 4 * (s0c % nq));
-        const int qhi = (s1c / nq) * nx + min(nx, 4 * (s1c % nq));
+        auto first_pose = [&](const int s) { return s < nslot ? slot_of(cube, lv.fpitch, s).q0 : npose; };
+        const int qlo = first_pose(ch * WAVE), qhi = first_pose((ch + 1) * WAVE);
         const int per2 = (qhi - qlo + WAVE - 1) / WAVE;
         const int a0 = qlo + lane * per2, a1 = min(qhi, a0 + per2);
         double lsum = 0.0;
@@ -2205,20 +2229,8 @@ __global__ __launch_bounds__(64) void k_select(Slam2dLevel lv, int chunks, const
         }
     }
     if (lane == 0) {
-        Slam2dMatch m;
-        const int it = pick / npose, rem = pick - it * npose;
-        const int iy = rem / nx, ix = rem - iy * nx;
-        const double ex = est[(size_t)p * estride], ey = est[(size_t)p * estride + 1], eth = est[(size_t)p * estride + 2];
-        m.x = ex + (double)(ix - lv.ncell) * lv.step;                               // :142-143
-        m.y = ey + (double)(iy - lv.ncell) * lv.step;
-        m.theta = eth + lv.thetas[it];
-        m.confidence = exp(M) * total;                                              // :141
-        m.log_confidence = M + log(total);
-        m.best_score = M;
-        m.pick = pick;
-        m.argmax = me.i;
-        out[p] = m;
-        if (lv.arrive) __hip_atomic_fetch_add(lv.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (Slam2dScan.match_seq)
+        const double* e = est + (size_t)p * estride;
+        store_match(lv, p, e[0], e[1], e[2], lv.thetas[pick / npose], pick, me.i, M, total, out);
     }
 }
 
@@ -2258,19 +2270,13 @@ __device__ __forceinline__ void tile_exact(const Slam2dLevel& lv, const __amdgpu
                                            unsigned long long (&acc)[4]) {
     const int lane = threadIdx.x & 63, r = lane >> 4, s = lane & 15;
     const int lanepart = ((4 * by + r) * lv.fpitch + 4 * bx) * 4;
-    unsigned lo[4] = {0u, 0u, 0u, 0u}, hi[4] = {0u, 0u, 0u, 0u};
+    Acc4 sum;
     {
         u32x4 v[NPRE];
 #pragma unroll
         for (int i = 0; i < NPRE; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lanepart + pre[i], 0, 0);
 #pragma unroll
-        for (int i = 0; i < NPRE; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned s2 = lo[e] + v[i][e];
-                hi[e] += s2 < v[i][e] ? 1u : 0u;
-                lo[e] = s2;
-            }
+        for (int i = 0; i < NPRE; ++i) sum.add(v[i]);
     }
     for (int k = s + 16 * NPRE; k < K; k += EXACT_DEPTH * 16) {            // longer lists
         int off[EXACT_DEPTH];
@@ -2283,16 +2289,42 @@ __device__ __forceinline__ void tile_exact(const Slam2dLevel& lv, const __amdgpu
 #pragma unroll
         for (int i = 0; i < EXACT_DEPTH; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i], 0, 0);
 #pragma unroll
-        for (int i = 0; i < EXACT_DEPTH; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned s2 = lo[e] + v[i][e];
-                hi[e] += s2 < v[i][e] ? 1u : 0u;
-                lo[e] = s2;
-            }
+        for (int i = 0; i < EXACT_DEPTH; ++i) sum.add(v[i]);
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = row16_sum_u64(((unsigned long long)hi[e] << 32) | lo[e]);
+    for (int e = 0; e < 4; ++e) acc[e] = row16_sum_u64(sum.get(e));
+}
+// A seed: tile (sby, sbx) of one (particle, theta) scored exactly by one wave from the prefetched offsets `pre`; its best
+// score, a lower bound of the cube's maximum, raises lv.bnb_best[p] (atomic max: order-independent, deterministic).
+template <int NPRE>
+__device__ __forceinline__ void tile_seed(const Slam2dLevel& lv, const int p, const int sby, const int sbx, const int* __restrict__ cl,
+                                          const int K, const double inv, const int (&pre)[NPRE]) {
+    const int lane = threadIdx.x & 63;
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx, npose = cube.npose;
+    const int dy = 4 * sby + (lane >> 4);
+    const bool leader = (lane & 15) == 0 && dy < nx;
+    const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
+    double prv[4], ptw[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {                           // issued ahead of the tile's field loads
+        const int qq = min(dy, nx - 1) * nx + min(4 * sbx + e, nx - 1);
+        prv[e] = pr[qq]; ptw[e] = pr[npose + qq];
+    }
+    unsigned long long acc[4];
+    tile_exact<NPRE>(lv, field_rsrc(lv, p), cl, K, sby, sbx, pre, acc);
+    double val = -INFINITY;
+    if (leader) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (4 * sbx + e < nx) {
+                const double sc = pose_score(acc[e], inv, prv[e], ptw[e]);
+                if (!isnan(sc)) val = fmax(val, sc);
+            }
+    }
+    val = fmax(val, __shfl_xor(val, 16));
+    val = fmax(val, __shfl_xor(val, 32));
+    if (lane == 0 && val > -INFINITY) atomicMax(&lv.bnb_best[p], order_bits(val));
 }
 
 // One wave per (particle, theta); blocks of a particle pinned to one XCD like the sweep's.  Lane = one pose-tile row
@@ -2306,18 +2338,18 @@ __device__ __forceinline__ void tile_exact(const Slam2dLevel& lv, const __amdgpu
 __global__ __launch_bounds__(64 * BOUND_GROUP) void k_bound(Slam2dLevel lv, int P) {
     const int b = blockIdx.x;
     const int ngroup = (lv.ntheta + BOUND_GROUP - 1) / BOUND_GROUP;
-    const int xcd = b & 7, slot = b >> 3;
-    const int p = (slot / ngroup) * 8 + xcd, it = (slot % ngroup) * BOUND_GROUP + (threadIdx.x >> 6);
+    int p, grp;
+    xcd_particle(b, ngroup, &p, &grp);
+    const int it = grp * BOUND_GROUP + (threadIdx.x >> 6);
     if (p >= P || it >= lv.ntheta) return;
     const int lane = threadIdx.x & 63;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
-    const int nbt = (nx + 3) >> 2, nq = (nbt + 3) >> 2, nbq4 = nq << 2;
+    const Cube cube = cube_of(lv);
+    const int nbt = cube.nbt, nbq4 = cube.nbq4, nq = nbq4 >> 2;      // nq: lanes (of 4 tiles) per tile row
     const int gp = lv.tmax << 2;
     const int K = lv.kcount[p * lv.ntheta + it];
     const int* __restrict__ pcl = lv.pcells + ((size_t)p * lv.ntheta + it) * lv.kmax;
     const int* __restrict__ cl = lv.cells + ((size_t)p * lv.ntheta + it) * lv.kmax;
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.gmin2 + (size_t)p * gp * gp), (short)0, (int)((size_t)gp * gp * sizeof(uint32_t)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rg = image_rsrc(lv.gmin2 + (size_t)p * gp * gp, (size_t)gp * gp * sizeof(uint32_t));
     DBG_CLOCK(0, b == 0);
     const bool active = lane < nbt * nq;
     const int by = lane / nq, q = lane - by * nq;
@@ -2373,70 +2405,17 @@ __global__ __launch_bounds__(64 * BOUND_GROUP) void k_bound(Slam2dLevel lv, int 
     // the tile with the largest bound, exactly: its best score is a lower bound of the cube's maximum
     const int seed = me.i;
     const int sby = seed / nbq4, sbx = seed - sby * nbq4;
-    const int dy = 4 * sby + (lane >> 4);
-    const bool leader = (lane & 15) == 0 && dy < nx;
-    const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
-    double prv[4], ptw[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {                           // issued ahead of the tile's field loads
-        const int qq = min(dy, nx - 1) * nx + min(4 * sbx + e, nx - 1);
-        prv[e] = pr[qq]; ptw[e] = pr[npose + qq];
-    }
-    const size_t image = (size_t)lv.fmax * lv.fpitch;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.field + (size_t)p * image), (short)0, (int)(image * sizeof(uint32_t)), 0x00020000);
-    unsigned long long acc[4];
-    tile_exact<16>(lv, rsrc, cl, K, sby, sbx, pre, acc);
-    double val = -INFINITY;
-    if (leader) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (4 * sbx + e < nx) {
-                const double sc = (-((double)acc[e] * inv) + prv[e]) + ptw[e];
-                if (!isnan(sc)) val = fmax(val, sc);
-            }
-    }
-    val = fmax(val, __shfl_xor(val, 16));
-    val = fmax(val, __shfl_xor(val, 32));
+    tile_seed<16>(lv, p, sby, sbx, cl, K, inv, pre);
     DBG_CLOCK(3, b == 0);
-    if (lane == 0 && val > -INFINITY) atomicMax(&lv.bnb_best[p], order_bits(val));
     DBG_CLOCK(4, b == 0);
 }
 
-// The seed of one (particle, theta): tile `seed` (the one with the largest bound) scored exactly by one wave; its best score
-// raises lv.bnb_best[p].  (k_bound carries the same lines inline.)
+// The seed of one (particle, theta) whose cell offsets nobody has fetched yet
 __device__ __forceinline__ void bound_seed_exact(const Slam2dLevel& lv, const int p, const int sby, const int sbx, const int* __restrict__ cl,
                                                  const int K, const double inv) {
-    const int lane = threadIdx.x & 63;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
     int pre[16];
     tile_prefetch<16>(cl, K, pre);
-    const int dy = 4 * sby + (lane >> 4);
-    const bool leader = (lane & 15) == 0 && dy < nx;
-    const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
-    double prv[4], ptw[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {                           // issued ahead of the tile's field loads
-        const int qq = min(dy, nx - 1) * nx + min(4 * sbx + e, nx - 1);
-        prv[e] = pr[qq]; ptw[e] = pr[npose + qq];
-    }
-    const size_t image = (size_t)lv.fmax * lv.fpitch;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.field + (size_t)p * image), (short)0, (int)(image * sizeof(uint32_t)), 0x00020000);
-    unsigned long long acc[4];
-    tile_exact<16>(lv, rsrc, cl, K, sby, sbx, pre, acc);
-    double val = -INFINITY;
-    if (leader) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (4 * sbx + e < nx) {
-                const double sc = (-((double)acc[e] * inv) + prv[e]) + ptw[e];
-                if (!isnan(sc)) val = fmax(val, sc);
-            }
-    }
-    val = fmax(val, __shfl_xor(val, 16));
-    val = fmax(val, __shfl_xor(val, 32));
-    if (lane == 0 && val > -INFINITY) atomicMax(&lv.bnb_best[p], order_bits(val));
+    tile_seed<16>(lv, p, sby, sbx, cl, K, inv, pre);
 }
 
 // k_bound with the particle's bound image staged in LDS (the filled-machine form: DESIGN 4).  k_bound's loop is bound by the L1's
@@ -2535,12 +2514,12 @@ template <int NSET, bool RLE>
 __global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int bpp, int tpb, int refresh) {
     extern __shared__ __attribute__((aligned(16))) unsigned char g2s[];                  // [gp][lp] (+ RLE: [waves][64] words)
     const int lp = lv.g2b_pitch;
-    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-    const int p = (slot / bpp) * 8 + xcd, part = slot % bpp;
+    const int b = blockIdx.x;
+    int p, part;
+    xcd_particle(b, bpp, &p, &part);
     if (p >= P) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
-    const int nx = 2 * lv.ncell + 1;
-    const int nbt = (nx + 3) >> 2, nq = (nbt + 3) >> 2, nbq4 = nq << 2;
+    const int nbt = cube_of(lv).nbt, nbq4 = cube_of(lv).nbq4;
     const int gp = lv.tmax << 2;
     DBG_CLOCK(0, b == 0);
     // the refresh's chain starts ahead of the staging loads (refresh, and hence every branch on it, is uniform over the launch)
@@ -2754,13 +2733,12 @@ __device__ __forceinline__ double children_bounds(const Slam2dLevel& lv, const _
 #define B1_DEPTH 16
 __global__ __launch_bounds__(64) void k_bound1(Slam2dLevel lv, int P) {
     extern __shared__ __attribute__((aligned(16))) int b1_lds[];      // [64 * 4] partial sums, then [kmax] cell offsets
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;
-    const int p = (slot / lv.ntheta) * 8 + xcd, it = slot % lv.ntheta;
+    int p, it;
+    xcd_particle(blockIdx.x, lv.ntheta, &p, &it);
     if (p >= P) return;
     const int lane = threadIdx.x;
-    const int nx = 2 * lv.ncell + 1;
-    const int nbt = (nx + 3) >> 2, nbq4 = ((nbt + 3) >> 2) << 2;
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx, nbt = cube.nbt, nbq4 = cube.nbq4;
     const int nb1 = (nx + 7) >> 3, nq1 = (nb1 + 3) >> 2, L = nb1 * nq1, C = WAVE / L;
     const int gp = lv.tmax << 2, hp = gp >> 1;
     const int K = lv.kcount[p * lv.ntheta + it];
@@ -2768,8 +2746,7 @@ __global__ __launch_bounds__(64) void k_bound1(Slam2dLevel lv, int P) {
     unsigned* red = reinterpret_cast<unsigned*>(b1_lds);
     int* cs = b1_lds + WAVE * 4;
     for (int k = lane; k < K; k += WAVE) cs[k] = p3[k];
-    const __amdgpu_buffer_rsrc_t rg3 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.gmin3d + (size_t)p * gp * gp), (short)0, (int)((size_t)gp * gp * sizeof(uint32_t)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rg3 = image_rsrc(lv.gmin3d + (size_t)p * gp * gp, (size_t)gp * gp * sizeof(uint32_t));
     const int g = lane / L, l2 = lane - g * L, r = l2 / nq1, q = l2 - r * nq1;
     const bool active = g < C;
     const int lanepart = (r * hp + 4 * q) * 4;
@@ -2841,8 +2818,8 @@ __global__ __launch_bounds__(SEED_THREADS) void k_seed(Slam2dLevel lv, int P) {
     const unsigned long long key = lv.seed_key[p];
     if (!key) return;                                       // no finite bound anywhere: no threshold, every tile is scored
     const int it = (int)(key >> 6) & 0xFF, t1 = (int)key & 63, R = t1 >> 3, Cx = t1 & 7;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
-    const int nbt = (nx + 3) >> 2, nbq4 = ((nbt + 3) >> 2) << 2;
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx, npose = cube.npose, nbt = cube.nbt, nbq4 = cube.nbq4;
     const int gp = lv.tmax << 2;
     const int K = lv.kcount[p * lv.ntheta + it];
     const int* __restrict__ pcl = lv.pcells + ((size_t)p * lv.ntheta + it) * lv.kmax;
@@ -2851,8 +2828,7 @@ __global__ __launch_bounds__(SEED_THREADS) void k_seed(Slam2dLevel lv, int P) {
     if (tid < 16) acc_s[tid] = 0ull;
     __syncthreads();
     {
-        const __amdgpu_buffer_rsrc_t rg2 = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(lv.gmin2 + (size_t)p * gp * gp), (short)0, (int)((size_t)gp * gp * sizeof(uint32_t)), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rg2 = image_rsrc(lv.gmin2 + (size_t)p * gp * gp, (size_t)gp * gp * sizeof(uint32_t));
         unsigned s4[4] = {0u, 0u, 0u, 0u};
         for (int k = tid; k < K; k += SEED_THREADS) {
             const int off = pcl[k];
@@ -2885,9 +2861,7 @@ __global__ __launch_bounds__(SEED_THREADS) void k_seed(Slam2dLevel lv, int P) {
     __syncthreads();
     const int sby = 2 * R + (best_s >> 1), sbx = 2 * Cx + (best_s & 1);
     {
-        const size_t image = (size_t)lv.fmax * lv.fpitch;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(lv.field + (size_t)p * image), (short)0, (int)(image * sizeof(uint32_t)), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc = field_rsrc(lv, p);
         unsigned long long a[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) a[i] = 0ull;
@@ -2915,7 +2889,7 @@ __global__ __launch_bounds__(SEED_THREADS) void k_seed(Slam2dLevel lv, int P) {
             for (int e = 0; e < 4; ++e) {
                 const int dy = 4 * sby + r, dx = 4 * sbx + e;
                 if (dy >= nx || dx >= nx) continue;
-                const double sc = (-((double)acc_s[r * 4 + e] * inv) + pr[dy * nx + dx]) + pr[npose + dy * nx + dx];
+                const double sc = pose_score(acc_s[r * 4 + e], inv, pr[dy * nx + dx], pr[npose + dy * nx + dx]);
                 if (!isnan(sc)) val = fmax(val, sc);
             }
         if (val > -INFINITY) lv.bnb_best[p] = order_bits(val);
@@ -2928,13 +2902,11 @@ __global__ __launch_bounds__(SEED_THREADS) void k_seed(Slam2dLevel lv, int P) {
 // seed that is skipped because of a fresher value has a bound below the FINAL best, so neither the final bnb_best (the
 // maximum over all candidate seeds) nor the set of tiles k_exact_select keeps depends on the timing.
 __global__ __launch_bounds__(64) void k_bound2(Slam2dLevel lv, int P) {
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;
-    const int p = (slot / lv.ntheta) * 8 + xcd, it = slot % lv.ntheta;
+    int p, it;
+    xcd_particle(blockIdx.x, lv.ntheta, &p, &it);
     if (p >= P) return;
     const int lane = threadIdx.x;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
-    const int nbt = (nx + 3) >> 2, nbq4 = ((nbt + 3) >> 2) << 2, nt = nbt * nbq4;
+    const int nbt = cube_of(lv).nbt, nbq4 = cube_of(lv).nbq4, nt = nbt * nbq4;
     const int gp = lv.tmax << 2;
     const double thr = unorder_bits(__hip_atomic_load(&lv.bnb_best[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) - SLAM2D_BNB_MARGIN;
     double* __restrict__ bnd = lv.bounds + ((size_t)p * lv.ntheta + it) * nt;
@@ -2946,8 +2918,7 @@ __global__ __launch_bounds__(64) void k_bound2(Slam2dLevel lv, int P) {
     const int* __restrict__ pcl = lv.pcells + ((size_t)p * lv.ntheta + it) * lv.kmax;
     const int* __restrict__ cl = lv.cells + ((size_t)p * lv.ntheta + it) * lv.kmax;
     const double* __restrict__ pm = lv.tile_pmax + (size_t)p * nbt * nbq4;
-    const __amdgpu_buffer_rsrc_t rg2 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.gmin2 + (size_t)p * gp * gp), (short)0, (int)((size_t)gp * gp * sizeof(uint32_t)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rg2 = image_rsrc(lv.gmin2 + (size_t)p * gp * gp, (size_t)gp * gp * sizeof(uint32_t));
     const double inv = 1.0 / lv.cost_scale;
     int pre[8];
     tile_prefetch<8>(cl, K, pre);                           // for the seed below
@@ -2968,33 +2939,7 @@ __global__ __launch_bounds__(64) void k_bound2(Slam2dLevel lv, int P) {
     }
     if (seed < 0) return;
     if (ub < unorder_bits(__hip_atomic_load(&lv.bnb_best[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) return;
-    const int sby = seed / nbq4, sbx = seed - sby * nbq4;
-    const int dy = 4 * sby + (lane >> 4);
-    const bool leader = (lane & 15) == 0 && dy < nx;
-    const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
-    double prv[4], ptw[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int qq = min(dy, nx - 1) * nx + min(4 * sbx + e, nx - 1);
-        prv[e] = pr[qq]; ptw[e] = pr[npose + qq];
-    }
-    const size_t image = (size_t)lv.fmax * lv.fpitch;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.field + (size_t)p * image), (short)0, (int)(image * sizeof(uint32_t)), 0x00020000);
-    unsigned long long acc[4];
-    tile_exact<8>(lv, rsrc, cl, K, sby, sbx, pre, acc);
-    double val = -INFINITY;
-    if (leader) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (4 * sbx + e < nx) {
-                const double sc = (-((double)acc[e] * inv) + prv[e]) + ptw[e];
-                if (!isnan(sc)) val = fmax(val, sc);
-            }
-    }
-    val = fmax(val, __shfl_xor(val, 16));
-    val = fmax(val, __shfl_xor(val, 32));
-    if (lane == 0 && val > -INFINITY) atomicMax(&lv.bnb_best[p], order_bits(val));
+    tile_seed<8>(lv, p, seed / nbq4, seed % nbq4, cl, K, inv, pre);
 }
 
 // One block per particle: the tiles whose bound reaches bnb_best - SLAM2D_BNB_MARGIN, exactly, then the selection
@@ -3059,13 +3004,12 @@ __global__ __launch_bounds__(XS_THREADS) void k_exact_select(Slam2dLevel lv, con
     const int tid = threadIdx.x;
     int p = blockIdx.x, part = 0;
     if constexpr (SPLIT) {                             // block b runs on XCD b % 8: a particle's blocks share that XCD's L2
-        const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-        p = (slot / nsplit) * 8 + xcd; part = slot % nsplit;
+        xcd_particle(blockIdx.x, nsplit, &p, &part);
         if (p >= P) return;
     }
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
-    const int nbt = (nx + 3) >> 2, nbq4 = ((nbt + 3) >> 2) << 2, nt = nbt * nbq4;
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx, npose = cube.npose, nbt = cube.nbt, nbq4 = cube.nbq4, nt = nbt * nbq4;
     const int ntot = lv.ntheta * nt;
     const double thr = unorder_bits(lv.bnb_best[p]) - SLAM2D_BNB_MARGIN;
     const double* __restrict__ bnd = lv.bounds + (size_t)p * ntot;
@@ -3104,9 +3048,7 @@ __global__ __launch_bounds__(XS_THREADS) void k_exact_select(Slam2dLevel lv, con
     int off = incl - cnt, n_all = 0;
     for (int w2 = 0; w2 < XS_THREADS / WAVE; ++w2) { const int c = wtot_s[w2]; if (w2 < wave) off += c; n_all += c; }
     DBG_CLOCK(9, p == 0);
-    const size_t image = (size_t)lv.fmax * lv.fpitch;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(lv.field + (size_t)p * image), (short)0, (int)(image * sizeof(uint32_t)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = field_rsrc(lv, p);
     const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
     const double inv = 1.0 / lv.cost_scale;
     // the pass's list: surviving tiles [base, base + XS_TILES) in ascending (theta, tile) order
@@ -3149,7 +3091,7 @@ __global__ __launch_bounds__(XS_THREADS) void k_exact_select(Slam2dLevel lv, con
             if (e < 4) {
                 const unsigned long long a = e == 0 ? acc[0] : e == 1 ? acc[1] : e == 2 ? acc[2] : acc[3];
                 if (scorer) {
-                    sc = (-((double)a * inv) + prv) + ptw;                                    // :131, as k_sweep
+                    sc = pose_score(a, inv, prv, ptw);
                     store_score(&lv.cube[((size_t)p * lv.ntheta + it) * npose + qq], sc, SPLIT);
                 }
                 if constexpr (!SPLIT) sc_s[j][r * 4 + e] = sc;
@@ -3394,21 +3336,7 @@ __global__ __launch_bounds__(XS_THREADS) void k_exact_select(Slam2dLevel lv, con
     }
     const int it_sel = __builtin_amdgcn_readfirstlane(pick / npose);
     const double th_sel = lv.ntheta <= WAVE ? readlane_f64(th_pre, it_sel) : lv.thetas[it_sel];
-    if (lane == 0) {
-        Slam2dMatch m;
-        const int it = pick / npose, rem = pick - it * npose;
-        const int iy = rem / nx, ix = rem - iy * nx;
-        m.x = ex + (double)(ix - lv.ncell) * lv.step;                               // :142-143
-        m.y = ey + (double)(iy - lv.ncell) * lv.step;
-        m.theta = eth + th_sel;
-        m.confidence = exp(M) * total;                                              // :141
-        m.log_confidence = M + log(total);
-        m.best_score = M;
-        m.pick = pick;
-        m.argmax = Mi_s[0];
-        out[p] = m;
-        if (lv.arrive) __hip_atomic_fetch_add(lv.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (Slam2dScan.match_seq)
-    }
+    if (lane == 0) store_match(lv, p, ex, ey, eth, th_sel, pick, Mi_s[0], M, total, out);
     DBG_CLOCK(13, p == 0);
 }
 
@@ -4628,8 +4556,8 @@ __global__ void k_fill(uint32_t* cells, long long n, uint32_t value) {
 }
 
 // ------------------------------------------------------------------------------------
-// Pose mean and covariance of a match (slam2d_match_moments): every pose of the cube is scored again, exactly as k_sweep scores
-// it -- the same 64-bit integer sum over the unique endpoint cells, the same expression with the two prior planes -- and turned
+// Pose mean and covariance of a match (slam2d_match_moments): every pose of the cube is scored again through the
+// exact-score core k_sweep scores it with -- Acc4 over the unique endpoint cells, pose_score with the two prior planes -- and turned
 // into the weight w = exp(score - M), M = Slam2dMatch.best_score; the cube itself is neither read nor written (after branch and
 // bound it holds only the scored tiles, and the skipped poses' mass times offset^2 is not negligible for a second moment).
 // k_sweep's work shape: a block per (particle, theta, chunk of 64 slots), a lane owns the 4 consecutive dx of one slot through
@@ -4642,54 +4570,37 @@ __global__ void k_fill(uint32_t* cells, long long n, uint32_t value) {
 // ------------------------------------------------------------------------------------
 #define MOMENTS_ROW 12               // sum w | sum w d (x, y, theta) | sum w d d^T (xx, xy, xt, yy, yt, tt) | poses | NaN scores
 __device__ __forceinline__ int moments_argmax(const Slam2dLevel& lv, const Slam2dMatch* __restrict__ match, const int p) {
-    const int nx = 2 * lv.ncell + 1;
     const int a = match[p].argmax;
-    return (a >= 0 && a < lv.ntheta * nx * nx) ? a : 0;          // (a record nobody wrote: any pose serves as the origin)
+    return (a >= 0 && a < lv.ntheta * cube_of(lv).npose) ? a : 0;         // (a record nobody wrote: any pose serves as the origin)
 }
 __global__ __launch_bounds__(256) void k_moments(Slam2dLevel lv, int P, int chunks, int bpp, const Slam2dMatch* __restrict__ match,
                                                  double* __restrict__ work) {
     __shared__ unsigned long long part_s[3][WAVE * 4];
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;                         // blocks of one particle share an XCD's L2, as in k_sweep
-    const int p = (slot / bpp) * 8 + xcd;
+    int p, w;
+    xcd_particle(blockIdx.x, bpp, &p, &w);
     if (p >= P) return;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    const int w = slot % bpp;
     const int it = w / chunks, ch = w - it * chunks;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
-    const int nq = (nx + 3) >> 2, nslot = nx * nq;
-    const uint32_t* __restrict__ F = lv.field + (size_t)p * lv.fmax * lv.fpitch;
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx, npose = cube.npose;
     const int* __restrict__ cl = lv.cells + ((size_t)p * lv.ntheta + it) * lv.kmax;
     const int K = min(lv.kcount[p * lv.ntheta + it], lv.kmax);
-    // k_sweep's buffer addressing: field base + per-lane byte offset + wave-uniform cell offset; beyond the particle's field: 0
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)F, (short)0, (int)((size_t)lv.fmax * lv.fpitch * sizeof(uint32_t)), 0x00020000);
-    const int u = ch * WAVE + lane;                               // the lane's slot
-    const int uu = u < nslot ? u : 0;
-    const int iy = uu / nq, dx = (uu - iy * nq) * 4;
-    const int off = (iy * lv.fpitch + dx) * 4;
-    const int q0 = iy * nx + dx;
-    const int nv = u < nslot ? min(4, nx - dx) : 0;               // valid poses of the slot (the last slot of a row: nx - dx)
-    unsigned lo[4] = {0u, 0u, 0u, 0u}, hi[4] = {0u, 0u, 0u, 0u};
+    const __amdgpu_buffer_rsrc_t rsrc = field_rsrc(lv, p);
+    const Slot sl = slot_of(cube, lv.fpitch, ch * WAVE + lane);   // the lane's slot
+    const int iy = sl.iy, dx = sl.dx, off = sl.off, nv = sl.nv;
+    Acc4 sum4;
 #pragma unroll 4
     for (int k = wave; k < K; k += 4) {
         const int cell = cl[k] * 4;
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, cell, 0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const unsigned s = lo[e] + v[e];
-            hi[e] += s < v[e] ? 1u : 0u;
-            lo[e] = s;
-        }
+        sum4.add(__builtin_amdgcn_raw_buffer_load_b128(rsrc, off, cell, 0));
     }
     if (wave > 0) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) part_s[wave - 1][e * WAVE + lane] = ((unsigned long long)hi[e] << 32) | lo[e];
+        for (int e = 0; e < 4; ++e) part_s[wave - 1][e * WAVE + lane] = sum4.get(e);
     }
     __syncthreads();
     if (wave > 0) return;
-    const double* __restrict__ pr = lv.prior + (size_t)p * 2 * npose;
     const double inv = 1.0 / lv.cost_scale;
     const double M = match[p].best_score;
     const int am = moments_argmax(lv, match, p);
@@ -4698,21 +4609,14 @@ __global__ __launch_bounds__(256) void k_moments(Slam2dLevel lv, int P, int chun
     const double dth = lv.thetas[it] - lv.thetas[ita];
     const double dyv = (double)(iy - iya) * lv.step;
     double prv[4], ptw[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int q = min(q0 + e, npose - 1);
-        prv[e] = pr[q];
-        ptw[e] = pr[npose + q];
-    }
+    slot_priors(lv.prior + (size_t)p * 2 * npose, cube, sl.q0, prv, ptw);
     double s0 = 0.0, sx = 0.0, sy = 0.0, st = 0.0, sxx = 0.0, sxy = 0.0, sxt = 0.0, syy = 0.0, syt = 0.0, stt = 0.0;
     double cnt = 0.0, cnan = 0.0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         if (e < nv) {
-            const unsigned long long acc = (((unsigned long long)hi[e] << 32) | lo[e]) + part_s[0][e * WAVE + lane] +
-                                           part_s[1][e * WAVE + lane] + part_s[2][e * WAVE + lane];
-            const double sum = -((double)acc * inv);
-            const double sc = (sum + prv[e]) + ptw[e];                              // :131, k_sweep's expression
+            const unsigned long long acc = sum4.get(e) + part_s[0][e * WAVE + lane] + part_s[1][e * WAVE + lane] + part_s[2][e * WAVE + lane];
+            const double sc = pose_score(acc, inv, prv[e], ptw[e]);
             const double wgt = exp(sc - M);
             const double dxv = (double)(dx + e - ixa) * lv.step;
             s0 += wgt;
@@ -4748,7 +4652,7 @@ __global__ __launch_bounds__(64) void k_moments_fold(Slam2dLevel lv, int nrows, 
 #pragma unroll
     for (int i = 0; i < MOMENTS_ROW; ++i) acc[i] = wave_sum(acc[i]);
     if (lane != 0) return;
-    const int nx = 2 * lv.ncell + 1, npose = nx * nx;
+    const int nx = cube_of(lv).nx, npose = cube_of(lv).npose;
     const int am = moments_argmax(lv, match, p);
     const int ita = am / npose, rema = am - ita * npose;
     const int iya = rema / nx, ixa = rema - iya * nx;
@@ -4772,6 +4676,10 @@ __global__ __launch_bounds__(64) void k_moments_fold(Slam2dLevel lv, int nrows, 
 // ------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------
+// slots of 4 consecutive dx in a plane of the level's cube, and the chunks of 64 slots (one per lane) k_sweep and k_moments cut it into
+static int cube_slots(const Slam2dLevel& lv) { return cube_of(lv).nslot; }
+static int cube_chunks(const Slam2dLevel& lv) { return cdiv(cube_slots(lv), WAVE); }
+
 static void launch_sweep(const Slam2dLevel& lv, int P, int chunks, hipStream_t s, int mode = 0, const double* sel_est = nullptr,
                          int sel_estride = 0, Slam2dMatch* sel_out = nullptr) {
     const int bpp = lv.ntheta * cdiv(chunks, mode == 2 ? SWEEP_REST_CHUNKS : (mode == 0 ? SWEEP_MAIN_CHUNKS : 1));   // blocks per particle
@@ -4873,18 +4781,18 @@ static int check_field_args(const Slam2dLevel& lv, int P, bool lazy) {
         return SLAM2D_E_BADARG;
     if (lazy && !lv.tileneed) return SLAM2D_E_BADARG;
     if (lv.tmax * lv.tmax > 28000) return SLAM2D_E_TOOLARGE;        // k_tile_triage: 32 passes, 5 bytes of LDS per tile (144 KB)
+    const Cube cube = cube_of(lv);
+    const int nx = cube.nx;
     if (lv.bnb == 3) {                                 // angle bounds: small cubes only, windows of <= 5 x 5 cells
-        const int nx = 2 * lv.ncell + 1;
         if (!lazy || !lv.gmin || !lv.gmin2 || !lv.pcells || !lv.bounds || !lv.bnb_best || !lv.seed_key) return SLAM2D_E_BADARG;
-        if (nx > 5 || nx * ((nx + 3) / 4) > 32 || lv.tmax * 16 != lv.fpitch || lv.ntheta >= (1 << 14)) return SLAM2D_E_BADARG;
+        if (nx > 5 || cube.nslot > 32 || lv.tmax * 16 != lv.fpitch || lv.ntheta >= (1 << 14)) return SLAM2D_E_BADARG;
     } else if (lv.bnb) {
-        const int nx = 2 * lv.ncell + 1;
         if (!lazy || !lv.gmin || !lv.gmin2 || !lv.pcells || !lv.bounds || !lv.tile_pmax || !lv.bnb_best || !lv.prune_state)
             return SLAM2D_E_BADARG;
         if (lv.bnb == 2 && (!lv.gmin3d || !lv.p3cells || !lv.bounds1 || !lv.seed_key || (lv.tmax & 0) != 0)) return SLAM2D_E_BADARG;
         if (nx < 9 || nx > 64 || lv.tmax * 16 != lv.fpitch) return SLAM2D_E_BADARG;
         if (lv.ntheta > SLAM2D_BNB_MAX_THETA) return SLAM2D_E_TOOLARGE;
-        if ((long long)lv.ntheta * ((nx + 3) / 4) * (((nx + 3) / 4 + 3) / 4 * 4) > (long long)XS_THREADS * XS_MAX_PER) return SLAM2D_E_TOOLARGE;
+        if ((long long)lv.ntheta * cube.nbt * cube.nbq4 > (long long)XS_THREADS * XS_MAX_PER) return SLAM2D_E_TOOLARGE;
     }
     return 0;
 }
@@ -4992,7 +4900,7 @@ static BoundLdsPlan bound_lds_plan(const Slam2dLevel& lv, int P) {
     static const int mode = [] { const char* e = getenv("SLAM2D_BOUND_LDS"); return e ? atoi(e) : -1; }();
     BoundLdsPlan pl{};
     if (mode == 0 || lv.bnb != 1 || !lv.gmin2b) return pl;
-    const int nx = 2 * lv.ncell + 1, nbt = (nx + 3) >> 2;
+    const int nbt = cube_of(lv).nbt;
     pl.nset = cdiv(nbt * nbt, WAVE);
     const int gp = lv.tmax << 2, lp = lv.g2b_pitch;
     if (pl.nset > 4 || lv.kmax > 2048 || lp < gp || (lp & 15)) return pl;
@@ -5015,9 +4923,7 @@ static bool launch_bound_lds(const Slam2dLevel& lv, int P, const BoundLdsPlan& p
 
 static int launch_scores(const Slam2dLevel& lv, int P, const double* d_est, int est_stride, const double* d_uniform,
                          Slam2dMatch* d_out, hipStream_t s, int ring_chunks = 0) {
-    const int nx = 2 * lv.ncell + 1;
-    const int nslot = nx * ((nx + 3) / 4);            // slots of 4 consecutive dx
-    const int chunks = cdiv(nslot, WAVE);             // one slot per lane
+    const int nslot = cube_slots(lv), chunks = cube_chunks(lv);
     if (lv.ntheta * chunks > lv.npartial) return SLAM2D_E_BADARG;
     if (ring_chunks > 0) {
         // the prior's ring first (write_priors); the particles it does not settle are swept in full by the
@@ -5069,7 +4975,7 @@ static int launch_scores(const Slam2dLevel& lv, int P, const double* d_est, int 
 // the ring pass; 0 = pruning not applicable.  The ring itself is listed on the device by write_priors.
 static int ring_slot_bound(const Slam2dLevel& lv, double est_dist) {
     if (lv.fine || !lv.ring || !lv.prune_state || lv.ring_cap <= 0 || !(est_dist >= 0.0)) return 0;
-    const int nx = 2 * lv.ncell + 1, nq = (nx + 3) / 4;
+    const int nx = cube_of(lv).nx, nq = cube_of(lv).nq;
     const double slack = 1e-9 * (1.0 + est_dist + lv.step * nx);
     int n = 0;
     for (int iy = 0; iy < nx; ++iy)
@@ -5136,8 +5042,7 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
     int ring_chunks = 0;
     if (options & SLAM2D_MATCH_PRUNE_BY_PRIOR) {
         const int bound = ring_slot_bound(lv, est_moving_dist);
-        const int nx = 2 * lv.ncell + 1, nslot = nx * ((nx + 3) / 4);
-        if (bound > 0 && 2 * bound <= nslot) ring_chunks = cdiv(bound, WAVE);     // worth it only for a thin ring
+        if (bound > 0 && 2 * bound <= cube_slots(lv)) ring_chunks = cdiv(bound, WAVE);     // worth it only for a thin ring
     }
     // Below SLAM2D_BEAM_TABLE_MIN beams k_frame_axis is not launched at all: the endpoint kernel's per-particle block does
     // its work (one launch less per level) and the occupied-cell scatter rides in that launch as well; above, and from
@@ -5182,11 +5087,6 @@ int slam2d_match(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2
     return launch_status();
 }
 
-// slots of 4 consecutive dx in chunks of 64, as launch_scores cuts a plane for k_sweep
-static int moments_chunks(const Slam2dLevel& lv) {
-    const int nx = 2 * lv.ncell + 1;
-    return cdiv(nx * ((nx + 3) / 4), WAVE);
-}
 static int check_moments_level(const Slam2dLevel* lv, int P) {
     if (!lv || P <= 0) return SLAM2D_E_BADARG;
     if (lv->fmax <= 0 || lv->fpitch < lv->fmax || lv->ncell < 0 || lv->ntheta <= 0 || lv->kmax <= 0 || !(lv->cost_scale > 0.0)) return SLAM2D_E_BADARG;
@@ -5199,7 +5099,7 @@ static int check_moments_level(const Slam2dLevel* lv, int P) {
 int64_t slam2d_match_moments_work(const Slam2dLevel* level, int32_t P) {
     const int rc = check_moments_level(level, P);
     if (rc) return rc;
-    return (int64_t)P * level->ntheta * moments_chunks(*level) * MOMENTS_ROW;
+    return (int64_t)P * level->ntheta * cube_chunks(*level) * MOMENTS_ROW;
 }
 
 int slam2d_match_moments(const Slam2dLevel* level, int32_t P, const double* d_est, int32_t est_stride,
@@ -5210,7 +5110,7 @@ int slam2d_match_moments(const Slam2dLevel* level, int32_t P, const double* d_es
     const Slam2dLevel& lv = *level;
     if (!lv.field || !lv.cells || !lv.kcount || !lv.prior || !lv.thetas) return SLAM2D_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
-    const int chunks = moments_chunks(lv);
+    const int chunks = cube_chunks(lv);
     const int bpp = lv.ntheta * chunks;                                 // blocks (= rows of d_work) per particle
     if ((long long)cdiv(P, 8) * 8 * bpp >= (1ll << 31)) return SLAM2D_E_TOOLARGE;
     k_moments<<<(unsigned)cdiv(P, 8) * 8 * bpp, 256, 0, s>>>(lv, P, chunks, bpp, d_match, d_work);

@@ -343,6 +343,44 @@ def test_case9_same_bits_on_every_call(scene_a):
     assert scene_a["rows1"].tobytes() == scene_a["rows1_again"].tobytes()
 
 
+@pytest.mark.parametrize("ncell", [5, 8])
+def test_case11_tile_bounds_without_the_byte_image(pkg, ncell):
+    """A branch-and-bound level without Slam2dLevel.gmin2b is bounded by k_bound (the 32-bit minima, from global memory) instead
+    of k_bound_lds; no other test takes that kernel.  3 particles, 3 angles, 37 beams; ncell = 5: rows of 11 poses, 33 slots in
+    one chunk, the last slot of a row with 3 poses, 3 x 3 pose tiles; ncell = 8: 17 x 17, 85 slots in two chunks, 5 x 5 tiles.
+    Against the oracle: arg-max, pick and pose equal; every pose the match scored within the score bound of yardstick (b),
+    2 K_max / cost_scale + 1e-9; then the moments of the whole cube by both yardsticks."""
+    nx = 2 * ncell + 1
+    sc = _scene(pkg, 3, 37, 14, ((ncell + 0.5) * 2 * UNIT, 0.9 * _astep(37), 2, 0.1, 0.25, 0.3, 0.15, 2), seed=5)
+    pf, eng, P = sc["pf"], sc["eng"], sc["P"]
+    lv = pf.coarse
+    assert (lv.nx, lv.ntheta, lv.c.bnb) == (nx, 3, 1) and lv.c.gmin2b
+    lv.c.gmin2b = None
+    d_est, d_rng = eng.to_device(sc["est"]), eng.to_device(sc["ranges"])
+    d_psi = eng.to_device(np.tile([math.cos(PSI), math.sin(PSI)], (P, 1)))
+    eng.match(lv, d_est, 3, d_rng, DIST, d_psi, None, pf.m_coarse)
+    eng.take_flags()
+    match = eng.read_matches(pf.m_coarse).copy()
+    rows = eng.match_moments(lv, d_est, 3, pf.m_coarse).cpu().numpy()
+    smo = sc["smo"]
+    sr, half, sigma, _, _, _, miss, cf = sc["smP"]
+    for p in range(P):
+        est = sc["est"][p]
+        xr, yr, prob = smo.frameSearchSpace(est[0], est[1], cf * UNIT, sigma / cf, miss)
+        want, cube, _ = smo.searchToMatch(prob, est[0], est[1], est[2], sc["ranges"], xr, yr, sr, half, cf * UNIT, DIST, PSI)
+        am = int(cube.argmax())
+        assert (int(match["argmax"][p]), int(match["pick"][p])) == (am, am)
+        assert (match["x"][p], match["y"][p], match["theta"][p]) == (want["x"], want["y"], want["theta"])
+        dev = lv.cube(p)
+        scored = dev != 0.0                                 # (a fresh level's cube is zero; a score never is)
+        eps = 2 * int(lv.t["kcount"][p].max().item()) / lv.c.cost_scale + 1e-9
+        err = float(np.abs(dev - cube)[scored].max())
+        print(f"case11 ncell {ncell} p{p}: {int(scored.sum())} of {scored.size} poses scored, largest error {err:.3g}, bound {eps:.3g}")
+        assert scored.reshape(-1)[am] and err <= eps
+        _check_a("case11", lv, p, rows[p], match)
+        _check_b("case11", lv, p, rows[p], cube)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # case 10: the public surface
 # ---------------------------------------------------------------------------------------------------------------------
