@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from bound_yardstick import host_bounds as _host_bounds, min2x2 as _min2x2
 from oracle import slam_oracle as so
 
 pytestmark = pytest.mark.gpu
@@ -42,27 +43,6 @@ def _assert_check_launch_folded(lv):
     assert gp * lp <= 160 * 1024 - 512                                   # ... and the image fits a CU's LDS
 
 
-def _host_bounds(lv, p):
-    """The tile bounds of particle p as k_bound_lds takes them, from the byte image as it lies in memory AFTER the scan:
-    U = (-((sum of the image bytes at the angle's cells, shifted to the tile) * 2^24 / scale) + tile_pmax) + 1e-9."""
-    gp, nbt = 4 * lv.tmax, (lv.nx + 3) // 4
-    img = lv.t["gmin2b"][p].cpu().numpy().astype(np.int64)
-    pcells = lv.t["pcells"][p].cpu().numpy()
-    kcount = lv.t["kcount"][p].cpu().numpy()
-    pmax = lv.t["tile_pmax"][p].cpu().numpy()[:, :nbt]
-    inv = 1.0 / lv.c.cost_scale
-    out = np.empty((lv.ntheta, nbt, nbt))
-    for it in range(lv.ntheta):
-        e = pcells[it, :kcount[it]].astype(np.int64) >> 2
-        Y0, X0 = e // gp, e % gp
-        sums = np.zeros((nbt, nbt), dtype=np.int64)
-        for by in range(nbt):
-            for bx in range(nbt):
-                sums[by, bx] = img[Y0 + by, X0 + bx].sum()
-        out[it] = (-((sums.astype(np.float64) * 16777216.0) * inv) + pmax) + 1e-9
-    return out
-
-
 def _config2_filter(pkg, P, world_seed=3):
     """A config-2-shaped filter (0.1 m cells, 34.5 m / 180 beams, 41 x 41 poses per angle, one level) on a synthetic world:
     its coarse level is scored by branch and bound with the bounds' byte image."""
@@ -78,14 +58,6 @@ def _config2_filter(pkg, P, world_seed=3):
     lv = pf.coarse
     _assert_check_launch_folded(lv)
     return pf, world, (unit, R, fov, beams, size_m)
-
-
-def _min2x2(g):
-    """min(g[Y..Y+1][X..X+1]) with the indices clamped to the image, as the device takes it."""
-    gy = np.concatenate([g[1:], g[-1:]], axis=0)
-    m = np.minimum(g, gy)
-    mx = np.concatenate([m[:, 1:], m[:, -1:]], axis=1)
-    return np.minimum(m, mx)
 
 
 def test_device_minima_equal_host_recompute(pkg):
