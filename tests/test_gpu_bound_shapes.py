@@ -101,12 +101,13 @@ def _assert_plan(lv, P, nset, rle):
     return pl
 
 
-def _pair(pkg, P, beams, ncell, half_steps, unit=UNIT, max_range=R_MAX, size_m=SIZE_M):
-    """A branch-and-bound filter and its brute-force twin over P copies of one map; coarse factor 1, search radius
-    (ncell + 0.5) * step, half_steps angular steps of heading to either side."""
+def _pair(pkg, P, beams, ncell, half_steps, unit=UNIT, max_range=R_MAX, size_m=SIZE_M, cf=1, level="coarse"):
+    """A branch-and-bound filter and its brute-force twin over P copies of one map; coarse factor cf (1), search radius
+    (ncell + 0.5) * step, half_steps angular steps of heading to either side.  level: the level the checks look at -- the
+    coarse one of 2 ncell + 1 poses a side, or the fine one behind it (2 cf + 1 poses a side)."""
     world, v, t = _world(size_m, unit)
     ogP = [size_m, size_m, {"x": 0.0, "y": 0.0}, unit, FOV, max_range, beams, WALL]
-    smP = [(ncell + 0.5) * unit, half_steps * FOV / beams, 2, 0.1, 0.25, 0.3, 0.15, 1]
+    smP = [(ncell + 0.5) * unit * cf, half_steps * FOV / beams, 2, 0.1, 0.25, 0.3, 0.15, cf]
     pfs = []
     for bnb in (True, False):
         pf = pkg.ParticleFilter(P, ogP, smP, growable=False, rng=np.random.RandomState(0), bnb=bnb)
@@ -116,8 +117,8 @@ def _pair(pkg, P, beams, ncell, half_steps, unit=UNIT, max_range=R_MAX, size_m=S
     assert pfs[0].coarse.nx == 2 * ncell + 1 == pfs[1].coarse.nx and not pfs[1].coarse.bnb
     ogo = so.GridOracle(size_m, size_m, {"x": 0.0, "y": 0.0}, unit, FOV, beams, max_range, WALL)
     ogo.visited[:], ogo.total[:] = v, t
-    return dict(bnb=pfs[0], twin=pfs[1], lv=pfs[0].coarse, P=P, world=world, unit=unit, max_range=max_range, beams=beams,
-                origin=(-size_m / 2, -size_m / 2), smP=smP, smo=_PairPriorOracle(ogo, *smP))
+    return dict(bnb=pfs[0], twin=pfs[1], lv=getattr(pfs[0], level), level=level, P=P, world=world, unit=unit, max_range=max_range,
+                beams=beams, origin=(-size_m / 2, -size_m / 2), smP=smP, smo=_PairPriorOracle(ogo, *smP))
 
 
 def _estimates(P, s, unit, k):
@@ -149,21 +150,28 @@ def _close_wall_scan(sc, s):
     return 0.4 + 0.05 * np.sin(np.arange(sc["beams"]) * (2 * np.pi / sc["beams"]))
 
 
+_DOWNLOADS = ("bounds", "theta_umax", "gmin2b", "pcells", "kcount", "tile_pmax", "gmin2", "gmin3d", "p3cells", "bounds1", "seed_key",
+              "bnb_best", "prior", "partials")
+
+
 def _match_both(sc, est, ranges, psi, uni):
     """One slam2d_match of the filter and of its twin on the same inputs; everything the checks read, downloaded."""
     out = {}
+    level = sc.get("level", "coarse")
     for name in ("bnb", "twin"):
         pf = sc[name]
-        eng, lv = pf.engine, pf.coarse
+        eng, lv = pf.engine, getattr(pf, level)
+        buf = pf.m_coarse if level == "coarse" else pf.m_fine
         if name == "bnb":
             lv.t["cube"].fill_(UNSCORED)
-        eng.match(lv, eng.to_device(est), 3, eng.to_device(ranges), DIST, eng.to_device(psi),
-                  None if uni is None else eng.to_device(uni), pf.m_coarse)
+        eng.match(lv, eng.to_device(est), 3, eng.to_device(ranges), DIST, None if psi is None else eng.to_device(psi),
+                  None if uni is None else eng.to_device(uni), buf)
         eng.take_flags()
-        out[name] = dict(m=eng.read_matches(pf.m_coarse).copy(), cube=lv.t["cube"].cpu().numpy().copy())
+        out[name] = dict(m=eng.read_matches(buf).copy(), cube=lv.t["cube"].cpu().numpy().copy())
     lv = sc["lv"]
-    for k in ("bounds", "theta_umax", "gmin2b", "pcells", "kcount", "tile_pmax"):
-        out[k] = lv.t[k].cpu().numpy().copy()
+    for k in _DOWNLOADS:                                                 # (whichever of them the level's bound kernels have)
+        if k in lv.t:
+            out[k] = lv.t[k].cpu().numpy().copy()
     return out
 
 
@@ -205,29 +213,46 @@ def _check_scored(tag, sc, out, nan_prior=False):
         assert np.array_equal(cb[p][scored & ~np.isnan(ct[p])].view(np.int64), ct[p][scored & ~np.isnan(ct[p])].view(np.int64))
 
 
-def _check_oracle(tag, sc, out, est, ranges, psi, uni, particles):
-    """Points 3 and 4 (oracle) for the given particles; the draw's pick where uni is given."""
+def _check_oracle(tag, sc, out, est, ranges, psi, uni, particles, tol=None):
+    """Points 3 and 4 (oracle) for the given particles; the draw's pick where uni is given.  The bounds are the level's own:
+    per 4 x 4 tile, or per angle plane behind angle bounds (bnb_levels 3); under two levels a tile cut at level 1 holds -inf
+    by design and is not compared.  tol: the relative bound of the confidence where it is not this cube's n_poses * exp(-30)."""
     lv = sc["lv"]
     smo = sc["smo"]
     sr, half, sigma, _, _, _, miss, cf = sc["smP"]
+    fine = sc.get("level", "coarse") == "fine"
     nbt, n_poses = (lv.nx + 3) // 4, lv.ntheta * lv.nx ** 2
-    tol = n_poses * math.exp(-BNB_MARGIN) + 1e-9
+    if tol is None:
+        tol = n_poses * math.exp(-BNB_MARGIN) + 1e-9
     m = out["bnb"]["m"]
     for p in particles:
         e = est[p]
-        xr, yr, prob = smo.frameSearchSpace(e[0], e[1], cf * sc["unit"], sigma / cf, miss)
         with np.errstate(invalid="ignore"):                              # (the heading as the (cos, sin) pair the device was given)
-            want, cube, conf = smo.searchToMatch(prob, e[0], e[1], e[2], ranges, xr, yr, sr, half, cf * sc["unit"], DIST,
-                                                 (float(psi[p][0]), float(psi[p][1])), fineSearch=False, matchMax=uni is None,
-                                                 uniform=None if uni is None else float(uni[p]))
+            if fine:
+                xr, yr, prob = smo.frameSearchSpace(e[0], e[1], sc["unit"], sigma, miss ** (2 / cf))
+                want, cube, conf = smo.searchToMatch(prob, e[0], e[1], e[2], ranges, xr, yr, cf * sc["unit"], half, sc["unit"], DIST,
+                                                     None, fineSearch=True, matchMax=uni is None,
+                                                     uniform=None if uni is None else float(uni[p]))
+            else:
+                xr, yr, prob = smo.frameSearchSpace(e[0], e[1], cf * sc["unit"], sigma / cf, miss)
+                want, cube, conf = smo.searchToMatch(prob, e[0], e[1], e[2], ranges, xr, yr, sr, half, cf * sc["unit"], DIST,
+                                                     (float(psi[p][0]), float(psi[p][1])), fineSearch=False, matchMax=uni is None,
+                                                     uniform=None if uni is None else float(uni[p]))
         assert cube.shape == (lv.ntheta, lv.nx, lv.nx)
         eps = 2 * int(out["kcount"][p].max()) / lv.c.cost_scale + 1e-9      # (_check_b of tests/test_gpu_moments.py)
-        best, has_nan = yard.tile_max(cube, lv.nx, nbt)
-        U = out["bounds"][p][:, :, :nbt]
-        short = best - eps - U
+        if lv.bnb_levels == 3:
+            flat = cube.reshape(lv.ntheta, -1)
+            has_nan = np.isnan(flat).any(axis=1)
+            best = np.where(np.isnan(flat), -np.inf, flat).max(axis=1)
+            U = out["bounds"][p]
+        else:
+            best, has_nan = yard.tile_max(cube, lv.nx, nbt)
+            U = out["bounds"][p][:, :, :nbt]
+        cut = (U == -np.inf) if lv.bnb_levels == 2 else np.zeros(U.shape, dtype=bool)
+        short = (best - eps - U)[~cut]
         print(f"{tag} p{p}: oracle's tile maxima exceed the bounds by at most {short.max():.3g} (0 allowed, eps {eps:.3g} inside); "
               f"{int(has_nan.sum())} NaN tiles")
-        assert (U >= best - eps).all() and (U[has_nan] == np.inf).all(), f"{tag} p{p}: bounds against the oracle"
+        assert ((U >= best - eps) | cut).all() and (U[has_nan] == np.inf).all(), f"{tag} p{p}: bounds against the oracle"
         am = int(cube.argmax())
         assert int(m["argmax"][p]) == am, f"{tag} p{p}: arg-max"
         pick = am
