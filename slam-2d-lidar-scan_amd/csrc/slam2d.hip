@@ -716,7 +716,10 @@ struct BlurLds {
 
 template <int RAD>
 __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& sm, const int p, const Slam2dFrame& fr,
-                                          const int tby, const int tbx, const int mode, const bool use_flags) {
+                                          const int tby, const int tbx, const int mode, const bool use_flags,
+                                          const bool minmax = true) {
+    // minmax == false (mode 0 only): the caller knows that nobody will read this build's tilemin / tilemax -- the tile's two wave
+    // reductions and their stores are skipped
     const int fh = fr.fh, fw = fr.fw;
     const int ty0 = tby * BLUR_TILE, tx0 = tbx * BLUR_TILE;
     if (ty0 >= fh || tx0 >= fw) return;
@@ -815,7 +818,7 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
     const double* __restrict__ w = lv.blur_w;
     if (!any) {
         const double v = lv.floor_value;
-        if (mode == 0 && tid == 0) {
+        if (mode == 0 && minmax && tid == 0) {
             lv.tilemin[((size_t)p * lv.tmax + tby) * lv.tmax + tbx] = v;
             lv.tilemax[((size_t)p * lv.tmax + tby) * lv.tmax + tbx] = v > thr ? 0.0 : v;
         }
@@ -846,8 +849,9 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
                 // is selected, not multiplied: 0.0 * lw would be -0.0.)
                 double f[8 + 2 * RAD], lw[RAD + 1];
 #pragma unroll
-                for (int k = 0; k < 8 + 2 * RAD; ++k) f[k] = __hiloint2double((int)((uint32_t)sm.occ[g * 8 + k][lx] * 0x3FF00000u), 0);     // 1 = free -> 1.0 (a
-                    // v_cvt_f64_u32 here costs the kernel 17 VGPRs and a third of its waves)
+                for (int k = 0; k < 8 + 2 * RAD; ++k) f[k] = __hiloint2double(sm.occ[g * 8 + k][lx] ? 0x3FF00000 : 0, 0);     // 1 = free -> 1.0 (a
+                    // v_cvt_f64_u32 here costs the kernel 17 VGPRs and a third of its waves; a multiply by 0x3FF00000 is a quarter-rate
+                    // v_mul_lo_u32 per value)
 #pragma unroll
                 for (int j = 0; j <= RAD; ++j) lw[j] = L * w[j];
 #pragma unroll
@@ -928,7 +932,7 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
         }
     }
     DBG_CLOCK(53, dbg);
-    if (mode == 0) {
+    if (mode == 0 && minmax) {
         lmin = wave64_min(lmin); lmax = wave64_max(lmax);       // (a ds_bpermute butterfly here was ~1 us of the tile's ~4.5)
         if (tid == 0) {                                // reduced by k_blur_check_redo
             lv.tilemin[((size_t)p * lv.tmax + tby) * lv.tmax + tbx] = lmin;
@@ -1132,13 +1136,22 @@ __global__ __launch_bounds__(BLUR_THREADS, BLUR_MIN_WAVES) void k_blur_clamp(Sla
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int p = (slot / bpp) * 8 + xcd, first = slot % bpp;
     if (p >= P) return;
-    const int n = lv.tilecount[2 * p];
-    if (first >= n) return;
-    const Slam2dFrame fr = lv.frames[p];
+    // the block's first list entry and the frame are requested with the count, not behind it (each a round trip to what the
+    // triage has just written); the entry may be a stale one (first >= n: slot `first` clamped into the particle's lists) and
+    // is used only when it is not.  What the tiles need of the frame: its size and min_known.  (The empty asm is the values'
+    // first use: without it the compiler sinks the loads behind the count's branch.)
     const int* list = lv.tilelist + (size_t)p * 2 * lv.tmax * lv.tmax;
+    int t0 = list[min(first, 2 * lv.tmax * lv.tmax - 1)];
+    Slam2dFrame fr = lv.frames[p];
+    int n = lv.tilecount[2 * p];
+    asm volatile("" : "+s"(t0), "+s"(fr.fh), "+s"(fr.fw), "+s"(fr.min_known), "+s"(n));      // (all four arrive with one wait)
+    if (first >= n) return;
+    // the per-tile minima and maxima have two readers: blur_check_tail below (a frame without a free tile) and k_blur_check_redo,
+    // which is not launched where tail != 0
+    const bool minmax = !(tail && fr.min_known);
     for (int b = first; b < n; b += bpp) {
-        const int t = list[b];
-        blur_tile<RAD>(lv, sm, p, fr, t / lv.tmax, t % lv.tmax, 0, false);
+        const int t = b == first ? t0 : list[b];
+        blur_tile<RAD>(lv, sm, p, fr, t / lv.tmax, t % lv.tmax, 0, false, minmax);
     }
     if (tail && !fr.min_known) {                       // (block-uniform; rare)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                       // this wave's per-tile minima leave the XCD's L2
@@ -2510,9 +2523,21 @@ __device__ __forceinline__ void bound_refresh_frame(const uint32_t* __restrict__
         bound_refresh_entry(G, G2, G2B, g2s, gp, lp, Y, X, writer);
     }
 }
-template <int NSET, bool RLE>
+//
+// HOIST (short lists, NSET <= 2: the wider instantiations spill with it): what a wave's FIRST angle reads from the lists k_endpoints
+// wrote -- kcount, its lane's entry of pcells, the head of cells that the seed's prefetch covers (BL_HEAD entries), and bnb_best --
+// has addresses known at the kernel's first instruction, and each is a first touch of another kernel's data: a round trip of its
+// own where it stood (behind the staging barrier, one after the other).  They are issued ahead of the staging loads instead and
+// travel with the image.  Nothing waits for K: the rows of pcells and cells are kmax long, so the index is clamped to the row and
+// the `k < K` masks are applied when K has arrived.  The list head waits in a slot of BL_HEAD words per wave behind the image
+// (held in registers across the loop it spills); the seed reads it back as k_exact_select reads its staged lists.  bnb_best read
+// early is an older value: by the rule above it can only let more seeds be scored, the final maximum is the same.  A wave's later
+// angles (64 particles per launch and more) load as before.
+#define BL_HEAD 256
+template <int NSET, bool RLE, bool HOIST = false>
 __global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int bpp, int tpb, int refresh) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char g2s[];                  // [gp][lp] (+ RLE: [waves][64] words)
+    static_assert(!HOIST || (!RLE && NSET <= 2), "the hoisted form exists for short lists and one or two tile sets");
+    extern __shared__ __attribute__((aligned(16))) unsigned char g2s[];                  // [gp][lp] (+ RLE: [waves][64] words; HOIST: [waves][BL_HEAD] words)
     const int lp = lv.g2b_pitch;
     const int b = blockIdx.x;
     int p, part;
@@ -2522,6 +2547,25 @@ __global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int b
     const int nbt = cube_of(lv).nbt, nbq4 = cube_of(lv).nbq4;
     const int gp = lv.tmax << 2;
     DBG_CLOCK(0, b == 0);
+    // angles from the middle of the block's range outwards: the first round (which finds lv.bnb_best[p] at -inf and scores every
+    // seed) then holds the angles nearest the estimate's, where a tracked pose has its maximum
+    const int it0 = part * tpb, it_end = min(lv.ntheta, it0 + tpb);
+    const int nth = it_end - it0, mid = (nth - 1) >> 1;
+    auto angle_of = [&](const int j) -> int { return it0 + mid + ((j & 1) ? ((j + 1) >> 1) : -((j + 1) >> 1)); };
+    int hK = 0, hcv = 0, hcl[BL_HEAD / WAVE] = {};
+    unsigned long long hbest = 0ull;
+    if constexpr (HOIST) {                                  // the first angle's loads (see above): in flight with the image
+        if (w < nth && lv.kmax > 0) {
+            const size_t row = (size_t)p * lv.ntheta + angle_of(w);
+            const int* __restrict__ pcl = lv.pcells + row * lv.kmax;
+            const int* __restrict__ cl = lv.cells + row * lv.kmax;
+            hK = lv.kcount[row];
+            hcv = pcl[min(lane, lv.kmax - 1)];
+            hbest = __hip_atomic_load(&lv.bnb_best[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int i = 0; i < BL_HEAD / WAVE; ++i) hcl[i] = cl[min(lane + WAVE * i, lv.kmax - 1)];
+        }
+    }
     // the refresh's chain starts ahead of the staging loads (refresh, and hence every branch on it, is uniform over the launch)
     // -- tile counts, then this thread's tile of the lists: in flight with the image
     const int ntile = lv.tmax * lv.tmax;
@@ -2544,6 +2588,11 @@ __global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int b
 #pragma unroll
             for (int k = 0; k < 4; ++k) if (i + k * nt < n16) dst[i + k * nt] = v[k];
         }
+    }
+    int* const head_s = reinterpret_cast<int*>(g2s + (((size_t)gp * lp + 15) & ~(size_t)15)) + w * BL_HEAD;      // (HOIST: this wave's slot)
+    if constexpr (HOIST) {
+#pragma unroll
+        for (int i = 0; i < BL_HEAD / WAVE; ++i) head_s[lane + WAVE * i] = hcl[i];
     }
     DBG_CLOCK(1, b == 0);
     if (refresh) {                                          // the bound minima of the tiles written at this build (see above)
@@ -2583,28 +2632,29 @@ __global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int b
 #pragma unroll
     for (int s = 0; s < NSET; ++s) pmx[s] = valid[s] ? pm[(tslot[s] >> 8) * nbq4 + (tslot[s] & 255)] : -INFINITY;
     const unsigned magic = (unsigned)((0x100000000ull + (unsigned)gp - 1u) / (unsigned)gp);      // e / gp = umulhi(e, magic), e < 2^32 / gp
-    const int it0 = part * tpb, it_end = min(lv.ntheta, it0 + tpb);
     __syncthreads();
+    // (the hoisted values are first USED here: without this the compiler moves conv()'s shift up to the load and waits for it
+    // in front of the staging loads)
+    if constexpr (HOIST) asm volatile("" : "+v"(hK), "+v"(hcv));
     DBG_CLOCK(2, b == 0);
-    // angles from the middle of the block's range outwards: the first round (which finds lv.bnb_best[p] at -inf and scores every
-    // seed) then holds the angles nearest the estimate's, where a tracked pose has its maximum
-    const int nth = it_end - it0, mid = (nth - 1) >> 1;
     double seedU = -INFINITY;
     int seedT = INT_MAX, seedIt = 0, seedK = 0;
     for (int j = w; j < nth; j += nw) {
-        const int it = it0 + mid + ((j & 1) ? ((j + 1) >> 1) : -((j + 1) >> 1));
-        const int K = lv.kcount[p * lv.ntheta + it];
+        const int it = angle_of(j);
+        const bool hoisted = HOIST && j == w && lv.kmax > 0;        // (wave-uniform)
+        const int K = hoisted ? hK : lv.kcount[p * lv.ntheta + it];
         const int* __restrict__ pcl = lv.pcells + ((size_t)p * lv.ntheta + it) * lv.kmax;
         unsigned sum[NSET];
 #pragma unroll
         for (int s = 0; s < NSET; ++s) sum[s] = 0u;
         // a cell's byte offset into gmin2 ((Y0 gp + X0) 4) -> into the LDS image (Y0 lp + X0); beyond the list: offset 0
-        auto conv = [&](const int k) -> int {
+        auto conv_of = [&](const int k, const int raw) -> int {
             if (k >= K) return 0;
-            const unsigned e = (unsigned)pcl[k] >> 2, Y0 = __umulhi(e, magic);
+            const unsigned e = (unsigned)raw >> 2, Y0 = __umulhi(e, magic);
             return (int)(Y0 * (unsigned)lp + (e - Y0 * (unsigned)gp));
         };
-        int cv = conv(lane);
+        auto conv = [&](const int k) -> int { return k >= K ? 0 : conv_of(k, pcl[k]); };
+        int cv = hoisted ? conv_of(lane, hcv) : conv(lane);
         for (int base = 0; base < K; base += WAVE) {
             const int cur = cv;
             if (base + WAVE < K) cv = conv(base + WAVE + lane);
@@ -2687,9 +2737,22 @@ __global__ __launch_bounds__(1024) void k_bound_lds(Slam2dLevel lv, int P, int b
             if (me.v > seedU || seedT == INT_MAX) { seedU = me.v; seedT = me.i; seedIt = it; seedK = K; }
             continue;
         }
-        const unsigned long long best = __hip_atomic_load(&lv.bnb_best[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long best = hoisted ? hbest : __hip_atomic_load(&lv.bnb_best[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (!(me.v > unorder_bits(best))) continue;                         // (wave-uniform; bounds are never NaN: tile_pmax maps NaN to +inf)
-        bound_seed_exact(lv, p, me.i >> 8, me.i & 255, lv.cells + ((size_t)p * lv.ntheta + it) * lv.kmax, K, inv);
+        const int* __restrict__ cl = lv.cells + ((size_t)p * lv.ntheta + it) * lv.kmax;
+        if constexpr (HOIST) {
+            int pre[16];
+            if (hoisted) {                                                  // tile_prefetch<16>, from the wave's slot
+                const int sl = lane & 15;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) pre[i] = sl + 16 * i < K ? head_s[sl + 16 * i] * 4 : 0x7ffffff0;
+            } else {
+                tile_prefetch<16>(cl, K, pre);
+            }
+            tile_seed<16>(lv, p, me.i >> 8, me.i & 255, cl, K, inv, pre);
+        } else {
+            bound_seed_exact(lv, p, me.i >> 8, me.i & 255, cl, K, inv);
+        }
         DBG_CLOCK(5, b == 0 && j == 0);
     }
     if (RLE && seedT != INT_MAX) {
@@ -4717,20 +4780,20 @@ static bool grant_dynamic_lds(const void* kernel, size_t (&granted)[64], size_t 
 }
 // How k_bound_lds runs at a level (bound_lds_plan): ok = it does -- every condition of its launch, the dynamic-LDS grant included,
 // was evaluated when the plan was made, so whoever reads the plan (the field build's fold, the launch) sees one decision.
-struct BoundLdsPlan { bool ok; int nset; bool rle; int bpp, tpb, nw; size_t lds; };
+struct BoundLdsPlan { bool ok; int nset; bool rle; int bpp, tpb, nw; size_t lds; bool hoist; };      // hoist: the form with a list-head slot per wave
 // one instantiation of k_bound_lds: its LDS granted (launch == false: that is all; false: not granted), then launched
-template <int NSET, bool RLE>
+template <int NSET, bool RLE, bool HOIST = false>
 static bool bound_lds_as(const Slam2dLevel& lv, int P, const BoundLdsPlan& pl, bool launch, int refresh, hipStream_t s) {
     static size_t granted[64] = {};
-    if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_bound_lds<NSET, RLE>), granted, pl.lds)) return false;
-    if (launch) k_bound_lds<NSET, RLE><<<(unsigned)cdiv(P, 8) * 8 * pl.bpp, WAVE * pl.nw, pl.lds, s>>>(lv, P, pl.bpp, pl.tpb, refresh);
+    if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_bound_lds<NSET, RLE, HOIST>), granted, pl.lds)) return false;
+    if (launch) k_bound_lds<NSET, RLE, HOIST><<<(unsigned)cdiv(P, 8) * 8 * pl.bpp, WAVE * pl.nw, pl.lds, s>>>(lv, P, pl.bpp, pl.tpb, refresh);
     return true;
 }
 static bool bound_lds_dispatch(const Slam2dLevel& lv, int P, const BoundLdsPlan& pl, bool launch, int refresh, hipStream_t s) {
     switch ((pl.nset - 1) * 2 + (pl.rle ? 1 : 0)) {
-        case 0: return bound_lds_as<1, false>(lv, P, pl, launch, refresh, s);
+        case 0: return pl.hoist ? bound_lds_as<1, false, true>(lv, P, pl, launch, refresh, s) : bound_lds_as<1, false>(lv, P, pl, launch, refresh, s);
         case 1: return bound_lds_as<1, true>(lv, P, pl, launch, refresh, s);
-        case 2: return bound_lds_as<2, false>(lv, P, pl, launch, refresh, s);
+        case 2: return pl.hoist ? bound_lds_as<2, false, true>(lv, P, pl, launch, refresh, s) : bound_lds_as<2, false>(lv, P, pl, launch, refresh, s);
         case 3: return bound_lds_as<2, true>(lv, P, pl, launch, refresh, s);
         case 4: return bound_lds_as<3, false>(lv, P, pl, launch, refresh, s);
         case 5: return bound_lds_as<3, true>(lv, P, pl, launch, refresh, s);
@@ -4913,6 +4976,12 @@ static BoundLdsPlan bound_lds_plan(const Slam2dLevel& lv, int P) {
     const int rounds = cdiv(pl.tpb, 16);
     pl.nw = cdiv(pl.tpb, rounds);
     pl.lds = image + (pl.rle ? (size_t)pl.nw * WAVE * sizeof(unsigned) : 0);
+    if (!pl.rle && pl.nset <= 2) {                              // the first angle's loads hoisted: a list-head slot per wave behind the image
+        BoundLdsPlan hp = pl;
+        hp.hoist = true;
+        hp.lds = image + (size_t)pl.nw * BL_HEAD * sizeof(int);
+        if (bound_lds_dispatch(lv, P, hp, false, 0, nullptr)) { hp.ok = true; return hp; }
+    }                                                           // (not granted with the slots: the same kernel without them)
     pl.ok = bound_lds_dispatch(lv, P, pl, false, 0, nullptr);      // (the grant alone)
     return pl;
 }
