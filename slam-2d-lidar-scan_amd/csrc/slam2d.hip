@@ -414,18 +414,140 @@ __device__ __forceinline__ void store_match(const Slam2dLevel& lv, const int p, 
 }
 
 // ------------------------------------------------------------------------------------
+// The scan front end: what lies between "a pose and a scan" and "the cell lists and the occupied field"
+// (Utils/ScanMatcher_OGBased.py:21-37,81-89,173-176), stated once for the kernels that need it -- a beam's angle, the
+// field frame, the field index of a map column / row, occupied map bits to occupied field bytes, np.unique's hash set.
+// ------------------------------------------------------------------------------------
+// np.linspace(theta - fov/2, theta + fov/2, num=B) (:82-83): the last sample is the end point itself, num == 1 gives the start.
+// check_level refuses fewer than 2 beams on the match and sweep paths, so in k_frame_axis and k_endpoints the one-beam case
+// changes nothing reachable; it is settled per fan, not in angle(), where it cost k_endpoints<192> a second copy of its cos / sin.
+struct BeamFan {
+    double a0, alast, astep;           // alast: the sample of beam B - 1
+    int B;
+    __device__ __forceinline__ double angle(const int b) const { return (b == B - 1) ? alast : (double)b * astep + a0; }
+};
+__device__ __forceinline__ BeamFan fan_of(const Slam2dLidar& lid, const double theta) {
+    const double a0 = theta - lid.fov / 2, a1 = theta + lid.fov / 2;
+    return BeamFan{a0, lid.beams == 1 ? a0 : a1, (a1 - a0) / (double)(lid.beams - 1), lid.beams};
+}
+
+// The field frame around (ex, ey) (:22-25): its edges and its size in cells before any clamp
+struct FrameExtent { double xlo, xhi, ylo, yhi; int fw, fh; };
+__device__ __forceinline__ FrameExtent frame_extent(const Slam2dLevel& lv, const double ex, const double ey) {
+    FrameExtent e;
+    e.xlo = ex - lv.reach; e.xhi = ex + lv.reach;              // :22-23
+    e.ylo = ey - lv.reach; e.yhi = ey + lv.reach;
+    e.fw = (int)((e.xhi - e.xlo) / lv.step) + 1;                // :24-25
+    e.fh = (int)((e.yhi - e.ylo) / lv.step) + 1;
+    return e;
+}
+// The size of a frame record another call wrote, clipped to the slot: a frame is at most fmax x fmax, so whatever the
+// record holds, no access leaves the slot's image
+struct FieldSize { int fw, fh; };
+__device__ __forceinline__ FieldSize frame_clip(const Slam2dLevel& lv, const Slam2dFrame& fr) {
+    return FieldSize{min(fr.fw, min(lv.fmax, lv.fpitch)), min(fr.fh, lv.fmax)};
+}
+// What one thread per particle does at the start of a scan: the frame record, the per-scan counters, the frame's flags
+__device__ __forceinline__ void frame_publish(const Slam2dLevel& lv, const int p, const Slam2dFrame& fr, const uint32_t f, uint32_t* flags) {
+    lv.frames[p] = fr;
+    lv.tilecount[2 * p] = 0; lv.tilecount[2 * p + 1] = 0;
+    if (lv.bnb) lv.bnb_best[p] = order_bits(-INFINITY);
+    if (lv.bnb >= 2) lv.seed_key[p] = 0ull;
+    if (f) atomicOr(&flags[p], f);
+}
+
+// The field index of a map column / row (:32-37) from q = its (coordinate - frame edge) / step truncated as astype(int) has
+// it; -1: the cell is dropped (the frame's owner raises SLAM2D_F_FIELD_INDEX).  How q is divided is the caller's choice.
+__device__ __forceinline__ int axis_index(int q, const int dim) {
+    if (q < 0) q += dim;                           // Python negative-index wrap (:37)
+    return (q < 0 || q >= dim) ? -1 : q;
+}
+
+// Entry j of particle p's axis table -- axis 0: axis_x, the window's columns; 1: axis_y, its rows -- by the true division
+// (astype(int): truncation toward zero); false where the index is out of range
+__device__ __forceinline__ int axis_length(const Slam2dFrame& fr, const int axis) { return axis == 0 ? fr.mx1 - fr.mx0 : fr.my1 - fr.my0; }
+__device__ __forceinline__ bool axis_table_store(const Slam2dLevel& lv, const Slam2dMap& m, const Slam2dFrame& fr, const int p,
+                                                 const int axis, const int j) {
+    const double d = axis == 0 ? m.X[fr.mx0 + j] - fr.xlo : m.Y[fr.my0 + j] - fr.ylo;
+    const int idx = axis_index((int)(d / lv.step), axis == 0 ? fr.fw : fr.fh);
+    (axis == 0 ? lv.axis_x : lv.axis_y)[(size_t)p * lv.wmax + j] = idx;
+    return idx >= 0;
+}
+
+// np.unique (:120) through a hash set of cell keys in LDS (hmask + 1 slots, a power of two, INT_MAX = empty, load factor
+// <= 2/3 so that an empty slot ends every probe): inserts key, gives its slot, and says whether this call was the first.
+__device__ __forceinline__ bool cell_set_insert(int* hkey, const int hmask, const int key, int& slot) {
+    int h = (int)(((unsigned)key * 2654435761u) >> 7) & hmask;
+    for (;;) {
+        const int prev = atomicCAS(&hkey[h], INT_MAX, key);
+        if (prev == INT_MAX || prev == key) { slot = h; return prev == INT_MAX; }
+        h = (h + 1) & hmask;
+    }
+}
+// k_endpoints' hash set: a power of two >= 1.5 * beams, 512 at least (its LDS size is part of the launch).  No loop: as
+// `while (h < n) h <<= 1` here k_endpoints<256> took 36 bytes of scratch per lane, not 20, and <192> a third spilled SGPR.
+__host__ __device__ __forceinline__ int endpoints_hash_size(const int beams) {
+    const int n = beams + (beams >> 1);
+    return n <= 512 ? 512 : 1 << (32 - __builtin_clz(n - 1));
+}
+
+// Occupied map bits -> occupied field bytes and 8 x 8 block flags (:29-37) by one wave: lane = word w0 + lane of NR map rows
+// (words[k]; fy[k]: the row's field row, wave-uniform, or -1), ax_s: the field column of every window column.  The bits of a
+// non-zero word are handled by 32 lanes at once (two words per step), so a horizontal wall -- words with up to 32 bits set --
+// costs one step, not 32 serial iterations of one lane.  Buffer stores: the row's byte offset rides in the scalar offset, the
+// column in the lane's -- no 64-bit address arithmetic per set bit (the launch is bound by its vector instructions).
+template <int NR>
+__device__ __forceinline__ void scatter_expand(const Slam2dLevel& lv, const int p, const Slam2dFrame& fr, const int w0, const int lane,
+                                               const uint32_t (&words)[NR], const int (&fy)[NR], const int32_t* ax_s) {
+    const int col_base = (w0 + lane) << 5;
+    uint32_t edge = ~0u;
+    if (col_base < fr.mx0) edge &= ~0u << (fr.mx0 - col_base);                    // window edges
+    if (col_base + 32 > fr.mx1) edge &= ~0u >> (col_base + 32 - fr.mx1);
+    const int fpad = flag_pitch(lv);
+    const __amdgpu_buffer_rsrc_t ro = image_rsrc(lv.occ + (size_t)p * lv.fmax * lv.fpitch, (size_t)lv.fmax * lv.fpitch);
+    const __amdgpu_buffer_rsrc_t rt = image_rsrc(lv.tilemask + (size_t)p * flag_bytes(lv), flag_bytes(lv));   // flags of 8 x 8-cell blocks, [2 tmax][flag_pitch]
+    const uint8_t stamp = occ_stamp(lv);
+    const int half = lane >> 5, bit = lane & 31;
+    const int lbase = (w0 << 5) + bit - fr.mx0;            // the lane's column of word w0, relative to the window
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        const uint32_t word = words[k] & edge;
+        unsigned long long nz = __ballot(word != 0u);
+        if (!nz) continue;
+        if (fy[k] < 0) continue;                                                   // :36-37
+        const int so = fy[k] * lv.fpitch, st = (fy[k] >> FLAG_SHIFT) * fpad;       // (wave-uniform)
+        while (nz) {
+            const int sa = __ffsll((long long)nz) - 1;
+            nz &= nz - 1;
+            int sb = -1;
+            if (nz) { sb = __ffsll((long long)nz) - 1; nz &= nz - 1; }
+            // (sa, sb are wave-uniform: v_readlane, not a ds_bpermute round trip per step)
+            const uint32_t wa = (uint32_t)__builtin_amdgcn_readlane((int)word, sa), wb = sb >= 0 ? (uint32_t)__builtin_amdgcn_readlane((int)word, sb) : 0u;
+            const uint32_t wsel = half ? wb : wa;
+            const int src = half ? sb : sa;
+            if ((wsel >> bit) & 1u) {
+                const int fx = ax_s[lbase + (src << 5)];
+                if (fx >= 0) {
+                    __builtin_amdgcn_raw_buffer_store_b8(stamp, ro, fx, so, 0);
+                    __builtin_amdgcn_raw_buffer_store_b8(stamp, rt, fx >> FLAG_SHIFT, st, 0);
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // K2a  frame geometry                      (Utils/ScanMatcher_OGBased.py:21-28)
 // ------------------------------------------------------------------------------------
 // Frame geometry of one particle (every thread of k_frame_axis evaluates it redundantly: a few fp64
 // operations are cheaper than a kernel boundary).
 __device__ __forceinline__ Slam2dFrame make_frame(const Slam2dLidar& lid, const Slam2dLevel& lv, const Slam2dMap& m,
                                                   const double ex, const double ey, uint32_t& f) {
+    const FrameExtent e = frame_extent(lv, ex, ey);
     Slam2dFrame fr;
     fr.cx = ex; fr.cy = ey;
-    fr.xlo = ex - lv.reach; fr.xhi = ex + lv.reach;            // :22-23
-    fr.ylo = ey - lv.reach; fr.yhi = ey + lv.reach;
-    int fw = (int)((fr.xhi - fr.xlo) / lv.step) + 1;            // :24-25
-    int fh = (int)((fr.yhi - fr.ylo) / lv.step) + 1;
+    fr.xlo = e.xlo; fr.xhi = e.xhi; fr.ylo = e.ylo; fr.yhi = e.yhi;
+    int fw = e.fw, fh = e.fh;
     f = 0;
     if (fw > lv.fmax) { fw = lv.fmax; f |= SLAM2D_F_FIELD_INDEX; }
     if (fh > lv.fmax) { fh = lv.fmax; f |= SLAM2D_F_FIELD_INDEX; }
@@ -458,11 +580,10 @@ __global__ void k_frame_axis(Slam2dLidar lid, Slam2dLevel lv, const Slam2dMap* _
         // particle would otherwise each evaluate the same cos / sin (a third of its time at 1081 beams x 139 angles)
         const double ex = centre[(size_t)p * cstride], ey = centre[(size_t)p * cstride + 1], eth = centre[(size_t)p * cstride + 2];
         const int B = lid.beams;
-        const double a0 = eth - lid.fov / 2, a1 = eth + lid.fov / 2;       // np.linspace(theta - fov/2, theta + fov/2, num=B) (:82-83)
-        const double astep = (a1 - a0) / (double)(B - 1);
+        const BeamFan fan = fan_of(lid, eth);
         for (int b = j; b < B; b += gridDim.x * blockDim.x) {
             const double rg = ranges[b];
-            const double a = (b == B - 1) ? a1 : (double)b * astep + a0;
+            const double a = fan.angle(b);
             lv.beam_xy[((size_t)p * B + b) * 2] = ex + cos(a) * rg;                              // :87
             lv.beam_xy[((size_t)p * B + b) * 2 + 1] = ey + sin(a) * rg;                          // :88
         }
@@ -470,22 +591,8 @@ __global__ void k_frame_axis(Slam2dLidar lid, Slam2dLevel lv, const Slam2dMap* _
     const Slam2dMap m = maps[p];
     uint32_t f;
     const Slam2dFrame fr = make_frame(lid, lv, m, centre[(size_t)p * cstride], centre[(size_t)p * cstride + 1], f);
-    if (j == 0 && axis == 0) {
-        lv.frames[p] = fr;
-        lv.tilecount[2 * p] = 0; lv.tilecount[2 * p + 1] = 0;
-        if (lv.bnb) lv.bnb_best[p] = order_bits(-INFINITY);
-        if (lv.bnb >= 2) lv.seed_key[p] = 0ull;
-        if (f) atomicOr(&flags[p], f);
-    }
-    const int n = axis == 0 ? fr.mx1 - fr.mx0 : fr.my1 - fr.my0;
-    if (j >= n) return;
-    const double coord = axis == 0 ? m.X[fr.mx0 + j] : m.Y[fr.my0 + j];
-    const double lo = axis == 0 ? fr.xlo : fr.ylo;
-    const int dim = axis == 0 ? fr.fw : fr.fh;
-    int idx = (int)((coord - lo) / lv.step);       // astype(int): truncation toward zero
-    if (idx < 0) idx += dim;                       // Python negative-index wrap (:37)
-    if (idx < 0 || idx >= dim) { idx = -1; atomicOr(&flags[p], SLAM2D_F_FIELD_INDEX); }
-    (axis == 0 ? lv.axis_x : lv.axis_y)[(size_t)p * lv.wmax + j] = idx;
+    if (j == 0 && axis == 0) frame_publish(lv, p, fr, f, flags);
+    if (j < axis_length(fr, axis) && !axis_table_store(lv, m, fr, p, axis, j)) atomicOr(&flags[p], SLAM2D_F_FIELD_INDEX);
 }
 
 // ------------------------------------------------------------------------------------
@@ -497,9 +604,7 @@ __global__ void k_frame_axis(Slam2dLidar lid, Slam2dLevel lv, const Slam2dMap* _
 // One thread = one 32-cell word of the map window.
 #define SCATTER_ROWS 32
 __global__ __launch_bounds__(256) void k_occ_scatter(Slam2dLevel lv, const Slam2dMap* __restrict__ maps) {
-    // wave = threadIdx.y walks 8 rows of the map window; lane = one 32-cell word of the row.  The bits
-    // of a non-zero word are handled by 32 lanes at once (two words per step), so a horizontal wall --
-    // words with up to 32 bits set -- costs one step, not 32 serial iterations of one lane.
+    // wave = threadIdx.y walks 8 rows of the map window; lane = one 32-cell word of the row (scatter_expand)
     const int p = blockIdx.z;
     const Slam2dFrame fr = lv.frames[p];
     const int nrow = fr.my1 - fr.my0;
@@ -514,10 +619,9 @@ __global__ __launch_bounds__(256) void k_occ_scatter(Slam2dLevel lv, const Slam2
     // the field column of every window column is staged in LDS and the rows' field indices are loaded with
     // the words: the expansion loop below then has no global load in its dependency chain
     extern __shared__ int32_t ax_s[];
-    const int ncol = fr.mx1 - fr.mx0;
     {
         const int32_t* __restrict__ ax = lv.axis_x + (size_t)p * lv.wmax;
-        for (int j = wave * 64 + lane; j < ncol; j += 256) ax_s[j] = ax[j];
+        for (int j = wave * 64 + lane; j < axis_length(fr, 0); j += 256) ax_s[j] = ax[j];
     }
     uint32_t words[NR];
     int fyk[NR];
@@ -528,49 +632,16 @@ __global__ __launch_bounds__(256) void k_occ_scatter(Slam2dLevel lv, const Slam2
         fyk[k] = i < nrow ? lv.axis_y[(size_t)p * lv.wmax + i] : -1;
     }
     __syncthreads();
-    const int col_base = w << 5;
-    uint32_t edge = ~0u;
-    if (col_base < fr.mx0) edge &= ~0u << (fr.mx0 - col_base);                    // window edges
-    if (col_base + 32 > fr.mx1) edge &= ~0u >> (col_base + 32 - fr.mx1);
-    const int fpad = flag_pitch(lv);
-    const __amdgpu_buffer_rsrc_t ro = image_rsrc(lv.occ + (size_t)p * lv.fmax * lv.fpitch, (size_t)lv.fmax * lv.fpitch);
-    const __amdgpu_buffer_rsrc_t rt = image_rsrc(lv.tilemask + (size_t)p * flag_bytes(lv), flag_bytes(lv));   // flags of 8 x 8-cell blocks, [2 tmax][flag_pitch]
-    const uint8_t stamp = occ_stamp(lv);
-    const int half = lane >> 5, bit = lane & 31;
-    const int lbase = (w0 << 5) + bit - fr.mx0;            // the lane's column of word w0, relative to the window
 #pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const uint32_t word = words[k] & edge;
-        unsigned long long nz = __ballot(word != 0u);
-        if (!nz) continue;
-        const int fy = __builtin_amdgcn_readfirstlane(fyk[k]);                     // (the wave's row: uniform)
-        if (fy < 0) continue;                                                      // :36-37
-        const int so = fy * lv.fpitch, st = (fy >> FLAG_SHIFT) * fpad;
-        while (nz) {
-            const int sa = __ffsll((long long)nz) - 1;
-            nz &= nz - 1;
-            int sb = -1;
-            if (nz) { sb = __ffsll((long long)nz) - 1; nz &= nz - 1; }
-            // (sa, sb are wave-uniform: v_readlane, not a ds_bpermute round trip per step)
-            const uint32_t wa = (uint32_t)__builtin_amdgcn_readlane((int)word, sa), wb = sb >= 0 ? (uint32_t)__builtin_amdgcn_readlane((int)word, sb) : 0u;
-            const uint32_t wsel = half ? wb : wa;
-            const int src = half ? sb : sa;
-            if ((wsel >> bit) & 1u) {
-                const int fx = ax_s[lbase + (src << 5)];
-                if (fx >= 0) {                                                     // (buffer stores: see scatter_role)
-                    __builtin_amdgcn_raw_buffer_store_b8(stamp, ro, fx, so, 0);
-                    __builtin_amdgcn_raw_buffer_store_b8(stamp, rt, fx >> FLAG_SHIFT, st, 0);
-                }
-            }
-        }
-    }
+    for (int k = 0; k < NR; ++k) fyk[k] = __builtin_amdgcn_readfirstlane(fyk[k]);  // (the wave's row: uniform)
+    scatter_expand<NR>(lv, p, fr, w0, lane, words, fyk, ax_s);
 }
 
 // k_occ_scatter's work as a block role of k_endpoints' launch (slam2d_match below 512 beams, where no k_frame_axis
 // precedes it): the block derives the frame itself and evaluates the field index of its columns / rows inline (:32-37)
 // instead of reading the axis tables the frame block of the same launch is still writing.  Block (sbx, sby) of NW waves:
-// wave = 8 rows of the map window, lane = one 32-cell word.  Out-of-range indices are skipped here and flagged by the
-// frame block.
+// wave = SCATTER_ROLE_NR rows of the map window, lane = one 32-cell word.  Out-of-range indices are skipped here and
+// flagged by the frame block.
 #ifndef SCATTER_ROLE_NR
 #define SCATTER_ROLE_NR 8           // map rows per wave of the scatter role (every block derives the field index of ALL window columns first)
 #endif
@@ -590,7 +661,6 @@ __device__ __forceinline__ void scatter_role(const Slam2dLidar& lid, const Slam2
     constexpr int NR = SCATTER_ROLE_NR;
     const int i0 = sby * (NW * NR) + wave;
     if (sby * (NW * NR) >= nrow) return;
-    const int ncol = fr.mx1 - fr.mx0;
     const double inv_step = 1.0 / lv.step;
     // (the rows' words and coordinates are requested FIRST: they need the frame only, and their round trip then runs under the
     // column table's)
@@ -602,60 +672,14 @@ __device__ __forceinline__ void scatter_role(const Slam2dLidar& lid, const Slam2
         words[k] = (i < nrow && w <= wlast) ? m.occ_bits[(size_t)(fr.my0 + i) * m.bits_pitch + w] : 0u;
     }
     const double ycoord = (lane < NR && i0 + NW * lane < nrow) ? m.Y[fr.my0 + i0 + NW * lane] : 0.0;
-    for (int j = threadIdx.x; j < ncol; j += NW * 64) {
-        int idx = trunc_div_fast(m.X[fr.mx0 + j] - fr.xlo, lv.step, inv_step);
-        if (idx < 0) idx += fr.fw;                         // Python negative-index wrap (:37)
-        ax_s[j] = (idx < 0 || idx >= fr.fw) ? -1 : idx;
-    }
+    for (int j = threadIdx.x; j < axis_length(fr, 0); j += NW * 64)
+        ax_s[j] = axis_index(trunc_div_fast(m.X[fr.mx0 + j] - fr.xlo, lv.step, inv_step), fr.fw);
     int fy_lane = -1;                                      // lane k < NR evaluates the field row of the wave's k-th map row
-    if (lane < NR) {
-        const int i = i0 + NW * lane;
-        if (i < nrow) {
-            int idx = trunc_div_fast(ycoord - fr.ylo, lv.step, inv_step);
-            if (idx < 0) idx += fr.fh;
-            fy_lane = (idx < 0 || idx >= fr.fh) ? -1 : idx;
-        }
-    }
+    if (lane < NR && i0 + NW * lane < nrow) fy_lane = axis_index(trunc_div_fast(ycoord - fr.ylo, lv.step, inv_step), fr.fh);
 #pragma unroll
     for (int k = 0; k < NR; ++k) fyk[k] = __builtin_amdgcn_readlane(fy_lane, k);
     __syncthreads();
-    const int col_base = w << 5;
-    uint32_t edge = ~0u;
-    if (col_base < fr.mx0) edge &= ~0u << (fr.mx0 - col_base);                    // window edges
-    if (col_base + 32 > fr.mx1) edge &= ~0u >> (col_base + 32 - fr.mx1);
-    // (buffer stores: the row's byte offset rides in the scalar offset, the column in the lane's -- no 64-bit address
-    // arithmetic per set bit; the kernel's launch is bound by its vector instructions)
-    const int fpad = flag_pitch(lv);
-    const __amdgpu_buffer_rsrc_t ro = image_rsrc(lv.occ + (size_t)p * lv.fmax * lv.fpitch, (size_t)lv.fmax * lv.fpitch);
-    const __amdgpu_buffer_rsrc_t rt = image_rsrc(lv.tilemask + (size_t)p * flag_bytes(lv), flag_bytes(lv));   // flags of 8 x 8-cell blocks, [2 tmax][flag_pitch]
-    const uint8_t stamp = occ_stamp(lv);
-    const int half = lane >> 5, bit = lane & 31;
-    const int lbase = (w0 << 5) + bit - fr.mx0;            // the lane's column of word w0, relative to the window
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const uint32_t word = words[k] & edge;
-        unsigned long long nz = __ballot(word != 0u);
-        if (!nz) continue;
-        const int fy = fyk[k];
-        if (fy < 0) continue;                                                      // :36-37
-        const int so = fy * lv.fpitch, st = (fy >> FLAG_SHIFT) * fpad;             // (wave-uniform)
-        while (nz) {
-            const int sa = __ffsll((long long)nz) - 1;
-            nz &= nz - 1;
-            int sb = -1;
-            if (nz) { sb = __ffsll((long long)nz) - 1; nz &= nz - 1; }
-            const uint32_t wa = (uint32_t)__builtin_amdgcn_readlane((int)word, sa), wb = sb >= 0 ? (uint32_t)__builtin_amdgcn_readlane((int)word, sb) : 0u;
-            const uint32_t wsel = half ? wb : wa;
-            const int src = half ? sb : sa;
-            if ((wsel >> bit) & 1u) {
-                const int fx = ax_s[lbase + (src << 5)];
-                if (fx >= 0) {
-                    __builtin_amdgcn_raw_buffer_store_b8(stamp, ro, fx, so, 0);
-                    __builtin_amdgcn_raw_buffer_store_b8(stamp, rt, fx >> FLAG_SHIFT, st, 0);
-                }
-            }
-        }
-    }
+    scatter_expand<NR>(lv, p, fr, w0, lane, words, fyk, ax_s);
 }
 
 __global__ __launch_bounds__(256) void k_refresh_bits(const Slam2dMap* __restrict__ maps, const int32_t* __restrict__ index) {
@@ -1453,26 +1477,10 @@ __device__ __forceinline__ void frame_duties(const Slam2dLidar& lid, const Slam2
     const Slam2dMap m = maps[p];
     uint32_t f;
     const Slam2dFrame fr = make_frame(lid, lv, m, centre[(size_t)p * cstride], centre[(size_t)p * cstride + 1], f);
-    if (threadIdx.x == 0) {
-        lv.frames[p] = fr;
-        lv.tilecount[2 * p] = 0; lv.tilecount[2 * p + 1] = 0;
-        if (lv.bnb) lv.bnb_best[p] = order_bits(-INFINITY);
-        if (lv.bnb >= 2) lv.seed_key[p] = 0ull;
-        if (f) atomicOr(&flags[p], f);
-    }
+    if (threadIdx.x == 0) frame_publish(lv, p, fr, f, flags);
     bool bad = false;
-    for (int axis = 0; axis < 2; ++axis) {
-        const int n = axis == 0 ? fr.mx1 - fr.mx0 : fr.my1 - fr.my0;
-        const double lo = axis == 0 ? fr.xlo : fr.ylo;
-        const int dim = axis == 0 ? fr.fw : fr.fh;
-        for (int j = threadIdx.x; j < n; j += blockDim.x) {
-            const double coord = axis == 0 ? m.X[fr.mx0 + j] : m.Y[fr.my0 + j];
-            int idx = (int)((coord - lo) / lv.step);       // astype(int): truncation toward zero
-            if (idx < 0) idx += dim;                       // Python negative-index wrap (:37)
-            if (idx < 0 || idx >= dim) { idx = -1; bad = true; }
-            (axis == 0 ? lv.axis_x : lv.axis_y)[(size_t)p * lv.wmax + j] = idx;
-        }
-    }
+    for (int axis = 0; axis < 2; ++axis)
+        for (int j = threadIdx.x; j < axis_length(fr, axis); j += blockDim.x) bad = !axis_table_store(lv, m, fr, p, axis, j) || bad;
     if (bad) atomicOr(&flags[p], SLAM2D_F_FIELD_INDEX);
 }
 
@@ -1520,19 +1528,17 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
     const double ex = est[(size_t)p * estride], ey = est[(size_t)p * estride + 1];
     Slam2dFrame fr;
     if (maps) {
-        // no k_frame_axis ahead of this launch: the four frame fields used here, in make_frame's very expressions (:22-25)
-        fr.xlo = ex - lv.reach; fr.ylo = ey - lv.reach;
-        fr.fw = min((int)(((ex + lv.reach) - fr.xlo) / lv.step) + 1, lv.fmax);
-        fr.fh = min((int)(((ey + lv.reach) - fr.ylo) / lv.step) + 1, lv.fmax);
+        // no k_frame_axis ahead of this launch: the four frame fields used here (the frame block flags what is clamped)
+        const FrameExtent e = frame_extent(lv, ex, ey);
+        fr.xlo = e.xlo; fr.ylo = e.ylo;
+        fr.fw = min(e.fw, lv.fmax); fr.fh = min(e.fh, lv.fmax);
     } else {
         fr = lv.frames[p];
     }
     const int B = lid.beams;
     DBG_CLOCK(40, grp == 0 && p == 0);
     constexpr int NW = NT / 64;
-    int hsize = 512;                                       // power of two >= 1.5 * beams (load factor <= 2/3)
-    while (hsize < B + (B >> 1)) hsize <<= 1;
-    const int hmask = hsize - 1;
+    const int hsize = endpoints_hash_size(B), hmask = hsize - 1;
     int* hkey = ep_lds;
     int* hown = ep_lds + hsize;
     int* cnt_s = ep_lds + 2 * hsize;
@@ -1561,10 +1567,7 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
     //                                                        a third of the kernel's vector instructions), interleaved: beam = q * NT + tid, so that a
     //                                                        wave's loads and stores are contiguous (at 1081 beams the
     //                                                        thread-contiguous mapping cost 32 cache lines per wave-load)
-    // np.linspace(theta - fov/2, theta + fov/2, num=B)  (:82-83)
-    const double eth = est[(size_t)p * estride + 2];
-    const double a0 = eth - lid.fov / 2, a1 = eth + lid.fov / 2;
-    const double astep = (a1 - a0) / (double)(B - 1);
+    const BeamFan fan = fan_of(lid, est[(size_t)p * estride + 2]);
     constexpr int QMAX = NT == 256 ? SLAM2D_MAX_BEAMS / 256 : 1;
     int key[QMAX], slot[QMAX];
     double bdx[QMAX], bdy[QMAX];                           // beam endpoint - estimate (:167-168), NaN: no return (:84)
@@ -1580,7 +1583,7 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
                 if (beam_table) {                           // k_frame_axis evaluated :87-88 once for the particle
                     px = lv.beam_xy[((size_t)p * B + b) * 2]; py = lv.beam_xy[((size_t)p * B + b) * 2 + 1];
                 } else {
-                    const double a = (b == B - 1) ? a1 : (double)b * astep + a0;
+                    const double a = fan.angle(b);
                     px = ex + cos(a) * rg; py = ey + sin(a) * rg;                   // :87-88
                 }
                 bdx[q] = px - ex; bdy[q] = py - ey;
@@ -1615,14 +1618,8 @@ __global__ __launch_bounds__(NT) void k_endpoints(Slam2dLidar lid, Slam2dLevel l
 #pragma unroll
     for (int q = 0; q < QMAX; ++q) {
         if (key[q] == INT_MAX) continue;
-        int h = (int)(((unsigned)key[q] * 2654435761u) >> 7) & hmask;
-        for (;;) {
-            const int prev = atomicCAS(&hkey[h], INT_MAX, key[q]);
-            if (prev == INT_MAX || prev == key[q]) break;
-            h = (h + 1) & hmask;
-        }
-        slot[q] = h;
-        atomicMin(&hown[h], q * NT + tid);
+        cell_set_insert(hkey, hmask, key[q], slot[q]);
+        atomicMin(&hown[slot[q]], q * NT + tid);
         if (mark) {                                        // tiles of the (2 nc + 1)^2 patch at (x0, y0)
             const int y0 = key[q] >> 16, x0 = key[q] & 0xFFFF;
             const int tx0 = x0 >> BLUR_SHIFT, ty0 = y0 >> BLUR_SHIFT;
@@ -4317,14 +4314,12 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar li
     __syncthreads();
     if (n >= N) return;                                                          // (wave-uniform)
     const Slam2dFrame fr = lv.frames[p_field];
-    // (a frame is at most fmax x fmax: whatever the frame record holds, no access leaves the slot's image)
-    const int fw = min(fr.fw, min(lv.fmax, lv.fpitch)), fh = min(fr.fh, lv.fmax);
+    const FieldSize fs = frame_clip(lv, fr);
     const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
     const double x = pose[(size_t)n * pstride], y = pose[(size_t)n * pstride + 1], th = pose[(size_t)n * pstride + 2];
     const double* __restrict__ rg = ranges + (size_t)n * rstride;
     const int B = lid.beams;
-    const double a0 = th - lid.fov / 2, a1 = th + lid.fov / 2;                   // np.linspace(theta - fov/2, theta + fov/2, num=B) (:82-83)
-    const double astep = (a1 - a0) / (double)(B - 1);
+    const BeamFan fan = fan_of(lid, th);
     unsigned long long sum_u = 0ull, sum_b = 0ull;                               // (this lane's share)
     int n_u = 0, n_in = 0, n_rng = 0;                                            // (the wave's counts: ballots)
     for (int b0 = 0; b0 < B; b0 += 64) {                                         // (wave-uniform trip count)
@@ -4335,10 +4330,10 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar li
         int key = INT_MAX;
         uint32_t cost = 0u;
         if (in_range) {
-            const double a = B == 1 ? a0 : (b == B - 1) ? a1 : (double)b * astep + a0;
+            const double a = fan.angle(b);
             const double px = x + cos(a) * r, py = y + sin(a) * r;               // :87-88
             int cx, cy;
-            if (score_cell(px, py, fr.xlo, fr.ylo, lv.step, fw, fh, cx, cy)) {
+            if (score_cell(px, py, fr.xlo, fr.ylo, lv.step, fs.fw, fs.fh, cx, cy)) {
                 inside = true;
                 key = (cy << 16) | cx;
                 cost = field[(size_t)cy * lv.fpitch + cx];
@@ -4346,13 +4341,8 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar li
         }
         bool owns = false;
         if (inside) {
-            int h = (int)(((unsigned)key * 2654435761u) >> 7) & hmask;
-            for (;;) {
-                const int prev = atomicCAS(&hkey[h], INT_MAX, key);
-                if (prev == INT_MAX) { owns = true; break; }
-                if (prev == key) break;
-                h = (h + 1) & hmask;
-            }
+            int slot;
+            owns = cell_set_insert(hkey, hmask, key, slot);
             sum_b += cost;
             if (owns) sum_u += cost;
         }
@@ -4384,7 +4374,7 @@ __host__ __device__ __forceinline__ int search_chunk(const long long positions, 
 }
 
 // First launch: E[it][k] = (cos(a_b) * r_b, sin(a_b) * r_b) of heading it and the k-th beam IN RANGE, b -- the only cos / sin of the
-// search, the angles as k_score_poses forms them, the products rounded here so that x + e is x + cos(a) * r bit for bit (no
+// search, the products rounded here so that x + e is x + cos(a) * r bit for bit (no
 // contraction).  Which beams are in range does not depend on the pose: every heading's row is compacted alike, k = the number of
 // beams in range below b (the lanes of a wave read ranges[j] at one address), and the search sums integers, in any order.  Also
 // d_out = all ones, the identity of the search launch's atomicMin.
@@ -4400,9 +4390,7 @@ __global__ __launch_bounds__(256) void k_search_table(Slam2dLidar lid, int nth, 
     int k = 0;
     for (int j = 0; j < b; ++j) k += ranges[j] < lid.max_range;
     const double th = th0 + (double)it * dth;
-    const double a0 = th - lid.fov / 2, a1 = th + lid.fov / 2;                   // np.linspace(theta - fov/2, theta + fov/2, num=B) (:82-83)
-    const double astep = (a1 - a0) / (double)(B - 1);
-    const double a = B == 1 ? a0 : (b == B - 1) ? a1 : (double)b * astep + a0;
+    const double a = fan_of(lid, th).angle(b);
     E[(size_t)it * B + k] = make_double2(cos(a) * r, sin(a) * r);                // :87-88
 }
 
@@ -4420,8 +4408,7 @@ __global__ __launch_bounds__(256) void k_search_lattice(Slam2dLidar lid, Slam2dL
     const unsigned p = blockIdx.x * 256u + threadIdx.x;                           // (positions < 2^31: no wrap)
     if (p >= (unsigned)positions) return;
     const Slam2dFrame fr = lv.frames[p_field];
-    // (a frame is at most fmax x fmax: whatever the frame record holds, no access leaves the slot's image)
-    const int fw = min(fr.fw, min(lv.fmax, lv.fpitch)), fh = min(fr.fh, lv.fmax);
+    const FieldSize fs = frame_clip(lv, fr);
     const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
     const int B = lid.beams;
     const int iy = (int)p / nx, ix = (int)p - iy * nx;
@@ -4436,7 +4423,7 @@ __global__ __launch_bounds__(256) void k_search_lattice(Slam2dLidar lid, Slam2dL
         int n_in = 0;
         const auto beam = [&](const double2 d) {
             int cx, cy;
-            const bool inside = score_cell(x + d.x, y + d.y, fr.xlo, fr.ylo, lv.step, fw, fh, cx, cy);
+            const bool inside = score_cell(x + d.x, y + d.y, fr.xlo, fr.ylo, lv.step, fs.fw, fs.fh, cx, cy);
             const uint32_t cost = field[inside ? cy * lv.fpitch + cx : 0];       // (fmax * fpitch < 2^29)
             sum_b += inside ? cost : 0u;
             n_in += inside;
@@ -4929,8 +4916,7 @@ static void launch_endpoints(const Slam2dLidar& lid, const Slam2dLevel& lv, int 
     StageScope prof(SLAM2D_STAGE_ENDPOINTS, s);
     int n = 256;
     while (n < lid.beams) n <<= 1;
-    int hsize = 512;
-    while (hsize < lid.beams + (lid.beams >> 1)) hsize <<= 1;
+    const int hsize = endpoints_hash_size(lid.beams);
     size_t ep_lds = (size_t)(2 * hsize + 32 + (mark ? 6 * lv.tmax * ((lv.tmax + 31) / 32) + (lv.tmax * lv.tmax + 31) / 32 : 0)) * sizeof(int);
     const int G = lv.ep_group > 0 ? lv.ep_group : 1;
     const int nt = lid.beams <= 192 ? 192 : 256;
@@ -5252,16 +5238,26 @@ int slam2d_predict_scan(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32
     return launch_status();
 }
 
-int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose,
-                       int32_t pose_stride, const double* d_ranges, int32_t ranges_stride, double* d_out, void* stream) {
-    if (!lidar || !level || !d_pose || !d_ranges || !d_out || !level->field || !level->frames) return SLAM2D_E_BADARG;
-    if (N <= 0 || p_field < 0 || pose_stride < 3) return SLAM2D_E_BADARG;
+// What slam2d_score_poses and slam2d_search_lattice ask of the lidar and of the level whose slot p_field they read.  Every
+// SLAM2D_E_BADARG of theirs comes before any SLAM2D_E_TOOLARGE, so a caller returns the former at once and the latter after
+// its own argument checks.
+static int check_scored_field(const Slam2dLidar* lidar, const Slam2dLevel* level, int p_field) {
+    if (!lidar || !level || !level->field || !level->frames || p_field < 0) return SLAM2D_E_BADARG;
     if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_BADARG;
-    if (ranges_stride != 0 && ranges_stride < lidar->beams) return SLAM2D_E_BADARG;
     if (!(lidar->max_range > 0.0) || !(level->step > 0.0) || !(level->cost_scale > 0.0)) return SLAM2D_E_BADARG;   // (the negated forms refuse a NaN)
-    // the field's own limits (check_level): a cell key packs (row << 16 | column), offsets into one image stay below 2^31
+    // the field's limits as check_level has them: a cell key packs (row << 16 | column), offsets into one image stay below 2^31
     if (level->fmax <= 0 || level->fpitch < level->fmax) return SLAM2D_E_BADARG;
     if ((long long)level->fmax * level->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;
+    return 0;
+}
+
+int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose,
+                       int32_t pose_stride, const double* d_ranges, int32_t ranges_stride, double* d_out, void* stream) {
+    const int rc = check_scored_field(lidar, level, p_field);
+    if (rc == SLAM2D_E_BADARG) return rc;
+    if (!d_pose || !d_ranges || !d_out || N <= 0 || pose_stride < 3) return SLAM2D_E_BADARG;
+    if (ranges_stride != 0 && ranges_stride < lidar->beams) return SLAM2D_E_BADARG;
+    if (rc) return rc;
     const int hsize = score_hash_size(lidar->beams);
     const int waves = hsize > 2048 ? SCORE_WAVES / 2 : SCORE_WAVES;               // <= 32 KB of hash sets per block
     const long long blocks = ((long long)N + waves - 1) / waves;
@@ -5290,16 +5286,16 @@ int64_t slam2d_search_lattice_work(const Slam2dLidar* lidar, int32_t nx, int32_t
 int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t nx, int32_t ny, int32_t nth,
                           double x0, double dx, double y0, double dy, double th0, double dth, const double* d_ranges,
                           uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out, void* stream) {
-    if (!lidar || !level || !d_ranges || !d_out || !level->field || !level->frames || p_field < 0) return SLAM2D_E_BADARG;
+    const int frc = check_scored_field(lidar, level, p_field);
+    if (frc == SLAM2D_E_BADARG) return frc;
+    if (!d_ranges || !d_out) return SLAM2D_E_BADARG;
     if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
-    if (!(lidar->max_range > 0.0) || !(level->step > 0.0) || !(level->cost_scale > 0.0)) return SLAM2D_E_BADARG;   // (the negated forms refuse a NaN)
-    if (level->fmax <= 0 || level->fpitch < level->fmax) return SLAM2D_E_BADARG;
     long long words = 0;
     const int rc = check_search_lattice(lidar, nx, ny, nth, &words);
     if (rc == SLAM2D_E_BADARG) return rc;
     if (words > 0 && !d_work) return SLAM2D_E_BADARG;
     if (rc) return rc;
-    if ((long long)level->fmax * level->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;
+    if (frc) return frc;
     const int positions = nx * ny;
     const int hc = search_chunk(positions, nth);
     const long long blocks = ((long long)positions + 255) / 256, rows = cdiv(nth, hc);
