@@ -550,6 +550,61 @@ int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, in
                           uint64_t* d_work, uint64_t* d_out, void* stream);
 int64_t slam2d_search_lattice_work(const Slam2dLidar* lidar, int32_t nx, int32_t ny, int32_t nth);
 
+/* One step of Monte-Carlo localisation in a known map: N pose hypotheses are moved by the odometry increment, weighed against the
+ * ONE field of slot p_field with slam2d_score_poses' measurement model, resampled, and left on the device -- no host decision in
+ * between (an added symbol: no struct and no existing signature changed, the ABI number stays).  PRECONDITION: that of
+ * slam2d_score_poses (the FULL slam2d_field_build has run for slot p_field of `level`, ordered in front of this call); the same
+ * members of `level` and `lidar` are read.  Everything below is an integer operation or ONE rounded IEEE operation at a time (no
+ * contraction), so NumPy reproduces it bit for bit and the same inputs give the same bits on every call.
+ *   a. NOISE.  Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments
+ *      0x9E3779B9, 0xBB67AE85; one round maps the counter c to [hi(M1 * c2) ^ c1 ^ k0, lo(M1 * c2), hi(M0 * c0) ^ c3 ^ k1,
+ *      lo(M0 * c0)] and then bumps the key; ten rounds.  Key = (seed low, seed high).  For particle n and draw j in {0, 1, 2} the
+ *      counter is (n, j, scan low, scan high); S = the sum of the four output words read as int32, in 64 bits, and
+ *      g_j = (double)S * 2^-31: exact, |g| < 4, approximately normal -- the Irwin-Hall sum of four uniforms, variance 4/3, support
+ *      +/- 3.46 sigma (no tail beyond).  The resampler's word r is output word 0 of the counter (0xffffffff, 0, scan low, scan high).
+ *   b. MOVE.  With (x, y, th) = d_pose_in[n * pose_stride + 0..2], motion = (dfwd, dside, dturn) -- the odometry increment in the
+ *      robot's own previous frame -- and amp (noise amplitudes: std = amp * sqrt(4/3); 0 = none), each product and sum rounded,
+ *      in this order:  fx = dfwd + amp[0] * g_0,  fy = dside + amp[1] * g_1,  c = cos(th), s = sin(th),
+ *        x' = (x + c * fx) - s * fy,   y' = (y + s * fx) + c * fy,   th' = (th + dturn) + amp[2] * g_2.
+ *   c. WEIGH.  For the moved pose and the ONE scan d_ranges[beams], steps 1-4 of slam2d_score_poses define sum_b (the field's sum
+ *      over every inside beam), the INSIDE beams and the beams IN RANGE, the true division and the 1e9 guard included; no cell set
+ *      is built.  cost_n = sum_b + (uint64)(in_range - inside) * outside_cost (slam2d_search_lattice's cost, below 2^44);
+ *      cmin = the minimum cost, best = the LOWEST n that attains it (the 64-bit minimum of cost << 20 | n);
+ *        w_n = min(d_lut[min((cost_n - cmin) >> lut_shift, lut_n - 1)], SLAM2D_MCL_MAX_WEIGHT)
+ *      -- integer weights from a table the host makes (exp(-cost / cost_scale) scaled to 24 bits is the reference's soft-max): no
+ *      exp on the device, whose last bit could flip a resampling.
+ *   d. RESAMPLE, systematic, in integers.  C_n = the inclusive prefix sum of w, W = C_(N-1) < 2^44;
+ *      u0 = floor(r * W / 2^32) = W_hi * r + ((W_lo * r) >> 32);  t_k = floor((k * W + u0) / N) for offspring k (below 2^64, as
+ *      w <= 0xffffff and N <= 2^20);  the ancestor a_k = the least n with t_k < C_n;  W == 0: a_k = k.
+ *      d_pose_out[k * pose_stride + 0..2] = the moved pose of a_k (the other slots of the stride are untouched);
+ *      d_ancestor[k] = a_k where d_ancestor is not NULL.  Ancestors never decrease with k.
+ *   e. REPORT.  d_report[0..15], 64-bit words:  0 cmin   1 best   2 W   3 the number of w_n > 0   4 u0   5 in_range
+ *      6 the number of DISTINCT ancestors   7-9 the bit patterns of the best particle's moved pose   10 M, the number of offspring
+ *      with |x| < 2^20, |y| < 2^20 and a finite th   11-14 the signed sums over those offspring of llrint(x * 65536),
+ *      llrint(y * 65536), llrint(cos(th) * 2^30), llrint(sin(th) * 2^30) (two's complement)   15 0.
+ *      Sums of integers: x / (65536 M), y / (65536 M) and atan2 of the last two are a mean pose of the same bits on every call.
+ *   f. A pose with a non-finite component has no inside beam and costs in_range * outside_cost; no field access leaves
+ *      [0, fh) x [0, fw); no quotient that fails the guard is converted to an integer.
+ * d_pose_in and d_pose_out are different buffers (ping-pong).  d_work: slam2d_mcl_work(N) 8-byte words of scratch (5 * N + 1032:
+ * the moved poses, the costs, the prefix sums).  The caller need not initialise d_work, d_report, d_pose_out or d_ancestor.  The
+ * call allocates nothing, raises no fault bit, enqueues five launches on `stream` -- move, a thread per particle; score, a wave
+ * per particle, joined by the integer atomicMin; weigh and scan per block of 1024 particles; one block over the at most 1024 block
+ * sums; resample -- and does not synchronise: separate launches order the phases, every join is an integer atomic or a fixed
+ * prefix sum.  SLAM2D_E_BADARG, before any HIP call: a NULL pointer other than d_ancestor, d_pose_in == d_pose_out, N < 1,
+ * pose_stride < 3, lut_n < 1 or > 65536, lut_shift outside 0..43, a non-finite motion or amp, and the level and lidar cases of
+ * slam2d_score_poses; SLAM2D_E_TOOLARGE: N > SLAM2D_MCL_MAX_PARTICLES, fmax * fpitch >= 2^29.
+ * slam2d_mcl_work makes no HIP call; < 0 means SLAM2D_E_* (N < 1: BADARG; N > SLAM2D_MCL_MAX_PARTICLES: TOOLARGE). */
+#define SLAM2D_MCL_REPORT 16
+#define SLAM2D_MCL_MAX_PARTICLES (1 << 20)
+#define SLAM2D_MCL_MAX_WEIGHT 0xffffffu
+int64_t slam2d_mcl_work(int32_t N);
+int slam2d_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N,
+                    const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                    const double motion[3], const double amp[3], uint64_t seed, uint64_t scan,
+                    const double* d_ranges, uint32_t outside_cost,
+                    const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
+                    int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream);
+
 /* Particle.updateEstimatedPose for P particles (Algorithm/FastSlam.py:77-106): the pose prior of the
  * next scan from the previous matched poses and the raw odometry increment.
  *   d_prev_pose[p*3 + 0..2]  previous matched pose (prevMatchedReading)

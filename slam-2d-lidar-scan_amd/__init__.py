@@ -11,7 +11,8 @@ with ``importlib.import_module("slam-2d-lidar-scan_amd")`` or through the
 (Utils/OccupancyGrid.py, Utils/ScanMatcher_OGBased.py); ``ParticleFilter`` is the
 batched counterpart of Algorithm/FastSlam.py's.  ``map_from_poses`` builds the map of a log at
 given poses (Utils/OccupancyGrid.py:main).  ``ScanMatcher.matchMoments`` / ``ParticleFilter.match_moments`` give the pose
-mean and covariance of the last match over its whole pose cube (``ParticleEngine.match_moments``).  All of them need the HIP library
+mean and covariance of the last match over its whole pose cube (``ParticleEngine.match_moments``).  ``Localiser`` follows a robot
+through a finished map: Monte-Carlo localisation, one device call per scan (``ParticleEngine.mcl_step``).  All of them need the HIP library
 (``libslam2d_hip.so``, built by ``__graft_entry__.build()``) and a GPU; there is no
 CPU fallback.
 """
@@ -32,6 +33,7 @@ _LAZY = {
     "LidarModel": ("engine", "LidarModel"),
     "MapState": ("engine", "MapState"),
     "map_from_poses": ("mapping", "map_from_poses"),
+    "Localiser": ("localise", "Localiser"),
 }
 
 

@@ -57,6 +57,10 @@ PREDICT_STRIDE = 4                   # doubles per (pose, beam) of slam2d_predic
 SCORE_STRIDE = 8                     # doubles per pose of slam2d_score_poses' output: score, |U|, beam score, inside, in range, sum_u, sum_b, 0
 SEARCH_CHUNK = 8                     # headings per block row of slam2d_search_lattice's search launch, at least (csrc: SEARCH_CHUNK)
 SEARCH_WAVES = 4096                  # ... and more where fewer than this many waves of 64 positions would not fill the card otherwise
+MCL_REPORT = 16                      # 64-bit words of slam2d_mcl_step's report
+MCL_MAX_PARTICLES = 1 << 20
+MCL_MAX_WEIGHT = 0xffffff            # largest integer weight of a particle (24 bits: the weights' sum stays below 2^44)
+MCL_SCAN_BLOCK = 1024                # particles one block of slam2d_mcl_step's scan launch covers (csrc: MCL_SCAN_BLOCK)
 
 STAGE_SWEEP,STAGE_BLUR, STAGE_SCATTER, STAGE_UPDATE, STAGE_SELECT, STAGE_ENDPOINTS, STAGE_BOUND, STAGE_EXACT = range(8)
 STAGE_NAMES = {STAGE_SWEEP: "k_sweep", STAGE_BLUR: "k_blur_clamp", STAGE_SCATTER: "k_occ_scatter",
@@ -173,6 +177,10 @@ SIGNATURES = {
     "slam2d_search_lattice": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_uint32, _vp, _vp, _vp]),
     "slam2d_search_lattice_work": (C.c_int64, [C.POINTER(Slam2dLidar), C.c_int32, C.c_int32, C.c_int32]),
+    "slam2d_mcl_work": (C.c_int64, [C.c_int32]),
+    "slam2d_mcl_step": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32,
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_uint64, _vp, C.c_uint32,
+                                  _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "slam2d_occ_extent": (C.c_int, [C.POINTER(Slam2dLidar), C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "slam2d_map_scans": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "slam2d_prior": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int32, C.c_double, _vp, C.c_int32, _vp, _vp, _vp]),

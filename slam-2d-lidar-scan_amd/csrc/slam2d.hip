@@ -4443,6 +4443,269 @@ __global__ __launch_bounds__(256) void k_search_lattice(Slam2dLidar lid, Slam2dL
     atomicMin(&out[p], best);
 }
 
+// ---- Monte-Carlo localisation in a known map (slam2d_mcl_step): move, weigh, resample, all in integers and rounded operations ----
+#define MCL_WAVES 4                  // particles (waves) per block of the scoring launch
+#define MCL_UNROLL 2                 // trips of 64 beams its beam loop takes at a time: their gathers are in flight together
+#define MCL_SCAN_BLOCK 1024          // particles one block of the scan launch covers, 4 per thread (tests/test_gpu_mcl.py names it)
+#define MCL_TAIL 8                   // words of d_work behind its arrays: the packed minimum, then padding
+
+// d_work of slam2d_mcl_step: the moved poses [N][3], the costs [N], the weights' block-local prefix sums [N], the scan blocks'
+// sums (then: their exclusive prefix sums) [MCL_SCAN_BLOCK -- at most that many blocks at SLAM2D_MCL_MAX_PARTICLES], the tail
+struct MclWork {
+    double* moved;
+    unsigned long long *cost, *csum, *bsum, *key;
+};
+__host__ __device__ __forceinline__ long long mcl_work_words(const int N) { return 5ll * N + MCL_SCAN_BLOCK + MCL_TAIL; }
+__host__ __device__ __forceinline__ MclWork mcl_work_of(uint64_t* w, const int N) {
+    unsigned long long* u = (unsigned long long*)w;
+    return MclWork{reinterpret_cast<double*>(w), u + 3ll * N, u + 4ll * N, u + 5ll * N, u + 5ll * N + MCL_SCAN_BLOCK};
+}
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011): ten rounds, the key bumped behind each
+struct Philox4 { uint32_t v[4]; };
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+// draw j of particle n: the four words as int32 summed, times 2^-31 -- exact, |g| < 4, Irwin-Hall of four (variance 4/3)
+__device__ __forceinline__ double mcl_noise(const uint32_t n, const uint32_t j, const uint64_t seed, const uint64_t scan) {
+    const Philox4 o = philox4x32_10(n, j, (uint32_t)scan, (uint32_t)(scan >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+    const long long S = (long long)(int32_t)o.v[0] + (int32_t)o.v[1] + (int32_t)o.v[2] + (int32_t)o.v[3];
+    return (double)S * 0x1p-31;
+}
+
+// Inclusive prefix sum of v over the block's threads in thread order (blockDim.x a multiple of 64, at most 1024); total: the
+// block's sum.  lds: 16 words.  Integers: the same bits whatever the order of arrival.
+__device__ __forceinline__ unsigned long long block_scan_u64(unsigned long long v, unsigned long long* lds, unsigned long long& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    if (lane == 63) lds[wv] = v;
+    __syncthreads();
+    unsigned long long off = 0ull, tot = 0ull;
+    for (int i = 0; i < nw; ++i) {
+        const unsigned long long s = lds[i];
+        if (i < wv) off += s;
+        tot += s;
+    }
+    total = tot;
+    return v + off;
+}
+
+// First launch, one thread per particle: the three draws and the move, in the header's operations and order; thread 0 also sets
+// the identities of what the later launches join with integer atomics.  (Moving the pose inside the scoring launch, where a wave
+// holds one particle, costs that wave a cos / sin of its own: as much as 64 beams, a fourth trip beside the three of 180 beams --
+// profiles/r13_mcl_step.md.)
+__global__ __launch_bounds__(256) void k_mcl_move(int N, const double* __restrict__ pose, int pstride, double dfwd, double dside, double dturn,
+                                                  double amp0, double amp1, double amp2, uint64_t seed, uint64_t scan, MclWork wk,
+                                                  unsigned long long* __restrict__ report) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0) {
+        *wk.key = ~0ull;
+        report[3] = 0ull; report[6] = 0ull;
+        for (int i = 10; i < 15; ++i) report[i] = 0ull;
+    }
+    if (n >= N) return;
+    const double x0 = pose[(size_t)n * pstride], y0 = pose[(size_t)n * pstride + 1], th0 = pose[(size_t)n * pstride + 2];
+    const double fx = dfwd + amp0 * mcl_noise((uint32_t)n, 0u, seed, scan), fy = dside + amp1 * mcl_noise((uint32_t)n, 1u, seed, scan);
+    const double c = cos(th0), s = sin(th0);
+    double* m = wk.moved + (size_t)n * 3;
+    m[0] = (x0 + c * fx) - s * fy;
+    m[1] = (y0 + s * fx) + c * fy;
+    m[2] = (th0 + dturn) + amp2 * mcl_noise((uint32_t)n, 2u, seed, scan);
+}
+
+// U trips of 64 beams of one particle, from beam b0: every cell first, then the gathers, then the sums.  A beam that is not inside
+// -- out of range, beyond the last beam, outside the field, a quotient that fails the guard -- loads cell 0 of the image and adds
+// nothing: no branch, so the U gathers are in flight together.
+template <int U>
+__device__ __forceinline__ void mcl_beams(const int b0, const int lane, const int B, const double* __restrict__ ranges, const double max_range,
+                                          const BeamFan& fan, const double x, const double y, const Slam2dFrame& fr, const double step,
+                                          const FieldSize fs, const int fpitch, const uint32_t* __restrict__ field,
+                                          unsigned long long& sum_b, int& n_in, int& n_rng) {
+    int idx[U];
+    bool inside[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int b = b0 + 64 * u + lane;
+        const double r = b < B ? ranges[b] : NAN;
+        const bool in_range = r < max_range;                                     // :84 (NaN and +inf are out, 0 and negatives in)
+        const double a = fan.angle(b);
+        const double px = x + cos(a) * r, py = y + sin(a) * r;                   // :87-88
+        int cx, cy;
+        inside[u] = score_cell(px, py, fr.xlo, fr.ylo, step, fs.fw, fs.fh, cx, cy) && in_range;
+        idx[u] = inside[u] ? cy * fpitch + cx : 0;                               // (fmax * fpitch < 2^29)
+        n_rng += __popcll(__ballot(in_range));
+        n_in += __popcll(__ballot(inside[u]));
+    }
+    uint32_t cost[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) cost[u] = field[idx[u]];
+#pragma unroll
+    for (int u = 0; u < U; ++u) sum_b += inside[u] ? cost[u] : 0u;
+}
+
+// Score: k_score_poses' shape -- one wave per particle, beams interleaved over the lanes, the ranges read contiguously -- without
+// its cell set, on the moved poses; the trips of 64 beams go MCL_UNROLL at a time, the rest one by one.  cost << 20 | n joins the
+// particles in one 64-bit integer atomicMin, sent only where it can lower the word as last read (a stale read costs an atomic,
+// never the result).  Reads frames[p_field], the slot's field, the moved poses and the ranges; writes the costs; no fault bit.
+__global__ __launch_bounds__(64 * MCL_WAVES) void k_mcl_score(Slam2dLidar lid, Slam2dLevel lv, int p_field, int N, const double* __restrict__ ranges,
+                                                              unsigned outside_cost, MclWork wk) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = blockIdx.x * MCL_WAVES + wv;
+    if (n >= N) return;                                                          // (wave-uniform)
+    const Slam2dFrame fr = lv.frames[p_field];
+    const FieldSize fs = frame_clip(lv, fr);
+    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const double x = wk.moved[(size_t)n * 3], y = wk.moved[(size_t)n * 3 + 1], th = wk.moved[(size_t)n * 3 + 2];
+    const int B = lid.beams, trips = (B + 63) >> 6;
+    const BeamFan fan = fan_of(lid, th);
+    unsigned long long sum_b = 0ull;                                             // (this lane's share)
+    int n_in = 0, n_rng = 0;                                                     // (the wave's counts: ballots)
+    int t = 0;
+    for (; t + MCL_UNROLL <= trips; t += MCL_UNROLL)                             // (wave-uniform trip counts)
+        mcl_beams<MCL_UNROLL>(64 * t, lane, B, ranges, lid.max_range, fan, x, y, fr, lv.step, fs, lv.fpitch, field, sum_b, n_in, n_rng);
+    for (; t < trips; ++t) mcl_beams<1>(64 * t, lane, B, ranges, lid.max_range, fan, x, y, fr, lv.step, fs, lv.fpitch, field, sum_b, n_in, n_rng);
+    sum_b = wave64_sum_u64(sum_b);
+    if (lane == 0) {
+        const unsigned long long cost = sum_b + (unsigned long long)(n_rng - n_in) * outside_cost;      // (below 2^44 at 2048 beams)
+        wk.cost[n] = cost;
+        const unsigned long long v = (cost << 20) | (unsigned long long)n;
+        if (v < __hip_atomic_load(wk.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(wk.key, v);
+    }
+}
+
+// Weigh and scan: block b takes particles [b * MCL_SCAN_BLOCK, ...), four consecutive ones per thread; their integer weights from
+// the table, the block-local inclusive prefix sums into csum, the block's sum into bsum[b], the weights above zero counted
+__global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcl_weigh(int N, const uint32_t* __restrict__ lut, int lut_n, int lut_shift, MclWork wk,
+                                                                  unsigned long long* __restrict__ report) {
+    __shared__ unsigned long long lds[16];
+    __shared__ unsigned n_pos;
+    if (threadIdx.x == 0) n_pos = 0u;
+    const unsigned long long cmin = *wk.key >> 20;
+    const int n0 = blockIdx.x * MCL_SCAN_BLOCK + threadIdx.x * 4;
+    unsigned long long pre[4], run = 0ull;
+    unsigned pos = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint32_t w = 0u;
+        if (n0 + i < N) {
+            const unsigned long long d = (wk.cost[n0 + i] - cmin) >> lut_shift;
+            w = min(lut[d < (unsigned long long)(lut_n - 1) ? (int)d : lut_n - 1], (uint32_t)SLAM2D_MCL_MAX_WEIGHT);
+        }
+        pos += w > 0u;
+        run += w;
+        pre[i] = run;
+    }
+    unsigned long long total;
+    const unsigned long long off = block_scan_u64(run, lds, total) - run;         // (its barrier orders n_pos = 0 in front of the adds)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (n0 + i < N) wk.csum[n0 + i] = off + pre[i];
+    if (pos) atomicAdd(&n_pos, pos);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        wk.bsum[blockIdx.x] = total;
+        if (n_pos) atomicAdd(&report[3], (unsigned long long)n_pos);
+    }
+}
+
+// One block: the scan blocks' sums become their exclusive prefix sums; W, the resampler's word and u0, and the report's words
+// that need no particle loop
+__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcl_sums(Slam2dLidar lid, int N, uint64_t seed, uint64_t scan, const double* __restrict__ ranges,
+                                                             MclWork wk, unsigned long long* __restrict__ report) {
+    __shared__ unsigned long long lds[16];
+    __shared__ unsigned n_rng;
+    const int t = threadIdx.x, nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
+    if (t == 0) n_rng = 0u;
+    const unsigned long long v = t < nb ? wk.bsum[t] : 0ull;
+    unsigned long long W;
+    const unsigned long long incl = block_scan_u64(v, lds, W);
+    if (t < nb) wk.bsum[t] = incl - v;
+    unsigned cnt = 0u;
+    for (int b = t; b < lid.beams; b += MCL_SCAN_BLOCK) cnt += ranges[b] < lid.max_range;
+    if (cnt) atomicAdd(&n_rng, cnt);
+    __syncthreads();
+    if (t == 0) {
+        const unsigned long long key = *wk.key, best = key & 0xfffffull;
+        const unsigned long long r = philox4x32_10(0xffffffffu, 0u, (uint32_t)scan, (uint32_t)(scan >> 32), (uint32_t)seed, (uint32_t)(seed >> 32)).v[0];
+        report[0] = key >> 20;
+        report[1] = best;
+        report[2] = W;
+        report[4] = (W >> 32) * r + (((W & 0xffffffffull) * r) >> 32);          // floor(r * W / 2^32), W < 2^44
+        report[5] = n_rng;
+        for (int i = 0; i < 3; ++i) report[7 + i] = (unsigned long long)__double_as_longlong(wk.moved[best * 3 + i]);
+        report[15] = 0ull;
+    }
+}
+
+// Resample: one thread per offspring k.  t_k = floor((k W + u0) / N) < W (below 2^64: W <= N * 0xffffff, N <= 2^20); its ancestor
+// the least n with t_k < C_n, found in the scan blocks' prefix sums, then in that block's local ones.  k is its ancestor's FIRST
+// offspring iff t_(k-1) falls in front of the ancestor's share -- the count of those is the number of distinct ancestors.  The
+// sums of the report are joined per block, then with integer atomics.
+__global__ __launch_bounds__(256) void k_mcl_resample(int N, MclWork wk, double* __restrict__ out, int pstride, int32_t* __restrict__ ancestor,
+                                                      unsigned long long* __restrict__ report) {
+    __shared__ unsigned long long acc[6];
+    if (threadIdx.x < 6) acc[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long W = report[2], u0 = report[4];
+    unsigned long long part[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};            // first offspring, M, the four sums
+    if (k < N) {
+        int a = k;
+        bool first = true;
+        if (W) {
+            const unsigned long long t = ((unsigned long long)k * W + u0) / (unsigned long long)N;
+            const int nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
+            int lo = 0, hi = nb - 1;                                             // the least block whose inclusive end is beyond t
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (t < wk.bsum[mid + 1]) hi = mid; else lo = mid + 1;           // (mid + 1 <= nb - 1: block mid's end is the next one's start)
+            }
+            const unsigned long long start = wk.bsum[lo], rel = t - start;
+            const int base = lo * MCL_SCAN_BLOCK;
+            int i0 = 0, i1 = min(MCL_SCAN_BLOCK, N - base) - 1;                  // rel < the block's sum = csum of its last particle
+            while (i0 < i1) {
+                const int mid = (i0 + i1) >> 1;
+                if (rel < wk.csum[base + mid]) i1 = mid; else i0 = mid + 1;
+            }
+            a = base + i0;
+            if (k > 0) {
+                const unsigned long long tp = ((unsigned long long)(k - 1) * W + u0) / (unsigned long long)N;
+                first = tp < start + (i0 > 0 ? wk.csum[a - 1] : 0ull);
+            }
+        }
+        const double x = wk.moved[(size_t)a * 3], y = wk.moved[(size_t)a * 3 + 1], th = wk.moved[(size_t)a * 3 + 2];
+        double* o = out + (size_t)k * pstride;
+        o[0] = x; o[1] = y; o[2] = th;
+        if (ancestor) ancestor[k] = a;
+        part[0] = first;
+        if (fabs(x) < 0x1p20 && fabs(y) < 0x1p20 && __builtin_isfinite(th)) {    // (a NaN fails the comparisons)
+            part[1] = 1ull;
+            part[2] = (unsigned long long)llrint(x * 65536.0);
+            part[3] = (unsigned long long)llrint(y * 65536.0);
+            part[4] = (unsigned long long)llrint(cos(th) * 0x1p30);
+            part[5] = (unsigned long long)llrint(sin(th) * 0x1p30);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {                                                // (every lane is here: signed sums in two's complement)
+        const unsigned long long s = wave64_sum_u64(part[i]);
+        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&acc[i], s);
+    }
+    __syncthreads();
+    if (threadIdx.x < 6 && acc[threadIdx.x]) atomicAdd(&report[threadIdx.x == 0 ? 6 : 9 + threadIdx.x], acc[threadIdx.x]);
+}
+
 // Sharded normaliser, merge half: every rank folds the gathered [world][3] partials in rank order
 // (so the result does not depend on the network's reduction order), normalises its own particles
 // and evaluates sum (w - 1/N)^2 = sum w^2 - 1/N over ALL N particles (Algorithm/FastSlam.py:32-35).
@@ -5306,6 +5569,36 @@ int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, in
     k_search_table<<<(unsigned)((first + 255) / 256), 256, 0, s>>>(*lidar, nth, th0, dth, d_ranges, E, (unsigned long long*)d_out, positions);
     k_search_lattice<<<dim3((unsigned)blocks, (unsigned)rows), 256, 0, s>>>(*lidar, *level, p_field, nx, positions, nth, hc, x0, dx, y0, dy,
                                                                            d_ranges, E, outside_cost, (unsigned long long*)d_out);
+    return launch_status();
+}
+
+int64_t slam2d_mcl_work(int32_t N) {
+    if (N < 1) return SLAM2D_E_BADARG;
+    if (N > SLAM2D_MCL_MAX_PARTICLES) return SLAM2D_E_TOOLARGE;
+    return mcl_work_words(N);
+}
+
+int slam2d_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose_in,
+                    double* d_pose_out, int32_t pose_stride, const double motion[3], const double amp[3], uint64_t seed, uint64_t scan,
+                    const double* d_ranges, uint32_t outside_cost, const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
+                    int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream) {
+    const int frc = check_scored_field(lidar, level, p_field);
+    if (frc == SLAM2D_E_BADARG) return frc;
+    if (!d_pose_in || !d_pose_out || !motion || !amp || !d_ranges || !d_lut || !d_work || !d_report) return SLAM2D_E_BADARG;
+    if (d_pose_in == d_pose_out || N < 1 || pose_stride < 3 || lut_n < 1 || lut_n > 65536 || lut_shift < 0 || lut_shift > 43)
+        return SLAM2D_E_BADARG;
+    for (int i = 0; i < 3; ++i)
+        if (!__builtin_isfinite(motion[i]) || !__builtin_isfinite(amp[i])) return SLAM2D_E_BADARG;
+    if (N > SLAM2D_MCL_MAX_PARTICLES) return SLAM2D_E_TOOLARGE;
+    if (frc) return frc;
+    hipStream_t s = (hipStream_t)stream;
+    const MclWork wk = mcl_work_of(d_work, N);
+    unsigned long long* report = (unsigned long long*)d_report;
+    k_mcl_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion[0], motion[1], motion[2], amp[0], amp[1], amp[2], seed, scan, wk, report);
+    k_mcl_score<<<cdiv(N, MCL_WAVES), 64 * MCL_WAVES, 0, s>>>(*lidar, *level, p_field, N, d_ranges, outside_cost, wk);
+    k_mcl_weigh<<<cdiv(N, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(N, d_lut, lut_n, lut_shift, wk, report);
+    k_mcl_sums<<<1, MCL_SCAN_BLOCK, 0, s>>>(*lidar, N, seed, scan, d_ranges, wk, report);
+    k_mcl_resample<<<cdiv(N, 256), 256, 0, s>>>(N, wk, d_pose_out, pose_stride, d_ancestor, report);
     return launch_status();
 }
 

@@ -228,6 +228,42 @@ def encode_cost(prob, scale):
     return c.astype(np.uint32)
 
 
+def weight_table(cost_scale, temperature=1.0, entries=4096):
+    """The integer weights of slam2d_mcl_step (include/slam2d.h): ``(lut, shift)`` with
+    lut[i] = rint(0xffffff * exp(-(i << shift) / (cost_scale * temperature))) as uint32 [entries] and ``shift`` the smallest
+    value for which the last entry is 0 -- the finest table that still reaches the costs whose weight rounds to nothing.  A cost
+    is -score * cost_scale, so ``temperature`` 1.0 is the reference's own soft-max, exp(score - best score); a larger one
+    flattens it."""
+    entries = int(entries)
+    scale = float(cost_scale) * float(temperature)
+    if not 2 <= entries <= 65536:
+        raise ValueError(f"entries wants 2 .. 65536, not {entries!r}")
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError("cost_scale * temperature wants a positive number")
+    i = np.arange(entries, dtype=np.float64)
+    for shift in range(44):
+        lut = np.rint(float(_lib.MCL_MAX_WEIGHT) * np.exp(-(i * float(1 << shift)) / scale))
+        if lut[-1] == 0:
+            return lut.astype(np.uint32), shift
+    raise ValueError(f"no shift up to 43 lets a table of {entries} entries reach a weight of 0 at a scale of {scale:g}")
+
+
+def mcl_report_host(words):
+    """The sixteen words of slam2d_mcl_step's report (include/slam2d.h) as a dict: ``cmin``, ``best``, ``W``, ``positive`` (weights
+    above zero), ``u0``, ``in_range``, ``distinct`` (ancestors), ``best_pose`` (the best particle's moved pose), ``M`` (offspring
+    that count), ``sums`` (the four signed sums) and ``mean_pose`` = (sum_x / (65536 M), sum_y / (65536 M), atan2(sum_sin,
+    sum_cos)): sums of integers, the same bits on every call; NaNs when M == 0."""
+    w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
+    w = np.ascontiguousarray(w).reshape(-1).view(np.uint64)
+    if w.size != _lib.MCL_REPORT:
+        raise ValueError(f"{w.size} words: want {_lib.MCL_REPORT}")
+    M = int(w[10])
+    sx, sy, sc, ss = (int(v) for v in w[11:15].view(np.int64))
+    mean = (sx / (65536.0 * M), sy / (65536.0 * M), math.atan2(float(ss), float(sc))) if M else (math.nan,) * 3
+    return dict(cmin=int(w[0]), best=int(w[1]), W=int(w[2]), positive=int(w[3]), u0=int(w[4]), in_range=int(w[5]), distinct=int(w[6]),
+                best_pose=tuple(float(v) for v in w[7:10].view(np.float64)), M=M, sums=(sx, sy, sc, ss), mean_pose=mean)
+
+
 # ----------------------------------------------------------------------------
 # Lidar model + polar spoke LUT (Utils/OccupancyGrid.py:22-57)
 # ----------------------------------------------------------------------------
@@ -1182,6 +1218,33 @@ class ParticleEngine:
         cost = w >> np.uint64(16)
         return dict(cost=cost, heading=(w & np.uint64(0xffff)).astype(np.int64), score=-(cost.astype(np.float64) * (1.0 / cost_scale)),
                     xs=lat.xs, ys=lat.ys, thetas=lat.thetas)
+
+    def mcl_step(self, level, p_field, d_in, d_out, N, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift, d_report,
+                 d_ancestor=None):
+        """One step of Monte-Carlo localisation (include/slam2d.h, slam2d_mcl_step): the N poses of ``d_in`` moved by ``motion`` =
+        (dfwd, dside, dturn) with noise of amplitudes ``amp``, weighed against the field that ``field_build`` -- the full build
+        -- left in slot ``p_field`` of ``level`` for the one scan ``d_ranges[0..beams)``, resampled into ``d_out`` (another
+        buffer of the same row length, 3 or more doubles per pose).  ``d_lut``, ``shift``: ``weight_table`` on the device;
+        ``d_report``: 16 int64 words (``mcl_report_host`` decodes them); ``d_ancestor``: None or [N] int32.  Five launches on the
+        current stream, no synchronisation; the scratch is kept and grown."""
+        if not 0 <= p_field < level.P:
+            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        stride = d_in.shape[-1] if d_in.dim() > 1 else 3
+        if (d_out.shape[-1] if d_out.dim() > 1 else 3) != stride or d_in.numel() < N * stride or d_out.numel() < N * stride:
+            raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {N} poses of one row length")
+        if d_report.numel() < _lib.MCL_REPORT or (d_ancestor is not None and d_ancestor.numel() < N):
+            raise ValueError("d_report wants 16 words, d_ancestor N")
+        n = int(self.L.slam2d_mcl_work(N))
+        if n < 0:
+            check(n, "slam2d_mcl_work")
+        work = getattr(self, "_mcl_work", None)
+        if work is None or work.numel() < n:
+            work = self._mcl_work = torch.empty(n, dtype=torch.int64, device=self.device)
+        check(self.L.slam2d_mcl_step(C.byref(self.lidar_c), C.byref(level.c), p_field, N, _ptr(d_in), _ptr(d_out), stride,
+                                     (C.c_double * 3)(*[float(v) for v in motion]), (C.c_double * 3)(*[float(v) for v in amp]),
+                                     int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff, _ptr(d_ranges), int(outside_cost),
+                                     _ptr(d_lut), d_lut.numel(), int(shift), _ptr(d_ancestor), _ptr(work), _ptr(d_report), _stream()),
+              "slam2d_mcl_step")
 
     def grid_update(self, d_pose, stride, d_ranges, d_beam_shift=None):
         self._before_update()

@@ -1,0 +1,168 @@
+"""``Localiser``: Monte-Carlo localisation in a map that is already built -- follow a robot through it, scan by scan.
+
+N pose hypotheses live on the device.  One call per scan (slam2d_mcl_step, include/slam2d.h) moves them by the odometry
+increment, weighs them against ONE field of the map built once, resamples them and leaves the new set where it was: a scan
+costs an upload of its ranges and, if the estimate is wanted at once, a download of 128 bytes.  The step is defined in integers
+and rounded IEEE operations, so a run is the same bits every time; the generator is restated here in NumPy for the host-side
+seeding of the set.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .engine import encode_cost, mcl_report_host, pinned_stream, weight_table
+from .matcher import covering_window
+
+_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_MASK = np.uint64(0xffffffff)
+_IH_STD = math.sqrt(4.0 / 3.0)                                 # std of the Irwin-Hall noise g at amplitude 1
+# draws of the generator: 0-2 are the step's own (include/slam2d.h); the host-side seeding takes the next ones of the same counter
+_DRAW_SPREAD, _DRAW_UNIFORM = (3, 4, 5), 6
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al. 2011) as slam2d_mcl_step runs it: ``counter`` four 32-bit words (scalars or arrays that
+    broadcast), ``key`` two; uint32 [..., 4]."""
+    c = [v & _MASK for v in np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) for v in counter])]
+    k0, k1 = (int(v) & 0xffffffff for v in key)
+    for _ in range(10):
+        p0, p1 = np.uint64(_M0) * c[0], np.uint64(_M1) * c[2]                  # (32 x 32 bits: exact in 64)
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & _MASK, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & _MASK]
+        k0, k1 = (k0 + _W0) & 0xffffffff, (k1 + _W1) & 0xffffffff
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def _words(N, draws, seed, scan):
+    seed, scan = int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff
+    n = np.arange(N, dtype=np.uint64).reshape(-1, 1)
+    j = np.asarray(draws, dtype=np.uint64).reshape(1, -1)
+    return philox4x32_10((n, j, scan & 0xffffffff, scan >> 32), (seed & 0xffffffff, seed >> 32))
+
+
+def noise(N, draws, seed, scan):
+    """g [N, len(draws)] of the step's definition: the four words of counter (n, draw, scan) summed as int32, times 2^-31."""
+    return _words(N, draws, seed, scan).view(np.int32).astype(np.int64).sum(axis=-1).astype(np.float64) * 2.0 ** -31
+
+
+def odometry_motion(prev, cur):
+    """(dfwd, dside, dturn): the step from raw odometry pose ``prev`` to ``cur`` (dicts with x, y, theta, or triples), in the
+    frame of ``prev``."""
+    (x0, y0, t0), (x1, y1, t1) = (((p["x"], p["y"], p["theta"]) if isinstance(p, dict) else p) for p in (prev, cur))
+    dx, dy = float(x1) - float(x0), float(y1) - float(y0)
+    c, s = math.cos(t0), math.sin(t0)
+    return c * dx + s * dy, c * dy - s * dx, float(t1) - float(t0)
+
+
+def _ranges_of(reading_or_ranges, beams):
+    rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
+    rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
+    if rng.shape != (beams,):
+        raise ValueError(f"ranges of shape {rng.shape}: want ({beams},)")
+    return rng
+
+
+class Localiser:
+    """Monte-Carlo localisation in ``matcher``'s map, taken as static.
+
+    ``window = (cx, cy, half)``: the square the robot stays in; the constructor builds the field of ``matcher``'s ``level``
+    ('fine' or 'coarse') that covers it plus lidarMaxRange ONCE, as ``ScanMatcher.searchPoses`` does (the map grows to hold
+    that frame), in a level of its own.  ``particles``: the size of the set; ``sigma = (fwd, side, turn)``: the standard
+    deviations of the motion noise per step (metres, metres, radians; the step's amplitudes are these / sqrt(4/3));
+    ``temperature``: of the weights (``engine.weight_table``; 1.0 is the reference's soft-max); ``seed``: the generator's key;
+    ``outside_cost``: what an in-range beam that ends outside the field pays (default: free space as the field encodes it).
+    Seed the set with ``seed_at``, ``seed_from_peaks`` or ``seed_uniform``, then ``step`` or ``run``."""
+
+    def __init__(self, matcher, window, particles=4096, level="fine", sigma=(0.05, 0.05, 0.02), temperature=1.0, seed=0,
+                 outside_cost=None):
+        self.matcher = matcher
+        self.N = int(particles)
+        if not 1 <= self.N <= _lib.MCL_MAX_PARTICLES:
+            raise ValueError(f"particles wants 1 .. {_lib.MCL_MAX_PARTICLES}, not {particles!r}")
+        self.sigma = tuple(float(v) for v in sigma)
+        if len(self.sigma) != 3 or not all(math.isfinite(v) and v >= 0 for v in self.sigma):
+            raise ValueError(f"sigma = (fwd, side, turn) wants three finite numbers >= 0, not {sigma!r}")
+        self.amp = tuple(v / _IH_STD for v in self.sigma)
+        self.seed = int(seed) & 0xffffffffffffffff
+        self.scan = 0                                          # the number of the next scan: part of the generator's counter
+        cx, cy, half = self.window = covering_window(None, window)
+        og = matcher.og
+        lv = self.level = matcher.covering_level(level, half, shared=False)
+        self.outside_cost = int(encode_cost(lv.floor_value, lv.cost_scale)) if outside_cost is None else int(outside_cost)
+        lut, self.shift = weight_table(lv.cost_scale, temperature)
+        with pinned_stream():
+            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = self.eng = og.engine()
+            eng.field_build(lv, eng.to_device([[cx, cy]]), 2)
+            eng.take_flags()
+        dev = eng.device
+        self.d_lut = torch.from_numpy(lut.view(np.int32)).to(dev)
+        self.d_pose = [torch.zeros((self.N, 3), dtype=torch.float64, device=dev) for _ in range(2)]     # ping-pong
+        self.cur = 0
+        self.d_ancestor = torch.empty(self.N, dtype=torch.int32, device=dev)
+        self.d_report = torch.empty(_lib.MCL_REPORT, dtype=torch.int64, device=dev)
+        self.d_ranges = torch.empty(og.numSamplesPerRev, dtype=torch.float64, device=dev)
+
+    # ---- the set ----
+    def set_poses(self, poses):
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        if len(poses) != self.N:
+            raise ValueError(f"{len(poses)} poses for a set of {self.N}")
+        self.d_pose[self.cur].copy_(torch.from_numpy(poses))
+        return poses
+
+    def seed_at(self, pose, spread):
+        """The set around ``pose`` = (x, y, theta): pose + spread * g / sqrt(4/3) per component, g the step's noise at draws 3-5 of
+        the current scan number.  ``spread``: one standard deviation for all three, or (sx, sy, stheta).  Returns the poses."""
+        return self.seed_from_peaks([pose], spread)
+
+    def seed_from_peaks(self, peaks, spread):
+        """The set shared out in turn among ``peaks`` -- ``Peak``s of ``ScanMatcher.searchPoses`` or (x, y, theta) triples:
+        particle n around peak n mod len(peaks), spread as in ``seed_at``."""
+        centres = np.array([[float(p.x), float(p.y), float(p.theta)] if hasattr(p, "theta") else [float(v) for v in p[:3]] for p in peaks])
+        if not len(centres):
+            raise ValueError("no peaks")
+        sp = np.broadcast_to(np.asarray(spread, dtype=np.float64), (3,))
+        g = noise(self.N, _DRAW_SPREAD, self.seed, self.scan)
+        return self.set_poses(centres[np.arange(self.N) % len(centres)] + (sp / _IH_STD) * g)
+
+    def seed_uniform(self):
+        """The set uniform over the window and the full turn: words 0-2 of draw 6 of the current scan number, over 2^32."""
+        cx, cy, half = self.window
+        u = _words(self.N, (_DRAW_UNIFORM,), self.seed, self.scan)[:, 0, :3].astype(np.float64) * 2.0 ** -32
+        return self.set_poses(np.column_stack([cx + (2 * u[:, 0] - 1) * half, cy + (2 * u[:, 1] - 1) * half, -math.pi + 2 * math.pi * u[:, 2]]))
+
+    def poses(self):
+        """The current set, downloaded: [N, 3]."""
+        return self.d_pose[self.cur].cpu().numpy()
+
+    # ---- the filter ----
+    def _enqueue(self, d_ranges, motion, d_report):
+        eng = self.eng
+        eng.mcl_step(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], self.N, motion, self.amp, self.seed, self.scan,
+                     d_ranges, self.outside_cost, self.d_lut, self.shift, d_report, self.d_ancestor)
+        self.cur = 1 - self.cur
+        self.scan += 1
+
+    def step(self, reading_or_ranges, motion):
+        """One scan: the set moved by ``motion`` = (dfwd, dside, dturn) in the robot's own previous frame, weighed against the scan
+        and resampled.  One call, one download of 128 bytes: the report as ``engine.mcl_report_host`` decodes it --
+        ``mean_pose`` is the estimate."""
+        self.d_ranges.copy_(torch.from_numpy(_ranges_of(reading_or_ranges, self.d_ranges.numel())))
+        self._enqueue(self.d_ranges, motion, self.d_report)
+        return mcl_report_host(self.d_report)
+
+    def run(self, readings):
+        """A log: the motion of scan i is the step from raw odometry pose i - 1 to i in the frame of pose i - 1 (nothing for the
+        first scan).  Every scan is enqueued without a synchronisation, the reports go to one [S, 16] device array, and ONE
+        download ends the call.  Returns the list of decoded reports."""
+        beams = self.d_ranges.numel()
+        rng = np.stack([_ranges_of(r, beams) for r in readings])
+        with pinned_stream():
+            d_rng = torch.from_numpy(rng).to(self.eng.device)
+            d_rep = torch.empty((len(readings), _lib.MCL_REPORT), dtype=torch.int64, device=self.eng.device)
+            for i in range(len(readings)):
+                self._enqueue(d_rng[i], odometry_motion(readings[i - 1], readings[i]) if i else (0.0, 0.0, 0.0), d_rep[i])
+            host = d_rep.cpu().numpy()
+        return [mcl_report_host(row) for row in host]

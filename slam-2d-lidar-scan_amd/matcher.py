@@ -324,9 +324,10 @@ class ScanMatcher:
             return dict(pose_mean=(est[0] + mean[0], est[1] + mean[1], est[2] + mean[2]), cov=mom["cov"][0], sum_w=sum_w,
                         log_confidence=float(mom["best_score"][0]) + math.log(sum_w) if sum_w > 0 else float("nan"))
 
-    def covering_level(self, level, half):
+    def covering_level(self, level, half, shared=True):
         """The cached level whose field covers a window of half-edge ``half`` at this matcher's fine or coarse configuration
-        (step, sigma and miss probability exactly as fine_level() / coarse_level() derive them), with a cube of one angle."""
+        (step, sigma and miss probability exactly as fine_level() / coarse_level() derive them), with a cube of one angle.
+        ``shared=False``: a level of the caller's own, for a field that has to outlive the call (Localiser)."""
         if level not in ("fine", "coarse"):
             raise ValueError("level is 'fine' or 'coarse'")
         unit = self.og.unitGridSize
@@ -335,10 +336,12 @@ class ScanMatcher:
         else:
             step, sigma, miss = self.coarseFactor * unit, self.scanSigmaInNumGrid / self.coarseFactor, self.missMatchProbAtCoarse   # :54-55
         ctor = covering_radius(half, self.og.lidarMaxRange, step, unit)
+        kw = dict(step=step, sigma=sigma, miss_prob=miss, search_radius_ctor=ctor, radius=step, half_rad=0.0, fine=True,
+                  move_sigma=self.moveRSigma, max_move_dev=self.maxMoveDeviation, turn_sigma=self.turnSigma)
+        if not shared:
+            return SearchLevel(self.og.lidar, 1, self.og.device, bnb=False, **kw)
         key = ("cover", step, sigma, miss, ctor, self.moveRSigma, self.maxMoveDeviation, self.turnSigma)
-        return _shared_level(self.og, key, step=step, sigma=sigma, miss_prob=miss, search_radius_ctor=ctor, radius=step,
-                             half_rad=0.0, fine=True, move_sigma=self.moveRSigma, max_move_dev=self.maxMoveDeviation,
-                             turn_sigma=self.turnSigma)
+        return _shared_level(self.og, key, **kw)
 
     def scorePoses(self, poses, reading_or_ranges, level="fine", window=None):
         """How well a scan fits at N free poses anywhere in the map (include/slam2d.h, slam2d_score_poses): the reference's score
