@@ -1,0 +1,527 @@
+"""slam2d_score_poses, slam2d_search_lattice and slam2d_mcl_step in every field slot of a level of three, and in frames that are
+not the square 289 x 289 of the other files: the three calls take a slot ``p_field`` and read its frame record, clip it
+(frame_clip), step to its image by fmax * fpitch and test a beam for inside against the clipped size -- none of which a one-slot
+level with p_field = 0 and a square frame can tell from its mistaken neighbours.  Compared as tests/test_gpu_score.py,
+test_gpu_search.py and test_gpu_mcl.py compare: np.array_equal on bits against tests/score_yardstick.py, lattice_yardstick.py and
+mcl_yardstick.py, which read the DEVICE's field and frame and the device's cos / sin (slam2d_device_sincos); no tolerance.
+
+A. Built slots: one full field_build of a level of P = 3 over three maps of different content, at centres whose frames come out
+   289 x 289, 288 x 289 and 289 x 288 (fh x fw) -- frame_extent's expression, restated here on the CPU.
+B. Crafted slots, written into the same level: an oversized record over a full fmax x fmax image (the definition: the record
+   clipped), a short wide frame, a frame of one cell; every cell outside a slot's frame holds a poison cost of that slot's own.
+
+What keeps a case from being vacuous -- the slots differ, beams end on both sides of every edge, the filter resamples for real --
+is asserted on the yardstick alone, before the device's result is looked at.  Lidar and world of tests/test_score_host.py: unit
+0.1 m, range 4 m, FOV pi, 60 beams; the level of ScanMatcher.covering_level("fine", 8.0): reach 14.4 m, fmax 290, fpitch 304."""
+import ctypes
+import importlib
+
+import numpy as np
+import pytest
+
+import lattice_yardstick as lyard
+import mcl_yardstick as mcl
+import score_yardstick as yard
+import test_gpu_mcl as tmcl
+import test_gpu_score as tscore
+import test_gpu_search as tsearch
+from test_score_host import BEAMS, FOV, INIT, ORIGIN, R, SIZE, UNIT, WALL
+
+pytestmark = pytest.mark.gpu
+
+_lib = importlib.import_module("slam-2d-lidar-scan_amd._lib")
+
+SMP = tscore.SMP                                               # scan sigma 1 cell, fine miss probability 0.15 ** (2 / 1)
+P = 3                                                          # the smallest count with a first, a middle and a last slot
+SEEDS = (3, 11, 23)                                            # the three worlds
+CENTRES = ((0.29, -0.41), (1.75, 0.29), (-0.41, 1.75))         # (cx, cy) of the three frames
+SIZES = ((289, 289), (289, 288), (288, 289))                   # (fh, fw) they give: asserted on the CPU and against level.frames()
+FMAX, FPITCH = 290, 304
+TEMPERATURE, AMP, MOTION = tmcl.TEMPERATURE, tmcl.AMP, tmcl.MOTIONS[0]
+POISON = (0x51515151, 0x62626262, 0x73737373)                  # per slot, beyond any cost of a crafted image
+CRAFTED_COST = 0x40000000                                      # the largest cost of a crafted image
+CRAFTED = ((-14.11, -13.77, FMAX + 7, FPITCH + 5), (3.3, -7.25, 37, 101), (-2.05, 6.4, 1, 1))      # (xlo, ylo, fh, fw) of the records
+
+
+def frame_cells(c, reach, step):
+    """frame_extent (csrc/slam2d.hip) for one axis: the size in cells of the frame about centre coordinate c."""
+    return int(((c + reach) - (c - reach)) / step) + 1
+
+
+def level_kw():
+    """SearchLevel's arguments as ScanMatcher.covering_level("fine", 8.0) forms them from SMP."""
+    matcher = importlib.import_module("slam-2d-lidar-scan_amd.matcher")
+    _, _, sigma, move_sigma, max_move_dev, turn_sigma, miss, factor = SMP
+    return dict(step=UNIT, sigma=sigma, miss_prob=miss ** (2 / factor), search_radius_ctor=matcher.covering_radius(8.0, R, UNIT, UNIT),
+                radius=UNIT, half_rad=0.0, fine=True, move_sigma=move_sigma, max_move_dev=max_move_dev, turn_sigma=turn_sigma)
+
+
+# ---- the inputs of one slot, chosen on the CPU from its frame alone ----
+def pick(frame, pose, ranges):
+    """The pose, nudged until no quotient of its beams is near an integer (as tests/test_gpu_score.py picks its poses: well away
+    from truncation ties)."""
+    for k in range(50):
+        p = (pose[0] + 0.0007 * k, pose[1] + 0.0011 * k, pose[2] + 0.0013 * k)
+        if yard.min_distance_to_integer(frame, UNIT, [p], ranges, FOV, R) > 1e-4:
+            return p
+    raise AssertionError(pose)
+
+
+def edge_poses(frame, fh, fw):
+    """Twelve poses within two cells of the right edge, the top edge and their corner, on either side, for a scan of short
+    ranges: its beams end in the last column and row and in the first ones outside.  Four more a metre or two from the edges,
+    one of them outside and looking in, for a whole scan."""
+    xlo, ylo = frame
+    w, h = fw * UNIT, fh * UNIT
+    xr, yt = xlo + w, ylo + h
+    xm, ym = xlo + 0.57 * w, ylo + 0.43 * h
+    close = [(xr - 0.063, ym, 0.3), (xr - 0.031, ym + 0.11 * h, -0.4), (xr + 0.042, ym, np.pi - 0.2), (xr + 0.13, ym - 0.07 * h, 2.7),
+             (xm, yt - 0.063, np.pi / 2 + 0.3), (xm + 0.09 * w, yt - 0.031, np.pi / 2 - 0.4), (xm, yt + 0.042, -np.pi / 2 + 0.2),
+             (xm - 0.06 * w, yt + 0.13, -1.9),
+             (xr - 0.05, yt - 0.05, 0.8), (xr + 0.07, yt + 0.06, -2.4), (xr - 0.04, yt + 0.03, -0.6), (xr + 0.03, yt - 0.04, 2.2)]
+    far = [(xr - 1.5, ym, 0.1), (xm, yt - 2.0, 1.5), (xr - 2.5, yt - 1.2, 0.8), (xr + 1.0, yt + 0.8, -2.3)]
+    return close, far
+
+
+def slot_inputs(p, frame, fh, fw, near, near_scans, scans, small=False, short_scan=False):
+    """Everything the three calls are given in one slot.  ``near``: poses well inside the frame with a scan each; ``small``: the
+    crafted slots' sizes (a 5 x 4 lattice, 70 particles, their scan short on every other beam); ``short_scan``: ... on every beam (a
+    frame of one cell, which a beam of a metre never ends in)."""
+    rs = np.random.RandomState(100 + p)
+    xlo, ylo = frame
+    xr, yt = xlo + fw * UNIT, ylo + fh * UNIT
+    short = rs.uniform(0.02, 0.5, BEAMS)
+    close, far = edge_poses(frame, fh, fw)
+    poses = list(near) + close + far
+    ranges = list(near_scans) + [short] * len(close) + [scans[i] for i in range(len(far))]
+    poses = np.array([pick(frame, q, r) for q, r in zip(poses, ranges)])
+    span_x, span_y = min(6.03, 0.6 * fw * UNIT), min(4.52, 0.6 * fh * UNIT)      # from inside the frame to beyond its right and top edges
+    if small:
+        lat = (5, 4, 8, xr - span_x, 1.31 * span_x / 5, yt - span_y, 1.33 * span_y / 4, -np.pi + 0.1, np.pi / 4)
+    else:
+        lat = (9, 7, 8, xr - span_x, 1.31 * span_x / 9, yt - span_y, 1.33 * span_y / 7, -np.pi + 0.1, np.pi / 4)
+    N = 70 if small else 130
+    if small:       # a cloud about a pose near the right and top edges: beams on both sides of both
+        about = (xr - min(0.4, 0.5 * fw * UNIT), yt - min(0.35, 0.5 * fh * UNIT), 0.7)
+        spread = (0.3, 0.3, 0.3) if not short_scan else (0.08, 0.08, 0.5)
+    else:           # ... about pose 2 of the slot's walk, well inside its frame
+        about, spread = tuple(near[2]), (0.06, 0.06, 0.04)
+    cloud = np.array(about) + rs.standard_normal((N, 3)) * np.array(spread)
+    scan = scans[2]
+    if small:       # every other beam short, or all of them: ends within a few cells of the cloud, on either side of the edges
+        scan = short if short_scan else np.where(np.arange(BEAMS) % 2 == 1, 2 * short, scans[2])
+    return dict(poses=poses, ranges=np.array(ranges), lat=lat, scan=scan, cloud=cloud, seed=0xfeedface00 + p, scan_no=(1 << 33) + 7 * p)
+
+
+def beam_cells(frame, poses, ranges, cos, sin):
+    """(pose index, cx, cy) of every in-range beam whose quotients pass the guard: the yardstick's own expressions."""
+    ranges = np.asarray(ranges, dtype=np.float64)
+    out = []
+    for n, (x, y, th) in enumerate(np.asarray(poses, dtype=np.float64).reshape(-1, 3)):
+        r = ranges if ranges.ndim == 1 else ranges[n]
+        _, px, py = yard.endpoints(x, y, th, r, FOV, len(r), R, cos[n], sin[n])
+        qx, qy = yard.quotients(px, py, frame[0], frame[1], UNIT)
+        with np.errstate(invalid="ignore"):
+            ok = (np.abs(qx) < 1e9) & (np.abs(qy) < 1e9)
+        out.append(np.column_stack([np.full(int(ok.sum()), n), qx[ok].astype(int), qy[ok].astype(int)]))
+    return np.vstack(out)
+
+
+def edge_classes(frame, fh, fw, poses, ranges, cos, sin):
+    """How many beams end in the last column, in the first column outside, in the last row and in the first row outside -- the
+    other coordinate inside the frame."""
+    _, cx, cy = beam_cells(frame, poses, ranges, cos, sin).T
+    col, row = (cx >= 0) & (cx < fw), (cy >= 0) & (cy < fh)
+    return [int(((cx == fw - 1) & row).sum()), int(((cx == fw) & row).sum()), int(((cy == fh - 1) & col).sum()), int(((cy == fh) & col).sum())]
+
+
+def yardsticks(inp, field, frame, scale, free, lut, shift, sincos):
+    """The three definitions on one field and frame: rows [N, 8]; (cost, inside, in_range) [nth, ny, nx] and the packed words;
+    the dict of mcl_yardstick.step.  ``sincos``: angles -> the device's (cos, sin)."""
+    poses, ranges, lat = inp["poses"], inp["ranges"], inp["lat"]
+    c, s = sincos(np.array([yard.beam_angles(q[2], FOV, BEAMS) for q in poses]))
+    rows = yard.score_poses(field, frame, scale, UNIT, poses, ranges, FOV, R, c, s)
+    lc, ls = sincos(lyard.beam_angles(lat, FOV, BEAMS))
+    parts = lyard.costs(field, frame, scale, UNIT, lat, inp["scan"], FOV, R, free, lc, ls)
+    step = mcl.step(field, frame, scale, UNIT, inp["cloud"], MOTION, AMP, inp["seed"], inp["scan_no"], inp["scan"], FOV, R, free, lut, shift,
+                    sincos)
+    return dict(rows=rows, parts=parts, words=lyard.pack(parts[0]), step=step)
+
+
+def both_sides(inp, want, frame, fh, fw, sincos):
+    """On the yardstick: the edge classes of the three input sets (the filter's: of its MOVED poses)."""
+    c, s = sincos(np.array([yard.beam_angles(q[2], FOV, BEAMS) for q in inp["poses"]]))
+    lat_poses = lyard.poses(inp["lat"]).reshape(-1, 3)
+    lc, ls = sincos(np.array([yard.beam_angles(q[2], FOV, BEAMS) for q in lat_poses]))
+    moved = want["step"]["moved"]
+    mc, ms = sincos(np.array([yard.beam_angles(q[2], FOV, BEAMS) for q in moved]))
+    return dict(score=edge_classes(frame, fh, fw, inp["poses"], inp["ranges"], c, s),
+                search=edge_classes(frame, fh, fw, lat_poses, inp["scan"], lc, ls),
+                mcl=edge_classes(frame, fh, fw, moved, inp["scan"], mc, ms))
+
+
+def same_results(a, b):
+    return (np.array_equal(a["rows"], b["rows"]), np.array_equal(a["words"], b["words"]),
+            a["step"]["out"].tobytes() == b["step"]["out"].tobytes() and np.array_equal(a["step"]["report"], b["step"]["report"]))
+
+
+# ---- the device ----
+@pytest.fixture(scope="module")
+def pkg():
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return importlib.import_module("slam-2d-lidar-scan_amd")
+
+
+def memo_sincos(eng):
+    """slam2d_device_sincos of an array of angles, each array asked for once."""
+    seen = {}
+
+    def sincos(angles):
+        a = np.ascontiguousarray(angles, dtype=np.float64)
+        key = (a.shape, a.tobytes())
+        if key not in seen:
+            seen[key] = tscore.device_sincos(eng, a)
+        return seen[key]
+    return sincos
+
+
+def run_score(eng, level, p, inp):
+    """slam2d_score_poses of slot p: through ParticleEngine.score_poses where ``level`` is a SearchLevel, at the C ABI with a
+    poisoned buffer where it is a Slam2dLevel (a view).  Rows as float64 [N, 8] on the host."""
+    import torch
+    engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
+    N = len(inp["poses"])
+    d_pose, d_rng = eng.to_device(inp["poses"]), eng.to_device(inp["ranges"])
+    if hasattr(level, "t"):
+        return eng.score_poses(level, p, d_pose, 3, N, d_rng, BEAMS).cpu().numpy()
+    out = torch.full((N, _lib.SCORE_STRIDE), -1, dtype=torch.int64, device=eng.device)
+    _lib.check(eng.L.slam2d_score_poses(ctypes.byref(eng.lidar_c), ctypes.byref(level), p, N, d_pose.data_ptr(), 3, d_rng.data_ptr(), BEAMS,
+                                        out.data_ptr(), engine._stream()), "slam2d_score_poses")
+    return out.cpu().numpy().view(np.float64)
+
+
+def run_search(eng, level, p, inp, free):
+    """slam2d_search_lattice of slot p, as run_score: the image as uint64 [ny, nx]."""
+    import torch
+    engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
+    lat = inp["lat"]
+    d_rng = eng.to_device(inp["scan"])
+    if hasattr(level, "t"):
+        return eng.search_lattice(level, p, lat, d_rng, free).cpu().numpy().view(np.uint64)
+    nx, ny, nth = lat[:3]
+    n = eng.L.slam2d_search_lattice_work(ctypes.byref(eng.lidar_c), nx, ny, nth)
+    assert n == 2 * nth * BEAMS
+    work = torch.full((n,), -1, dtype=torch.int64, device=eng.device)
+    out = torch.full((ny, nx), -1, dtype=torch.int64, device=eng.device)
+    _lib.check(eng.L.slam2d_search_lattice(ctypes.byref(eng.lidar_c), ctypes.byref(level), p, nx, ny, nth, *[float(v) for v in lat[3:]],
+                                           d_rng.data_ptr(), free, work.data_ptr(), out.data_ptr(), engine._stream()), "slam2d_search_lattice")
+    return out.cpu().numpy().view(np.uint64)
+
+
+def run_mcl(eng, level, p, inp, free, lut, shift):
+    """slam2d_mcl_step of slot p, as run_score; every buffer poisoned with 0xff bytes.  The dict tests/test_gpu_mcl.py compares."""
+    import torch
+    engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
+    cloud = np.ascontiguousarray(inp["cloud"], dtype=np.float64)
+    N = len(cloud)
+    full = lambda shape, dt: torch.full(shape, -1, dtype=dt, device=eng.device)
+    d_in, d_rng = eng.to_device(cloud), eng.to_device(inp["scan"])
+    d_lut = torch.from_numpy(np.asarray(lut, dtype=np.uint32).view(np.int32).copy()).to(eng.device)
+    rep, out, anc = full((_lib.MCL_REPORT,), torch.int64), full((N, 3), torch.int64).view(torch.float64), full((N,), torch.int32)
+    if hasattr(level, "t"):
+        eng.mcl_step(level, p, d_in, out, N, MOTION, AMP, inp["seed"], inp["scan_no"], d_rng, free, d_lut, shift, rep, anc)
+    else:
+        work = full((eng.L.slam2d_mcl_work(N),), torch.int64)
+        _lib.check(eng.L.slam2d_mcl_step(ctypes.byref(eng.lidar_c), ctypes.byref(level), p, N, d_in.data_ptr(), out.data_ptr(), 3,
+                                         (ctypes.c_double * 3)(*MOTION), (ctypes.c_double * 3)(*AMP), inp["seed"], inp["scan_no"],
+                                         d_rng.data_ptr(), free, d_lut.data_ptr(), len(lut), shift, anc.data_ptr(), work.data_ptr(),
+                                         rep.data_ptr(), engine._stream()), "slam2d_mcl_step")
+    return dict(out=out.cpu().numpy(), ancestors=anc.cpu().numpy(), report=rep.cpu().numpy().view(np.uint64))
+
+
+def run_all(eng, level, p, inp, free, lut, shift):
+    return dict(rows=run_score(eng, level, p, inp), words=run_search(eng, level, p, inp, free), step=run_mcl(eng, level, p, inp, free, lut, shift))
+
+
+def same_bytes(a, b, what):
+    assert a["rows"].tobytes() == b["rows"].tobytes(), (what, "slam2d_score_poses")
+    assert a["words"].tobytes() == b["words"].tobytes(), (what, "slam2d_search_lattice")
+    for key in ("out", "ancestors", "report"):
+        assert a["step"][key].tobytes() == b["step"][key].tobytes(), (what, "slam2d_mcl_step", key)
+
+
+@pytest.fixture(scope="module")
+def built(pkg):
+    """Part A's scene: three maps of different content, grown to hold their frames; the level of three with its fields as ONE
+    full build left them, downloaded once; every slot's inputs and, from the yardsticks, what the three calls must give there
+    and what they would give on either other slot's field and frame.  Nothing here runs a call under test."""
+    import torch
+    engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
+    synth = importlib.import_module("slam-2d-lidar-scan_amd.synth")
+    dev = torch.device("cuda:0")
+    kw = level_kw()
+    lidar = engine.LidarModel.get(UNIT, R, FOV, BEAMS, WALL)
+    lv = engine.SearchLevel(lidar, P, dev, bnb=False, **kw)
+    # the very level of ScanMatcher.covering_level("fine", 8.0), but for its particle count
+    og = pkg.OccupancyGrid(SIZE, SIZE, INIT, UNIT, FOV, BEAMS, R, WALL)
+    ref = pkg.ScanMatcher(og, *SMP).covering_level("fine", 8.0, shared=False)
+    for name in ("step", "reach", "log_miss", "floor_value", "cost_scale", "blur_radius", "fmax", "fpitch", "wmax", "ncell", "ntheta", "fine",
+                 "kmax", "tmax", "bnb"):
+        assert getattr(lv.c, name) == getattr(ref.c, name), name
+    assert (lv.fmax, lv.fpitch, lv.P) == (FMAX, FPITCH, P)
+    # the frame sizes, on the CPU
+    assert [(frame_cells(cy, lv.reach, UNIT), frame_cells(cx, lv.reach, UNIT)) for cx, cy in CENTRES] == list(SIZES)
+    worlds = [synth.make_world(SIZE, UNIT, seed=s, n_boxes=25) for s in SEEDS]
+    maps = []
+    for world, (cx, cy) in zip(worlds, CENTRES):
+        m = engine.MapState.create(SIZE, SIZE, INIT, UNIT, dev)
+        m.upload(*synth.counts_from_world(world))
+        m.ensure_contains([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach], UNIT)      # every frame inside its map
+        maps.append(m)
+    eng = engine.ParticleEngine(lidar, maps, dev)
+    eng.field_build(lv, eng.to_device(CENTRES), 2)
+    assert not eng.take_flags(fatal=0xffffffff).any()
+    fr = lv.frames()
+    assert [(int(f["fh"]), int(f["fw"])) for f in fr] == list(SIZES)
+    assert [(float(f["xlo"]), float(f["ylo"])) for f in fr] == [(cx - lv.reach, cy - lv.reach) for cx, cy in CENTRES]
+    free = int(engine.encode_cost(lv.floor_value, lv.cost_scale))
+    lut, shift = engine.weight_table(lv.c.cost_scale, TEMPERATURE)
+    sincos = memo_sincos(eng)
+    slots = []
+    for p in range(P):
+        field = lv.field_cost(p).copy()
+        assert field.shape == SIZES[p] and (field > 0).any() and (field == 0).any()       # free space and walls
+        walk = np.array(synth.random_walk(worlds[p], UNIT, ORIGIN, 12, seed=5))
+        scans = np.array([synth.raycast(worlds[p], UNIT, ORIGIN, q, FOV, BEAMS, R) for q in walk])
+        frame = (float(fr[p]["xlo"]), float(fr[p]["ylo"]))
+        near = [tuple(q) for q in walk] + [(q[0] + 0.037, q[1] - 0.012, q[2] + 0.01) for q in walk]
+        inp = slot_inputs(p, frame, *SIZES[p], near, list(scans) * 2, scans)
+        slots.append(dict(field=field, frame=frame, size=SIZES[p], inp=inp, walk=walk, scans=scans))
+    for p, s in enumerate(slots):       # want[q]: slot p's inputs on slot q's field and frame
+        s["want"] = [yardsticks(s["inp"], slots[q]["field"], slots[q]["frame"], lv.c.cost_scale, free, lut, shift, sincos) for q in range(P)]
+        s["sides"] = both_sides(s["inp"], s["want"][p], s["frame"], *s["size"], sincos)
+    torch.cuda.synchronize()
+    return dict(eng=eng, lv=lv, maps=maps, lidar=lidar, kw=kw, dev=dev, free=free, lut=lut, shift=shift, sincos=sincos, slots=slots, worlds=worlds)
+
+
+# ---- A. built slots ----
+def test_preconditions_on_the_host(built):
+    """A wrong slot cannot pass by coincidence: the three fields differ, and for every call and slot the yardstick on that
+    slot's field and frame differs from the yardstick on either other slot's."""
+    slots = built["slots"]
+    for p in range(P):
+        for q in range(p + 1, P):
+            a, b = slots[p]["field"], slots[q]["field"]
+            assert a.shape != b.shape or not np.array_equal(a, b), (p, q)
+            assert not np.array_equal(a[:288, :288], b[:288, :288]), (p, q)       # (and not by their shapes alone)
+            assert slots[p]["frame"] != slots[q]["frame"]
+        for q in range(P):
+            if q != p:
+                assert same_results(slots[p]["want"][p], slots[p]["want"][q]) == (False, False, False), (p, q)
+    assert len(built["lv"].frames()) == P and not built["eng"].take_flags(fatal=0xffffffff).any()      # the build raised no fault bit
+
+
+@pytest.mark.parametrize("p", range(P))
+def test_score_poses_in_a_built_slot(built, p):
+    s = built["slots"][p]
+    want, inp = s["want"][p]["rows"], s["inp"]
+    assert 38 <= len(inp["poses"]) <= 44
+    assert yard.min_distance_to_integer(s["frame"], UNIT, inp["poses"], inp["ranges"], FOV, R) > 1e-4
+    assert min(s["sides"]["score"]) >= 1, s["sides"]["score"]                      # last column, first outside, last row, first outside
+    assert ((want[:, 3] > 0) & (want[:, 3] < want[:, 4])).any() and (want[:24, 3] == want[:24, 4]).all() and (want[:24, 3] > 20).all()
+    tscore.same(run_score(built["eng"], built["lv"], p, inp), want, f"slot {p}")
+    tscore.same(run_score(built["eng"], built["lv"].c, p, inp), want, f"slot {p}, at the C ABI")
+
+
+@pytest.mark.parametrize("p", range(P))
+def test_search_lattice_in_a_built_slot(built, p):
+    s = built["slots"][p]
+    (cost, inside, in_range), want, inp = s["want"][p]["parts"], s["want"][p]["words"], s["inp"]
+    assert inp["lat"][:3] == (9, 7, 8)
+    assert min(s["sides"]["search"]) >= 1, s["sides"]["search"]
+    assert (inside < in_range).any() and (inside == in_range).any() and len(np.unique(tsearch.headings(want))) >= 2
+    xs, ys, _ = lyard.axes(inp["lat"])
+    xr, yt = s["frame"][0] + s["size"][1] * UNIT, s["frame"][1] + s["size"][0] * UNIT
+    assert xs[0] < xr < xs[-1] and ys[0] < yt < ys[-1]                             # the lattice straddles the right and the top edge
+    tsearch.same(run_search(built["eng"], built["lv"], p, inp, built["free"]), want, f"slot {p}")
+    tsearch.same(run_search(built["eng"], built["lv"].c, p, inp, built["free"]), want, f"slot {p}, at the C ABI")
+
+
+@pytest.mark.parametrize("p", range(P))
+def test_mcl_step_in_a_built_slot(built, p):
+    s = built["slots"][p]
+    want, inp = s["want"][p]["step"], s["inp"]
+    assert len(inp["cloud"]) == 130
+    tmcl.lively(want, 130)
+    (xlo, ylo), (fh, fw) = s["frame"], s["size"]
+    assert xlo < s["walk"][2][0] < xlo + fw * UNIT and ylo < s["walk"][2][1] < ylo + fh * UNIT       # the walk pose: inside the frame
+    tmcl.same(run_mcl(built["eng"], built["lv"], p, inp, built["free"], built["lut"], built["shift"]), want, f"slot {p}")
+    tmcl.same(run_mcl(built["eng"], built["lv"].c, p, inp, built["free"], built["lut"], built["shift"]), want, f"slot {p}, at the C ABI")
+
+
+@pytest.mark.parametrize("p", range(P))
+def test_a_one_slot_level_of_map_p_gives_the_bytes_of_slot_p(built, p):
+    """No yardstick: a level of one, built from map p alone at centre p, against slot p of the level of three."""
+    engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
+    s = built["slots"][p]
+    eng1 = engine.ParticleEngine(built["lidar"], [built["maps"][p]], built["dev"])
+    lv1 = engine.SearchLevel(built["lidar"], 1, built["dev"], bnb=False, **built["kw"])
+    eng1.field_build(lv1, eng1.to_device([CENTRES[p]]), 2)
+    assert not eng1.take_flags(fatal=0xffffffff).any()
+    f1 = lv1.frames()[0]
+    assert (int(f1["fh"]), int(f1["fw"]), float(f1["xlo"]), float(f1["ylo"])) == (*s["size"], *s["frame"])
+    assert np.array_equal(lv1.field_cost(0), s["field"])
+    args = (s["inp"], built["free"], built["lut"], built["shift"])
+    same_bytes(run_all(eng1, lv1.c, 0, *args), run_all(built["eng"], built["lv"].c, p, *args), f"slot {p}")
+
+
+def test_slot_0_of_an_offset_view_is_slot_2_of_the_parent(built):
+    """The group calls hand the C ABI level.view(p0, p1): every per-particle pointer advanced to particle p0."""
+    eng, lv = built["eng"], built["lv"]
+    view = lv.view(2, 3)
+    lv.sync_view(view)
+    for p in (2, 0):                                           # (slot 2's inputs, and slot 0's, whose beams leave slot 2's frame elsewhere)
+        args = (built["slots"][p]["inp"], built["free"], built["lut"], built["shift"])
+        same_bytes(run_all(eng, view, 0, *args), run_all(eng, lv.c, 2, *args), f"inputs of slot {p}")
+    mid = lv.view(1, 3)
+    args = (built["slots"][1]["inp"], built["free"], built["lut"], built["shift"])
+    same_bytes(run_all(eng, mid, 1, *args), run_all(eng, lv.c, 2, *args), "slot 1 of view(1, 3)")
+
+
+@pytest.mark.parametrize("p_field", [-1, P])
+def test_the_wrappers_refuse_a_slot_outside_the_level(built, p_field):
+    import torch
+    engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
+    eng, lv, inp = built["eng"], built["lv"], built["slots"][0]["inp"]
+    N = len(inp["cloud"])
+    d_pose, d_rng, d_scan, d_in = eng.to_device(inp["poses"]), eng.to_device(inp["ranges"]), eng.to_device(inp["scan"]), eng.to_device(inp["cloud"])
+    d_lut = torch.from_numpy(built["lut"].view(np.int32).copy()).to(eng.device)
+    full = lambda shape, dt: torch.full(shape, -1, dtype=dt, device=eng.device)
+    out, rep, anc = full((N, 3), torch.int64), full((_lib.MCL_REPORT,), torch.int64), full((N,), torch.int32)
+    eng.search_lattice(lv, 0, inp["lat"], d_scan, built["free"])                   # (the wrappers' scratch exists: a launch would find it)
+    with pytest.raises(ValueError, match="field slot"):
+        eng.score_poses(lv, p_field, d_pose, 3, len(inp["poses"]), d_rng, BEAMS)
+    with pytest.raises(ValueError, match="field slot"):
+        eng.search_lattice(lv, p_field, inp["lat"], d_scan, built["free"])
+    with pytest.raises(ValueError, match="field slot"):
+        eng.mcl_step(lv, p_field, d_in, out.view(torch.float64), N, MOTION, AMP, 1, 2, d_scan, built["free"], d_lut, built["shift"], rep, anc)
+    torch.cuda.synchronize()
+    assert (out == -1).all() and (rep == -1).all() and (anc == -1).all()           # nothing was launched into the caller's buffers
+    if p_field < 0:                                            # the C calls refuse it too and leave their poisoned outputs alone
+        rows, words = full((len(inp["poses"]), _lib.SCORE_STRIDE), torch.int64), full((7, 9), torch.int64)
+        work = full((2 * 8 * BEAMS,), torch.int64)
+        rc = eng.L.slam2d_score_poses(ctypes.byref(eng.lidar_c), ctypes.byref(lv.c), p_field, len(inp["poses"]), d_pose.data_ptr(), 3,
+                                      d_rng.data_ptr(), BEAMS, rows.data_ptr(), engine._stream())
+        rc2 = eng.L.slam2d_search_lattice(ctypes.byref(eng.lidar_c), ctypes.byref(lv.c), p_field, 9, 7, 8, *[float(v) for v in inp["lat"][3:]],
+                                          d_scan.data_ptr(), built["free"], work.data_ptr(), words.data_ptr(), engine._stream())
+        torch.cuda.synchronize()
+        assert rc < 0 and rc2 < 0 and (rows == -1).all() and (words == -1).all() and (work == -1).all()
+
+
+# ---- B. crafted slots ----
+@pytest.fixture(scope="module")
+def crafted_plan(built):
+    """The three crafted images and records, their inputs and the yardsticks' results on the definition: the image clipped to
+    min(fh, fmax) x min(fw, fmax), the record's xlo / ylo.  Host only, but for the device's cos / sin."""
+    engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
+    lv, free, sincos = built["lv"], built["free"], built["sincos"]
+    walk, scans = built["slots"][0]["walk"], built["slots"][0]["scans"]
+    image = np.empty((P, FMAX, FPITCH), dtype=np.uint32)
+    records = lv.frames().copy()
+    plan = []
+    for p, (xlo, ylo, fh, fw) in enumerate(CRAFTED):
+        rs = np.random.RandomState(40 + p)
+        ch, cw = min(fh, FMAX), min(fw, FMAX)                  # frame_clip: fpitch >= fmax
+        image[p] = POISON[p]
+        image[p, :ch, :cw] = rs.randint(0, CRAFTED_COST + 1, size=(ch, cw))
+        records[p]["xlo"], records[p]["ylo"], records[p]["fh"], records[p]["fw"] = xlo, ylo, fh, fw
+        records[p]["xhi"], records[p]["yhi"] = xlo + fw * UNIT, ylo + fh * UNIT
+        xr, yt = xlo + cw * UNIT, ylo + ch * UNIT
+        if p == 0:          # a full image: the walk, inside it
+            near, near_scans = [tuple(q) for q in walk] + [(q[0] + 0.037, q[1] - 0.012, q[2] + 0.01) for q in walk], list(scans) * 2
+        elif p == 1:        # poses all over the short, wide frame
+            near = [(rs.uniform(xlo, xr), rs.uniform(ylo, yt), rs.uniform(-np.pi, np.pi)) for _ in range(24)]
+            near_scans = list(scans) * 2
+        else:               # about the one cell: short ranges; from its middle, ranges that stay in it
+            near = [(xlo + rs.uniform(-0.3, 0.4), ylo + rs.uniform(-0.3, 0.4), rs.uniform(-np.pi, np.pi)) for _ in range(20)]
+            near_scans = [rs.uniform(0.02, 0.5, BEAMS) for _ in range(20)]
+            near += [(xlo + 0.05, ylo + 0.05, th) for th in (0.3, -2.0)] + [(xlo + 0.031, ylo + 0.062, 1.1), (xlo + 2.0, ylo - 1.0, 0.4)]
+            near_scans += [rs.uniform(0.005, 0.028, BEAMS) for _ in range(4)]
+        inp = slot_inputs(p, (xlo, ylo), ch, cw, near, near_scans, scans, small=True, short_scan=p == 2)
+        field = image[p, :ch, :cw].copy()
+        # the filter's temperature from the spread of the yardstick's own costs, so that it resamples for real
+        cost = yardsticks(inp, field, (xlo, ylo), lv.c.cost_scale, free, built["lut"], built["shift"], sincos)["step"]["cost"]
+        spread = float(np.median(cost) - cost.min())
+        lut, shift = engine.weight_table(lv.c.cost_scale, max(spread, 3.0) / 3.0 / lv.c.cost_scale)
+        want = yardsticks(inp, field, (xlo, ylo), lv.c.cost_scale, free, lut, shift, sincos)
+        plan.append(dict(field=field, frame=(xlo, ylo), size=(ch, cw), inp=inp, lut=lut, shift=shift, want=want,
+                         sides=both_sides(inp, want, (xlo, ylo), ch, cw, sincos)))
+    assert len(set(POISON)) == P and min(POISON) > CRAFTED_COST
+    return dict(image=image, records=records, plan=plan)
+
+
+@pytest.fixture
+def crafted(built, crafted_plan):
+    """The crafted images and records in the level for one test -- written the way ScanMatcher._search_to_match writes a record,
+    never through set_field, which rescales the whole level -- and the built ones back behind it."""
+    import torch
+    lv = built["lv"]
+    torch.cuda.synchronize()
+    keep_field, keep_frames = lv.t["field"].clone(), lv.t["frames"].clone()
+    scale = lv.c.cost_scale
+    lv.t["field"].copy_(torch.from_numpy(crafted_plan["image"].view(np.int32)))
+    lv.t["frames"].copy_(torch.from_numpy(crafted_plan["records"].view(np.uint8).reshape(P, -1)))
+    got = lv.frames()
+    assert [(int(f["fh"]), int(f["fw"])) for f in got] == [(fh, fw) for _, _, fh, fw in CRAFTED] and lv.c.cost_scale == scale
+    yield crafted_plan["plan"]
+    torch.cuda.synchronize()
+    lv.t["field"].copy_(keep_field)
+    lv.t["frames"].copy_(keep_frames)
+    torch.cuda.synchronize()
+    for p, s in enumerate(built["slots"]):
+        assert np.array_equal(lv.field_cost(p), s["field"])
+
+
+def test_crafted_preconditions_on_the_host(crafted_plan):
+    plan = crafted_plan["plan"]
+    assert [s["size"] for s in plan] == [(FMAX, FMAX), (37, 101), (1, 1)]
+    for p, s in enumerate(plan):
+        for call in ("score", "search", "mcl"):
+            assert min(s["sides"][call]) >= 1, (p, call, s["sides"][call])         # beams on both sides of every clipped edge
+        rows, (cost, inside, in_range), step = s["want"]["rows"], s["want"]["parts"], s["want"]["step"]
+        assert ((rows[:, 3] > 0) & (rows[:, 3] < rows[:, 4])).any()
+        assert (inside < in_range).any() and (inside > 0).any()
+        N = len(s["inp"]["cloud"])
+        assert N == 70 and 1 < int(step["report"][6]) < N and int(step["report"][3]) > 2 and len(np.unique(step["w"])) > 2
+    # the poison is outside every frame and nowhere inside one
+    img = crafted_plan["image"]
+    for p, s in enumerate(plan):
+        ch, cw = s["size"]
+        assert (img[p, :ch, :cw] < POISON[p]).all() and (img[p, ch:] == POISON[p]).all() and (img[p, :, cw:] == POISON[p]).all()
+    rows = plan[2]["want"]["rows"]
+    assert (rows[:, 1] == 1).any() and (rows[:, 1] == 0).any() and (rows[:, 1] <= 1).all()      # the one cell in the set, or none
+    assert (rows[:, 3] == BEAMS).any()                                                          # (every beam of a pose in the one cell)
+
+
+@pytest.mark.parametrize("p", range(P))
+def test_score_poses_in_a_crafted_slot(built, crafted, p):
+    s = crafted[p]
+    assert yard.min_distance_to_integer(s["frame"], UNIT, s["inp"]["poses"], s["inp"]["ranges"], FOV, R) > 1e-4
+    assert min(s["sides"]["score"]) >= 1
+    tscore.same(run_score(built["eng"], built["lv"], p, s["inp"]), s["want"]["rows"], f"crafted slot {p}")
+
+
+@pytest.mark.parametrize("p", range(P))
+def test_search_lattice_in_a_crafted_slot(built, crafted, p):
+    s = crafted[p]
+    assert s["inp"]["lat"][:3] == (5, 4, 8) and min(s["sides"]["search"]) >= 1
+    tsearch.same(run_search(built["eng"], built["lv"], p, s["inp"], built["free"]), s["want"]["words"], f"crafted slot {p}")
+
+
+@pytest.mark.parametrize("p", range(P))
+def test_mcl_step_in_a_crafted_slot(built, crafted, p):
+    s = crafted[p]
+    assert min(s["sides"]["mcl"]) >= 1
+    tmcl.same(run_mcl(built["eng"], built["lv"], p, s["inp"], built["free"], s["lut"], s["shift"]), s["want"]["step"], f"crafted slot {p}")
