@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Monte-Carlo localisation in a finished map with Localiser: follow the robot scan by scan, the hypotheses never leaving the device.
 
-    python examples/localise.py [--scans 40] [--particles 4096] [--temperature 64] [--level fine]
+    python examples/localise.py [--scans 40] [--particles 4096] [--temperature 64] [--level fine] [--adaptive]
 
 Maps a seeded walk through a synthetic world at its true poses (map_from_poses), then forgets the poses: the first scan is
 searched for in the whole window (ScanMatcher.searchPoses), the particle set is seeded around the search's peaks
@@ -10,6 +10,10 @@ searched for in the whole window (ScanMatcher.searchPoses), the particle set is 
 in between, one download of 128 bytes per scan at the end.  The odometry is the walk seen in a frame of its own, turned and
 shifted, with a little noise on every increment: only the increments are used.  Prints the mean pose of every scan beside the
 pose it was taken at, and the number of distinct ancestors the resampling kept.
+
+--adaptive starts lost instead: no search, --particles poses (the capacity; try 262144) uniform over the window and the full turn
+(Localiser.seed_uniform), and Localiser(adaptive={}) -- KLD-sampling, slam2d_mcl_step_adaptive -- sizes the set on the device
+from the pose bins it occupies: the count is printed per scan as it falls from the capacity to a few hundred.
 """
 import argparse
 import importlib
@@ -53,16 +57,22 @@ def main():
     ap.add_argument("--particles", type=int, default=4096)
     ap.add_argument("--temperature", type=float, default=64.0)
     ap.add_argument("--level", choices=("coarse", "fine"), default="fine")
+    ap.add_argument("--adaptive", action="store_true", help="start from a uniform set of --particles poses and let the count adapt")
     args = ap.parse_args()
     pkg = importlib.import_module("slam-2d-lidar-scan_amd")
     true, log, grid, window = synthetic(args.scans)
     og = pkg.map_from_poses(true, **grid)
     sm = pkg.ScanMatcher(og, *SM_PARAMS)
-    found = sm.searchPoses(log[0], window, headings=120, level=args.level, top=4)
-    for q in found["peaks"]:
-        print(f"search peak ({q.x:7.2f}, {q.y:7.2f}, {q.theta:6.3f}) score {q.score:9.2f}")
-    loc = pkg.Localiser(sm, window, particles=args.particles, level=args.level, sigma=(0.03, 0.03, 0.02), temperature=args.temperature, seed=1)
-    loc.seed_from_peaks(found["peaks"], (0.1, 0.1, 0.05))
+    if args.adaptive:
+        loc = pkg.Localiser(sm, window, particles=args.particles, level=args.level, sigma=(0.03, 0.03, 0.02), temperature=args.temperature, seed=1,
+                            adaptive={})
+        loc.seed_uniform()
+    else:
+        found = sm.searchPoses(log[0], window, headings=120, level=args.level, top=4)
+        for q in found["peaks"]:
+            print(f"search peak ({q.x:7.2f}, {q.y:7.2f}, {q.theta:6.3f}) score {q.score:9.2f}")
+        loc = pkg.Localiser(sm, window, particles=args.particles, level=args.level, sigma=(0.03, 0.03, 0.02), temperature=args.temperature, seed=1)
+        loc.seed_from_peaks(found["peaks"], (0.1, 0.1, 0.05))
     t0 = time.perf_counter()
     reports = loc.run(log)
     dt = time.perf_counter() - t0
@@ -70,8 +80,9 @@ def main():
         x, y, th = rep["mean_pose"]
         dth = (th - r["theta"] + math.pi) % (2 * math.pi) - math.pi
         print(f"true ({r['x']:7.2f}, {r['y']:7.2f}, {r['theta']:6.3f})  mean ({x:7.2f}, {y:7.2f}, {th:6.3f})  off by "
-              f"{math.hypot(x - r['x'], y - r['y']):.3f} m, {abs(dth):.3f} rad  {rep['distinct']:5d} distinct ancestors of {args.particles}, "
-              f"{rep['positive']:5d} weights above zero")
+              f"{math.hypot(x - r['x'], y - r['y']):.3f} m, {abs(dth):.3f} rad  {rep['distinct']:5d} distinct ancestors of {rep.get('n_out', args.particles)}, "
+              f"{rep['positive']:5d} weights above zero"
+              + (f"  count {rep['n_in']:7d} -> {rep['n_out']:7d} ({rep['bins']} bins)" if args.adaptive else ""))
     print(f"{len(log)} scans, {args.particles} particles: {1e3 * dt / len(log):.3f} ms per scan, upload and the one download included")
 
 

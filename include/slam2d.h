@@ -605,6 +605,63 @@ int slam2d_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t 
                     const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
                     int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream);
 
+/* slam2d_mcl_step with a particle count that lives on the device and follows the spread of the set -- KLD-sampling (Fox 2003)
+ * stated in integers: the number of occupied pose bins is the size of a set, the bound a table the host makes, the resampler
+ * draws as many offspring as the table says (an added symbol: no existing signature, struct or kernel result changed, the ABI
+ * number stays).  n_cap: the capacity, in poses, of BOTH pose buffers, of d_ancestor and of the work arrays (at most
+ * SLAM2D_MCL_MAX_PARTICLES).  PRECONDITION and members read: those of slam2d_mcl_step.
+ *   LIVE COUNT.  N = min(max(*d_n_in, 1), n_cap), read on the device: the host never needs it.
+ *   a-c. NOISE, MOVE, WEIGH: steps a-c of slam2d_mcl_step over the particles n < N -- the same counters (n, j, scan), the same
+ *      five rounded operations, the same cost, cmin, best and table weight w_n, the same prefix sums C_n, W, r and u0.  Poses
+ *      n >= N of d_pose_in are not read.
+ *   d. REFERENCE ANCESTORS.  A = the distinct ancestors of slam2d_mcl_step's resampling with N offspring, t_k =
+ *      floor((k * W + u0) / N), k < N: particle n is in A iff some k < N has C_(n-1) * N <= k * W + u0 < C_n * N (products below
+ *      2^64, as W <= N * 0xffffff).  W == 0: A = every n < N.
+ *   e. BINS of the moved pose (x, y, th) of each member of A:  qx = (x - x0) / cell,  qy = (y - y0) / cell,  qt = th / turn, each
+ *      ONE true division.  The pose is BINNABLE when |qx|, |qy| and |qt| are all < 1e9 (a NaN fails) and ix = floor(qx),
+ *      iy = floor(qy) satisfy 0 <= ix < nx, 0 <= iy < ny;  it = floor(qt) mod nth, non-negative;  bin = (it * ny + iy) * nx + ix.
+ *      Every pose that is not binnable falls into the ONE extra bin n_bins = nx * ny * nth; a quotient that fails the guard is
+ *      never converted to an integer.  kbins = the number of distinct bins over A: a bitmap of n_bins + 1 bits set with integer
+ *      atomic OR, then a population count.
+ *   f. SIZE.  N_out = min(max(d_ntab[min(kbins, ntab_n - 1)], 1), n_cap): a table the host makes (engine.kld_table), no floating
+ *      point on the device.
+ *   g. RESAMPLE with N_out offspring:  t_j = floor((j * W + u0) / N_out), j < N_out (below 2^64 as before);  a_j = the least n
+ *      with t_j < C_n;  W == 0: a_j = j mod N.  d_pose_out[j * pose_stride + 0..2] = the moved pose of a_j; rows j >= N_out are
+ *      untouched, and so are the other slots of the stride.  d_ancestor[j] = a_j where d_ancestor is not NULL.  *d_n_out = N_out,
+ *      written by the last launch: d_n_in and d_n_out may be the same word.
+ *   h. REPORT.  d_report[0..23]:  0-15 are slam2d_mcl_step's -- 0-5 and 7-9 over the N particles, 6 (distinct ancestors) and
+ *      10-14 (M and the four sums) over the N_out offspring of step g --,  16 N   17 N_out   18 kbins   19 |A|   20-23 0.
+ *   EQUIVALENCE.  With *d_n_in == n_cap and a table that returns n_cap, the first n_cap output poses, d_ancestor and report words
+ *   0-15 are slam2d_mcl_step(N = n_cap)'s bit for bit, and word 19 equals word 6.
+ * d_work: slam2d_mcl_adapt_work(n_cap, bins) 8-byte words = slam2d_mcl_work(n_cap) + (nx * ny * nth + 64) / 64 (the bitmap) + 8.
+ * The caller need not initialise d_work, d_report, d_pose_out or d_ancestor: the call clears the bitmap itself.  It allocates
+ * nothing, raises no fault bit and does not synchronise.  Seven launches on `stream` order the phases -- move (and the bitmap's
+ * clearing), score, weigh and scan, the block sums, the reference ancestors and their bins, the bitmap's count, the resampling --
+ * ; every per-particle launch is a grid of at most a few blocks per compute unit that strides over n < N, so what a call costs
+ * follows N and nx * ny * nth / 64, not n_cap.  Every join is an integer atomic or a fixed prefix sum.
+ * SLAM2D_E_BADARG, before any HIP call: every case of slam2d_mcl_step (N read as n_cap), a NULL d_n_in, d_n_out, bins or d_ntab,
+ * ntab_n < 1 or > 65536, nx, ny or nth < 1, !(cell > 0), !(turn > 0), a non-finite x0 or y0; SLAM2D_E_TOOLARGE: n_cap >
+ * SLAM2D_MCL_MAX_PARTICLES, nx * ny * nth > SLAM2D_MCL_MAX_BINS (the product in 64 bits), fmax * fpitch >= 2^29.
+ * slam2d_mcl_adapt_work makes no HIP call; < 0 means SLAM2D_E_* (the n_cap and bins cases above). */
+typedef struct {            /* pose bins of the KLD count */
+    double x0, y0;          /* low corner of the bin window */
+    double cell;            /* bin edge, metres (> 0) */
+    double turn;            /* bin width, radians (> 0; the host passes 2 pi / nth) */
+    int32_t nx, ny, nth, _pad;
+} Slam2dMclBins;
+
+#define SLAM2D_MCL_ADAPT_REPORT 24
+#define SLAM2D_MCL_MAX_BINS (1 << 26)
+int64_t slam2d_mcl_adapt_work(int32_t n_cap, const Slam2dMclBins* bins);
+int slam2d_mcl_step_adaptive(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t n_cap,
+                             const uint32_t* d_n_in, uint32_t* d_n_out,
+                             const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                             const double motion[3], const double amp[3], uint64_t seed, uint64_t scan,
+                             const double* d_ranges, uint32_t outside_cost,
+                             const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
+                             const Slam2dMclBins* bins, const uint32_t* d_ntab, int32_t ntab_n,
+                             int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream);
+
 /* Particle.updateEstimatedPose for P particles (Algorithm/FastSlam.py:77-106): the pose prior of the
  * next scan from the previous matched poses and the raw odometry increment.
  *   d_prev_pose[p*3 + 0..2]  previous matched pose (prevMatchedReading)

@@ -61,6 +61,8 @@ MCL_REPORT = 16                      # 64-bit words of slam2d_mcl_step's report
 MCL_MAX_PARTICLES = 1 << 20
 MCL_MAX_WEIGHT = 0xffffff            # largest integer weight of a particle (24 bits: the weights' sum stays below 2^44)
 MCL_SCAN_BLOCK = 1024                # particles one block of slam2d_mcl_step's scan launch covers (csrc: MCL_SCAN_BLOCK)
+MCL_ADAPT_REPORT = 24                # 64-bit words of slam2d_mcl_step_adaptive's report
+MCL_MAX_BINS = 1 << 26               # most pose bins (nx * ny * nth) of its KLD count
 
 STAGE_SWEEP,STAGE_BLUR, STAGE_SCATTER, STAGE_UPDATE, STAGE_SELECT, STAGE_ENDPOINTS, STAGE_BOUND, STAGE_EXACT = range(8)
 STAGE_NAMES = {STAGE_SWEEP: "k_sweep", STAGE_BLUR: "k_blur_clamp", STAGE_SCATTER: "k_occ_scatter",
@@ -155,7 +157,13 @@ class Slam2dBeamPlan(C.Structure):
                 ("ac", C.c_int32), ("ar", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32)]
 
 
-STRUCTS = {"Slam2dBeamPlan": Slam2dBeamPlan, "Slam2dGroup": Slam2dGroup, "Slam2dScan": Slam2dScan, "Slam2dMap": Slam2dMap, "Slam2dLidar": Slam2dLidar, "Slam2dFrame": Slam2dFrame,
+class Slam2dMclBins(C.Structure):
+    """The pose bins of slam2d_mcl_step_adaptive's KLD count (include/slam2d.h)."""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("turn", C.c_double),
+                ("nx", C.c_int32), ("ny", C.c_int32), ("nth", C.c_int32), ("_pad", C.c_int32)]
+
+
+STRUCTS = {"Slam2dMclBins": Slam2dMclBins, "Slam2dBeamPlan": Slam2dBeamPlan, "Slam2dGroup": Slam2dGroup, "Slam2dScan": Slam2dScan, "Slam2dMap": Slam2dMap, "Slam2dLidar": Slam2dLidar, "Slam2dFrame": Slam2dFrame,
            "Slam2dLevel": Slam2dLevel, "Slam2dMatch": Slam2dMatch, "Slam2dPartial": Slam2dPartial}
 
 # name -> (restype, argtypes); every symbol include/slam2d.h declares
@@ -181,6 +189,10 @@ SIGNATURES = {
     "slam2d_mcl_step": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                   _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "slam2d_mcl_adapt_work": (C.c_int64, [C.c_int32, C.POINTER(Slam2dMclBins)]),
+    "slam2d_mcl_step_adaptive": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_uint64, _vp, C.c_uint32,
+                                           _vp, C.c_int32, C.c_int32, C.POINTER(Slam2dMclBins), _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "slam2d_occ_extent": (C.c_int, [C.POINTER(Slam2dLidar), C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "slam2d_map_scans": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "slam2d_prior": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int32, C.c_double, _vp, C.c_int32, _vp, _vp, _vp]),

@@ -4706,6 +4706,280 @@ __global__ __launch_bounds__(256) void k_mcl_resample(int N, MclWork wk, double*
     if (threadIdx.x < 6 && acc[threadIdx.x]) atomicAdd(&report[threadIdx.x == 0 ? 6 : 9 + threadIdx.x], acc[threadIdx.x]);
 }
 
+// ---- slam2d_mcl_step_adaptive: the same step over a LIVE count N that only the device knows, sized by the occupied pose bins ----
+// No launch can be sized by N: every per-particle launch is a grid of at most MCLA_BLOCKS blocks (MCLA_SCORE_BLOCKS for the wave
+// per particle of the scoring launch) that strides over n < N, so its cost follows N and not the capacity.  The loop bodies are
+// those of the k_mcl_* kernels above, operation for operation.
+#define MCLA_BLOCKS 1024             // blocks of 256 threads: four per compute unit, 2^18 threads -- four particles each at 2^20
+#define MCLA_SCORE_BLOCKS 2048       // blocks of MCL_WAVES waves: 32 waves per compute unit, a little more than its registers let it hold (28)
+#define MCLA_REF_BLOCKS 512          // blocks of the reference-ancestor launch: fewer and longer, so that a block's filter sees more of a bin
+#define MCLA_SEEN 1024               // entries of that filter: the bins a block has set already, direct-mapped in LDS
+#define MCLA_TAIL 8                  // words of d_work behind the bitmap: |A|, kbins, then padding
+
+__device__ __forceinline__ int mcla_live(const uint32_t* __restrict__ n_in, const int n_cap) {
+    return (int)min(max(*n_in, 1u), (uint32_t)n_cap);
+}
+__host__ __device__ __forceinline__ long long mcla_bitmap_words(const long long n_bins) { return (n_bins + 64) / 64; }   // n_bins + 1 bits
+
+// k_mcl_move over n < N; thread 0 also zeroes the two counters of the tail, and the grid clears the bitmap
+__global__ __launch_bounds__(256) void k_mcla_move(const uint32_t* __restrict__ n_in, int n_cap, const double* __restrict__ pose, int pstride,
+                                                   double dfwd, double dside, double dturn, double amp0, double amp1, double amp2,
+                                                   uint64_t seed, uint64_t scan, MclWork wk, unsigned long long* __restrict__ bitmap, int words,
+                                                   unsigned long long* __restrict__ tail, unsigned long long* __restrict__ report) {
+    const int N = mcla_live(n_in, n_cap), t0 = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    if (t0 == 0) {
+        *wk.key = ~0ull;
+        report[3] = 0ull; report[6] = 0ull;
+        for (int i = 10; i < 15; ++i) report[i] = 0ull;
+        tail[0] = 0ull; tail[1] = 0ull;
+    }
+    for (int i = t0; i < words; i += stride) bitmap[i] = 0ull;
+    for (int n = t0; n < N; n += stride) {
+        const double x0 = pose[(size_t)n * pstride], y0 = pose[(size_t)n * pstride + 1], th0 = pose[(size_t)n * pstride + 2];
+        const double fx = dfwd + amp0 * mcl_noise((uint32_t)n, 0u, seed, scan), fy = dside + amp1 * mcl_noise((uint32_t)n, 1u, seed, scan);
+        const double c = cos(th0), s = sin(th0);
+        double* m = wk.moved + (size_t)n * 3;
+        m[0] = (x0 + c * fx) - s * fy;
+        m[1] = (y0 + s * fx) + c * fy;
+        m[2] = (th0 + dturn) + amp2 * mcl_noise((uint32_t)n, 2u, seed, scan);
+    }
+}
+
+// k_mcl_score: a wave takes particles wave, wave + the grid's waves, ... below N
+__global__ __launch_bounds__(64 * MCL_WAVES) void k_mcla_score(Slam2dLidar lid, Slam2dLevel lv, int p_field, const uint32_t* __restrict__ n_in, int n_cap,
+                                                               const double* __restrict__ ranges, unsigned outside_cost, MclWork wk) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int N = mcla_live(n_in, n_cap);
+    const Slam2dFrame fr = lv.frames[p_field];
+    const FieldSize fs = frame_clip(lv, fr);
+    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const int B = lid.beams, trips = (B + 63) >> 6;
+    for (int n = blockIdx.x * MCL_WAVES + wv; n < N; n += gridDim.x * MCL_WAVES) {   // (wave-uniform)
+        const double x = wk.moved[(size_t)n * 3], y = wk.moved[(size_t)n * 3 + 1], th = wk.moved[(size_t)n * 3 + 2];
+        const BeamFan fan = fan_of(lid, th);
+        unsigned long long sum_b = 0ull;
+        int n_in_field = 0, n_rng = 0;
+        int t = 0;
+        for (; t + MCL_UNROLL <= trips; t += MCL_UNROLL)
+            mcl_beams<MCL_UNROLL>(64 * t, lane, B, ranges, lid.max_range, fan, x, y, fr, lv.step, fs, lv.fpitch, field, sum_b, n_in_field, n_rng);
+        for (; t < trips; ++t) mcl_beams<1>(64 * t, lane, B, ranges, lid.max_range, fan, x, y, fr, lv.step, fs, lv.fpitch, field, sum_b, n_in_field, n_rng);
+        sum_b = wave64_sum_u64(sum_b);
+        if (lane == 0) {
+            const unsigned long long cost = sum_b + (unsigned long long)(n_rng - n_in_field) * outside_cost;
+            wk.cost[n] = cost;
+            const unsigned long long v = (cost << 20) | (unsigned long long)n;
+            if (v < __hip_atomic_load(wk.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(wk.key, v);
+        }
+    }
+}
+
+// k_mcl_weigh, launched for the capacity: a block beyond N writes a zero sum and is done
+__global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcla_weigh(const uint32_t* __restrict__ n_in, int n_cap, const uint32_t* __restrict__ lut, int lut_n,
+                                                                   int lut_shift, MclWork wk, unsigned long long* __restrict__ report) {
+    __shared__ unsigned long long lds[16];
+    __shared__ unsigned n_pos;
+    const int N = mcla_live(n_in, n_cap);
+    if (blockIdx.x * MCL_SCAN_BLOCK >= N) {                                      // (block-uniform)
+        if (threadIdx.x == 0) wk.bsum[blockIdx.x] = 0ull;
+        return;
+    }
+    if (threadIdx.x == 0) n_pos = 0u;
+    const unsigned long long cmin = *wk.key >> 20;
+    const int n0 = blockIdx.x * MCL_SCAN_BLOCK + threadIdx.x * 4;
+    unsigned long long pre[4], run = 0ull;
+    unsigned pos = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint32_t w = 0u;
+        if (n0 + i < N) {
+            const unsigned long long d = (wk.cost[n0 + i] - cmin) >> lut_shift;
+            w = min(lut[d < (unsigned long long)(lut_n - 1) ? (int)d : lut_n - 1], (uint32_t)SLAM2D_MCL_MAX_WEIGHT);
+        }
+        pos += w > 0u;
+        run += w;
+        pre[i] = run;
+    }
+    unsigned long long total;
+    const unsigned long long off = block_scan_u64(run, lds, total) - run;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (n0 + i < N) wk.csum[n0 + i] = off + pre[i];
+    if (pos) atomicAdd(&n_pos, pos);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        wk.bsum[blockIdx.x] = total;
+        if (n_pos) atomicAdd(&report[3], (unsigned long long)n_pos);
+    }
+}
+
+// k_mcl_sums; word 16 = N is what the last launch reads, as it may overwrite *n_in
+__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcla_sums(Slam2dLidar lid, const uint32_t* __restrict__ n_in, int n_cap, uint64_t seed, uint64_t scan,
+                                                              const double* __restrict__ ranges, MclWork wk, unsigned long long* __restrict__ report) {
+    __shared__ unsigned long long lds[16];
+    __shared__ unsigned n_rng;
+    const int N = mcla_live(n_in, n_cap);
+    const int t = threadIdx.x, nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
+    if (t == 0) n_rng = 0u;
+    const unsigned long long v = t < nb ? wk.bsum[t] : 0ull;
+    unsigned long long W;
+    const unsigned long long incl = block_scan_u64(v, lds, W);
+    if (t < nb) wk.bsum[t] = incl - v;
+    unsigned cnt = 0u;
+    for (int b = t; b < lid.beams; b += MCL_SCAN_BLOCK) cnt += ranges[b] < lid.max_range;
+    if (cnt) atomicAdd(&n_rng, cnt);
+    __syncthreads();
+    if (t == 0) {
+        const unsigned long long key = *wk.key, best = key & 0xfffffull;
+        const unsigned long long r = philox4x32_10(0xffffffffu, 0u, (uint32_t)scan, (uint32_t)(scan >> 32), (uint32_t)seed, (uint32_t)(seed >> 32)).v[0];
+        report[0] = key >> 20;
+        report[1] = best;
+        report[2] = W;
+        report[4] = (W >> 32) * r + (((W & 0xffffffffull) * r) >> 32);
+        report[5] = n_rng;
+        for (int i = 0; i < 3; ++i) report[7 + i] = (unsigned long long)__double_as_longlong(wk.moved[best * 3 + i]);
+        report[15] = 0ull;
+        report[16] = (unsigned long long)N;
+        for (int i = 20; i < 24; ++i) report[i] = 0ull;
+    }
+}
+
+// The pose bin of the header's step e; n_bins for a pose that is not binnable.  No quotient that fails the guard is converted.
+__device__ __forceinline__ int mcla_bin(const Slam2dMclBins& bn, const double x, const double y, const double th) {
+    const double qx = (x - bn.x0) / bn.cell, qy = (y - bn.y0) / bn.cell, qt = th / bn.turn;
+    const int n_bins = bn.nx * bn.ny * bn.nth;
+    if (!(fabs(qx) < 1e9 && fabs(qy) < 1e9 && fabs(qt) < 1e9)) return n_bins;
+    const int ix = (int)floor(qx), iy = (int)floor(qy);
+    if (ix < 0 || ix >= bn.nx || iy < 0 || iy >= bn.ny) return n_bins;
+    int it = (int)floor(qt) % bn.nth;
+    if (it < 0) it += bn.nth;
+    return (it * bn.ny + iy) * bn.nx + ix;
+}
+
+// Reference ancestors and their bins, a thread per particle and no search: n has an offspring among the N of the plain step iff
+// the least k with k W + u0 >= C_(n-1) N is below N and has k W + u0 < C_n N (C N <= W N < 2^64; k W + u0 < N W).  Its bin's bit
+// is set with an integer atomic OR, sent only where the word as last read lacks it -- and read only where the block's filter
+// does not hold the bin: a set that has converged puts hundreds of thousands of members into a few dozen words, and without the
+// filter every one of them goes to the same few L2 lines (profiles/r18_mcl_adaptive.md).  A filter entry is written by a thread
+// that goes on to set that very bin, so a hit never loses a bit; a lost race costs an atomic.  |A| is counted per block, then
+// atomically.
+__global__ __launch_bounds__(256) void k_mcla_refs(const uint32_t* __restrict__ n_in, int n_cap, MclWork wk, Slam2dMclBins bn,
+                                                   unsigned long long* __restrict__ bitmap, unsigned long long* __restrict__ tail,
+                                                   const unsigned long long* __restrict__ report) {
+    __shared__ unsigned n_ref;
+    __shared__ int seen[MCLA_SEEN];
+    if (threadIdx.x == 0) n_ref = 0u;
+    for (int i = threadIdx.x; i < MCLA_SEEN; i += 256) seen[i] = -1;
+    __syncthreads();
+    const int N = mcla_live(n_in, n_cap);
+    const unsigned long long W = report[2], u0 = report[4];
+    unsigned long long cnt = 0ull;
+    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
+        bool member = true;
+        if (W) {
+            const unsigned long long start = wk.bsum[n / MCL_SCAN_BLOCK];
+            const unsigned long long lo = (start + (n % MCL_SCAN_BLOCK ? wk.csum[n - 1] : 0ull)) * (unsigned long long)N;
+            const unsigned long long hi = (start + wk.csum[n]) * (unsigned long long)N;
+            const unsigned long long k = lo > u0 ? (lo - u0 - 1ull) / W + 1ull : 0ull;      // ceil((lo - u0) / W)
+            member = k < (unsigned long long)N && k * W + u0 < hi;
+        }
+        if (member) {
+            const int bin = mcla_bin(bn, wk.moved[(size_t)n * 3], wk.moved[(size_t)n * 3 + 1], wk.moved[(size_t)n * 3 + 2]);
+            int* slot = seen + (bin & (MCLA_SEEN - 1));
+            if (*(volatile int*)slot != bin) {
+                *(volatile int*)slot = bin;
+                unsigned long long* word = bitmap + (bin >> 6);
+                const unsigned long long bit = 1ull << (bin & 63);
+                if (!(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(word, bit);
+            }
+            ++cnt;
+        }
+    }
+    cnt = wave64_sum_u64(cnt);                                                   // (every lane is here)
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&n_ref, (unsigned)cnt);
+    __syncthreads();
+    if (threadIdx.x == 0 && n_ref) atomicAdd(&tail[0], (unsigned long long)n_ref);
+}
+
+// kbins: the bitmap's population count
+__global__ __launch_bounds__(256) void k_mcla_count(const unsigned long long* __restrict__ bitmap, int words, unsigned long long* __restrict__ tail) {
+    __shared__ unsigned n_set;
+    if (threadIdx.x == 0) n_set = 0u;
+    __syncthreads();
+    unsigned long long cnt = 0ull;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < words; i += gridDim.x * 256) cnt += (unsigned long long)__popcll(bitmap[i]);
+    cnt = wave64_sum_u64(cnt);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&n_set, (unsigned)cnt);
+    __syncthreads();
+    if (threadIdx.x == 0 && n_set) atomicAdd(&tail[1], (unsigned long long)n_set);
+}
+
+// k_mcl_resample with N_out offspring of N particles: N from report word 16 (this launch writes *n_out, which may be *n_in),
+// N_out from the table at kbins.  W == 0: a_j = j mod N, first offspring where j < N.
+__global__ __launch_bounds__(256) void k_mcla_resample(int n_cap, const uint32_t* __restrict__ ntab, int ntab_n, MclWork wk,
+                                                       const unsigned long long* __restrict__ tail, double* __restrict__ out, int pstride,
+                                                       int32_t* __restrict__ ancestor, uint32_t* __restrict__ n_out,
+                                                       unsigned long long* __restrict__ report) {
+    __shared__ unsigned long long acc[6];
+    if (threadIdx.x < 6) acc[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int N = (int)report[16];
+    const unsigned long long kbins = tail[1];
+    const int N_out = (int)min(max(ntab[kbins < (unsigned long long)(ntab_n - 1) ? (int)kbins : ntab_n - 1], 1u), (uint32_t)n_cap);
+    const unsigned long long W = report[2], u0 = report[4];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        report[17] = (unsigned long long)N_out;
+        report[18] = kbins;
+        report[19] = tail[0];
+        *n_out = (uint32_t)N_out;
+    }
+    const int nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
+    unsigned long long part[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < N_out; j += gridDim.x * 256) {
+        int a = j % N;
+        bool first = j < N;
+        if (W) {
+            const unsigned long long t = ((unsigned long long)j * W + u0) / (unsigned long long)N_out;
+            int lo = 0, hi = nb - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (t < wk.bsum[mid + 1]) hi = mid; else lo = mid + 1;
+            }
+            const unsigned long long start = wk.bsum[lo], rel = t - start;
+            const int base = lo * MCL_SCAN_BLOCK;
+            int i0 = 0, i1 = min(MCL_SCAN_BLOCK, N - base) - 1;
+            while (i0 < i1) {
+                const int mid = (i0 + i1) >> 1;
+                if (rel < wk.csum[base + mid]) i1 = mid; else i0 = mid + 1;
+            }
+            a = base + i0;
+            first = true;
+            if (j > 0) {
+                const unsigned long long tp = ((unsigned long long)(j - 1) * W + u0) / (unsigned long long)N_out;
+                first = tp < start + (i0 > 0 ? wk.csum[a - 1] : 0ull);
+            }
+        }
+        const double x = wk.moved[(size_t)a * 3], y = wk.moved[(size_t)a * 3 + 1], th = wk.moved[(size_t)a * 3 + 2];
+        double* o = out + (size_t)j * pstride;
+        o[0] = x; o[1] = y; o[2] = th;
+        if (ancestor) ancestor[j] = a;
+        part[0] += first;
+        if (fabs(x) < 0x1p20 && fabs(y) < 0x1p20 && __builtin_isfinite(th)) {
+            part[1] += 1ull;
+            part[2] += (unsigned long long)llrint(x * 65536.0);
+            part[3] += (unsigned long long)llrint(y * 65536.0);
+            part[4] += (unsigned long long)llrint(cos(th) * 0x1p30);
+            part[5] += (unsigned long long)llrint(sin(th) * 0x1p30);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const unsigned long long s = wave64_sum_u64(part[i]);
+        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&acc[i], s);
+    }
+    __syncthreads();
+    if (threadIdx.x < 6 && acc[threadIdx.x]) atomicAdd(&report[threadIdx.x == 0 ? 6 : 9 + threadIdx.x], acc[threadIdx.x]);
+}
+
 // Sharded normaliser, merge half: every rank folds the gathered [world][3] partials in rank order
 // (so the result does not depend on the network's reduction order), normalises its own particles
 // and evaluates sum (w - 1/N)^2 = sum w^2 - 1/N over ALL N particles (Algorithm/FastSlam.py:32-35).
@@ -5067,6 +5341,7 @@ int slam2d_sizeof(const char* name) {
     if (!strcmp(name, "Slam2dGroup")) return (int)sizeof(Slam2dGroup);
     if (!strcmp(name, "Slam2dScan")) return (int)sizeof(Slam2dScan);
     if (!strcmp(name, "Slam2dBeamPlan")) return (int)sizeof(Slam2dBeamPlan);
+    if (!strcmp(name, "Slam2dMclBins")) return (int)sizeof(Slam2dMclBins);
     return -1;
 }
 
@@ -5599,6 +5874,62 @@ int slam2d_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t 
     k_mcl_weigh<<<cdiv(N, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(N, d_lut, lut_n, lut_shift, wk, report);
     k_mcl_sums<<<1, MCL_SCAN_BLOCK, 0, s>>>(*lidar, N, seed, scan, d_ranges, wk, report);
     k_mcl_resample<<<cdiv(N, 256), 256, 0, s>>>(N, wk, d_pose_out, pose_stride, d_ancestor, report);
+    return launch_status();
+}
+
+// the checks of the pose bins that slam2d_mcl_step_adaptive and its work size share; *n_bins: nx * ny * nth
+static int check_mcl_bins(const Slam2dMclBins* bins, long long* n_bins) {
+    if (!bins || bins->nx < 1 || bins->ny < 1 || bins->nth < 1) return SLAM2D_E_BADARG;
+    if (!(bins->cell > 0) || !(bins->turn > 0) || !__builtin_isfinite(bins->x0) || !__builtin_isfinite(bins->y0)) return SLAM2D_E_BADARG;
+    const long long plane = (long long)bins->nx * bins->ny;                       // (below 2^62; times nth only once it is small)
+    if (plane > SLAM2D_MCL_MAX_BINS || plane * bins->nth > SLAM2D_MCL_MAX_BINS) return SLAM2D_E_TOOLARGE;
+    *n_bins = plane * bins->nth;
+    return 0;
+}
+
+int64_t slam2d_mcl_adapt_work(int32_t n_cap, const Slam2dMclBins* bins) {
+    long long n_bins = 0;
+    const int rc = check_mcl_bins(bins, &n_bins);
+    if (rc == SLAM2D_E_BADARG || n_cap < 1) return SLAM2D_E_BADARG;
+    if (n_cap > SLAM2D_MCL_MAX_PARTICLES) return SLAM2D_E_TOOLARGE;
+    if (rc) return rc;
+    return mcl_work_words(n_cap) + mcla_bitmap_words(n_bins) + MCLA_TAIL;
+}
+
+int slam2d_mcl_step_adaptive(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t n_cap, const uint32_t* d_n_in,
+                             uint32_t* d_n_out, const double* d_pose_in, double* d_pose_out, int32_t pose_stride, const double motion[3],
+                             const double amp[3], uint64_t seed, uint64_t scan, const double* d_ranges, uint32_t outside_cost,
+                             const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift, const Slam2dMclBins* bins, const uint32_t* d_ntab,
+                             int32_t ntab_n, int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream) {
+    const int frc = check_scored_field(lidar, level, p_field);
+    if (frc == SLAM2D_E_BADARG) return frc;
+    if (!d_pose_in || !d_pose_out || !motion || !amp || !d_ranges || !d_lut || !d_work || !d_report) return SLAM2D_E_BADARG;
+    if (!d_n_in || !d_n_out || !d_ntab || ntab_n < 1 || ntab_n > 65536) return SLAM2D_E_BADARG;
+    if (d_pose_in == d_pose_out || n_cap < 1 || pose_stride < 3 || lut_n < 1 || lut_n > 65536 || lut_shift < 0 || lut_shift > 43)
+        return SLAM2D_E_BADARG;
+    for (int i = 0; i < 3; ++i)
+        if (!__builtin_isfinite(motion[i]) || !__builtin_isfinite(amp[i])) return SLAM2D_E_BADARG;
+    long long n_bins = 0;
+    const int brc = check_mcl_bins(bins, &n_bins);
+    if (brc == SLAM2D_E_BADARG) return brc;
+    if (n_cap > SLAM2D_MCL_MAX_PARTICLES) return SLAM2D_E_TOOLARGE;
+    if (brc) return brc;
+    if (frc) return frc;
+    hipStream_t s = (hipStream_t)stream;
+    const MclWork wk = mcl_work_of(d_work, n_cap);
+    const int words = (int)mcla_bitmap_words(n_bins);                             // (at most 2^20 + 1)
+    unsigned long long* bitmap = (unsigned long long*)d_work + mcl_work_words(n_cap);
+    unsigned long long* tail = bitmap + words;
+    unsigned long long* report = (unsigned long long*)d_report;
+    const int per_particle = min(cdiv(n_cap, 256), MCLA_BLOCKS);
+    k_mcla_move<<<min(max(cdiv(n_cap, 256), cdiv(words, 256)), MCLA_BLOCKS), 256, 0, s>>>(d_n_in, n_cap, d_pose_in, pose_stride, motion[0], motion[1],
+        motion[2], amp[0], amp[1], amp[2], seed, scan, wk, bitmap, words, tail, report);
+    k_mcla_score<<<min(cdiv(n_cap, MCL_WAVES), MCLA_SCORE_BLOCKS), 64 * MCL_WAVES, 0, s>>>(*lidar, *level, p_field, d_n_in, n_cap, d_ranges, outside_cost, wk);
+    k_mcla_weigh<<<cdiv(n_cap, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(d_n_in, n_cap, d_lut, lut_n, lut_shift, wk, report);
+    k_mcla_sums<<<1, MCL_SCAN_BLOCK, 0, s>>>(*lidar, d_n_in, n_cap, seed, scan, d_ranges, wk, report);
+    k_mcla_refs<<<min(per_particle, MCLA_REF_BLOCKS), 256, 0, s>>>(d_n_in, n_cap, wk, *bins, bitmap, tail, report);
+    k_mcla_count<<<min(cdiv(words, 256), MCLA_BLOCKS), 256, 0, s>>>(bitmap, words, tail);
+    k_mcla_resample<<<per_particle, 256, 0, s>>>(n_cap, d_ntab, ntab_n, wk, tail, d_pose_out, pose_stride, d_ancestor, d_n_out, report);
     return launch_status();
 }
 

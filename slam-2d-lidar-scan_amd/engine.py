@@ -264,6 +264,39 @@ def mcl_report_host(words):
                 best_pose=tuple(float(v) for v in w[7:10].view(np.float64)), M=M, sums=(sx, sy, sc, ss), mean_pose=mean)
 
 
+def kld_table(epsilon=0.05, z=2.326, n_min=256, n_max=_lib.MCL_MAX_PARTICLES, entries=65536):
+    """The particle count of slam2d_mcl_step_adaptive (include/slam2d.h) per number k of occupied pose bins, uint32 [entries]:
+    tab[k] = n_min for k <= 1, else ceil((k - 1) / (2 epsilon) * (1 - 2 / (9 (k - 1)) + sqrt(2 / (9 (k - 1))) * z) ** 3) clipped to
+    [n_min, n_max] -- KLD-sampling (Fox 2003) with the Wilson-Hilferty approximation of the chi-square quantile: with
+    probability 1 - delta (``z`` its upper normal quantile; 2.326 is delta = 0.01) the Kullback-Leibler distance between the
+    sampled and the true posterior stays below ``epsilon``.  Non-decreasing; the device reads entry min(k, entries - 1)."""
+    entries = int(entries)
+    if not 2 <= entries <= 65536:
+        raise ValueError(f"entries wants 2 .. 65536, not {entries!r}")
+    if not (math.isfinite(epsilon) and epsilon > 0 and math.isfinite(z) and z >= 0):
+        raise ValueError(f"epsilon wants a positive number and z a finite one >= 0, not {epsilon!r}, {z!r}")
+    if int(n_min) != n_min or int(n_max) != n_max or not 1 <= n_min <= n_max <= 0xffffffff:
+        raise ValueError(f"want integers 1 <= n_min <= n_max < 2^32, not {n_min!r}, {n_max!r}")
+    k1 = np.maximum(np.arange(entries, dtype=np.float64) - 1.0, 1.0)           # (entries 0 and 1 are overwritten below)
+    a = 2.0 / (9.0 * k1)
+    tab = np.clip(np.ceil(k1 / (2.0 * float(epsilon)) * (1.0 - a + np.sqrt(a) * float(z)) ** 3), float(n_min), float(n_max))
+    tab[:2] = float(n_min)
+    return np.maximum.accumulate(tab).astype(np.uint32)
+
+
+def mcl_adapt_report_host(words):
+    """The 24 words of slam2d_mcl_step_adaptive's report as a dict: ``mcl_report_host``'s of the first sixteen, and ``n_in`` (the
+    live count N the step ran over), ``n_out`` (the count it left), ``bins`` (occupied pose bins) and ``reference_distinct``
+    (|A|: the distinct ancestors a resampling to N would have had)."""
+    w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
+    w = np.ascontiguousarray(w).reshape(-1).view(np.uint64)
+    if w.size != _lib.MCL_ADAPT_REPORT:
+        raise ValueError(f"{w.size} words: want {_lib.MCL_ADAPT_REPORT}")
+    out = mcl_report_host(w[:_lib.MCL_REPORT])
+    out.update(n_in=int(w[16]), n_out=int(w[17]), bins=int(w[18]), reference_distinct=int(w[19]))
+    return out
+
+
 # ----------------------------------------------------------------------------
 # Lidar model + polar spoke LUT (Utils/OccupancyGrid.py:22-57)
 # ----------------------------------------------------------------------------
@@ -1245,6 +1278,38 @@ class ParticleEngine:
                                      int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff, _ptr(d_ranges), int(outside_cost),
                                      _ptr(d_lut), d_lut.numel(), int(shift), _ptr(d_ancestor), _ptr(work), _ptr(d_report), _stream()),
               "slam2d_mcl_step")
+
+    def mcl_step_adaptive(self, level, p_field, d_in, d_out, n_cap, d_count, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift,
+                          bins, d_ntab, d_report, d_ancestor=None, d_count_out=None):
+        """``mcl_step`` over a particle count that lives on the device (include/slam2d.h, slam2d_mcl_step_adaptive): ``d_count``,
+        one int32 word, holds the live count N <= ``n_cap``, the capacity of ``d_in``, ``d_out`` and ``d_ancestor``; the step
+        counts the pose bins ``bins`` (a ``_lib.Slam2dMclBins``) that a resampling to N would occupy, reads the new count from
+        ``d_ntab`` (``kld_table`` on the device), resamples to that many poses and leaves the count in ``d_count_out`` (default:
+        ``d_count`` itself).  ``d_report``: 24 int64 words (``mcl_adapt_report_host``).  Seven launches on the current stream,
+        no synchronisation; the scratch is kept and grown."""
+        if not 0 <= p_field < level.P:
+            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        stride = d_in.shape[-1] if d_in.dim() > 1 else 3
+        if (d_out.shape[-1] if d_out.dim() > 1 else 3) != stride or d_in.numel() < n_cap * stride or d_out.numel() < n_cap * stride:
+            raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {n_cap} poses of one row length")
+        if d_report.numel() < _lib.MCL_ADAPT_REPORT or (d_ancestor is not None and d_ancestor.numel() < n_cap):
+            raise ValueError("d_report wants 24 words, d_ancestor n_cap")
+        d_count_out = d_count if d_count_out is None else d_count_out
+        if any(t.numel() < 1 or t.element_size() != 4 for t in (d_count, d_count_out)):
+            raise ValueError("d_count wants one 32-bit word")
+        n = int(self.L.slam2d_mcl_adapt_work(n_cap, C.byref(bins)))
+        if n < 0:
+            check(n, "slam2d_mcl_adapt_work")
+        work = getattr(self, "_mcl_adapt_work", None)
+        if work is None or work.numel() < n:
+            work = self._mcl_adapt_work = torch.empty(n, dtype=torch.int64, device=self.device)
+        check(self.L.slam2d_mcl_step_adaptive(C.byref(self.lidar_c), C.byref(level.c), p_field, n_cap, _ptr(d_count), _ptr(d_count_out),
+                                              _ptr(d_in), _ptr(d_out), stride,
+                                              (C.c_double * 3)(*[float(v) for v in motion]), (C.c_double * 3)(*[float(v) for v in amp]),
+                                              int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff, _ptr(d_ranges), int(outside_cost),
+                                              _ptr(d_lut), d_lut.numel(), int(shift), C.byref(bins), _ptr(d_ntab), d_ntab.numel(),
+                                              _ptr(d_ancestor), _ptr(work), _ptr(d_report), _stream()),
+              "slam2d_mcl_step_adaptive")
 
     def grid_update(self, d_pose, stride, d_ranges, d_beam_shift=None):
         self._before_update()

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import encode_cost, mcl_report_host, pinned_stream, weight_table
+from .engine import encode_cost, kld_table, mcl_adapt_report_host, mcl_report_host, pinned_stream, weight_table
 from .matcher import covering_window
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -72,10 +72,18 @@ class Localiser:
     deviations of the motion noise per step (metres, metres, radians; the step's amplitudes are these / sqrt(4/3));
     ``temperature``: of the weights (``engine.weight_table``; 1.0 is the reference's soft-max); ``seed``: the generator's key;
     ``outside_cost``: what an in-range beam that ends outside the field pays (default: free space as the field encodes it).
-    Seed the set with ``seed_at``, ``seed_from_peaks`` or ``seed_uniform``, then ``step`` or ``run``."""
+    Seed the set with ``seed_at``, ``seed_from_peaks`` or ``seed_uniform``, then ``step`` or ``run``.
+
+    ``adaptive``: None -- the set keeps its size -- or a dict of ``n_min``, ``bin_xy`` (0.5 m), ``bin_theta`` (10 degrees, in
+    radians), ``epsilon`` (0.05) and ``z`` (2.326), any of them left to its default: KLD-sampling (slam2d_mcl_step_adaptive,
+    ``engine.kld_table``).  ``particles`` is then the capacity and the initial count; every step counts the pose bins of
+    ``bin_xy`` x ``bin_xy`` x ``bin_theta`` over the window that the resampled set occupies and resamples to as many poses as
+    the table wants for that number, between ``n_min`` and the capacity.  The count lives in one device word and travels from
+    call to call there; ``count`` downloads it, the reports carry it (``n_in``, ``n_out``), and the seeding calls take any
+    ``count`` from 1 to the capacity."""
 
     def __init__(self, matcher, window, particles=4096, level="fine", sigma=(0.05, 0.05, 0.02), temperature=1.0, seed=0,
-                 outside_cost=None):
+                 outside_cost=None, adaptive=None):
         self.matcher = matcher
         self.N = int(particles)
         if not 1 <= self.N <= _lib.MCL_MAX_PARTICLES:
@@ -103,43 +111,99 @@ class Localiser:
         self.d_ancestor = torch.empty(self.N, dtype=torch.int32, device=dev)
         self.d_report = torch.empty(_lib.MCL_REPORT, dtype=torch.int64, device=dev)
         self.d_ranges = torch.empty(og.numSamplesPerRev, dtype=torch.float64, device=dev)
+        self.adaptive = None
+        if adaptive is not None:
+            self._init_adaptive(dict(adaptive))
+
+    def _init_adaptive(self, opt):
+        unknown = set(opt) - {"n_min", "bin_xy", "bin_theta", "epsilon", "z"}
+        if unknown:
+            raise ValueError(f"adaptive: unknown keys {sorted(unknown)}")
+        cx, cy, half = self.window
+        n_min = int(opt.get("n_min", min(self.N, 256)))
+        bin_xy, bin_theta = float(opt.get("bin_xy", 0.5)), float(opt.get("bin_theta", math.radians(10.0)))
+        if not (math.isfinite(bin_xy) and bin_xy > 0 and math.isfinite(bin_theta) and 0 < bin_theta <= 2 * math.pi):
+            raise ValueError(f"adaptive: bin_xy wants a positive number and bin_theta one in (0, 2 pi], not {bin_xy!r}, {bin_theta!r}")
+        side, nth = max(1, math.ceil(2 * half / bin_xy)), max(1, round(2 * math.pi / bin_theta))
+        if side * side * nth > _lib.MCL_MAX_BINS:
+            raise ValueError(f"adaptive: {side} x {side} x {nth} bins, more than {_lib.MCL_MAX_BINS}")
+        epsilon, z = float(opt.get("epsilon", 0.05)), float(opt.get("z", 2.326))
+        tab = kld_table(epsilon, z, n_min, self.N)
+        dev = self.eng.device
+        self.bins = _lib.Slam2dMclBins(x0=cx - half, y0=cy - half, cell=bin_xy, turn=2 * math.pi / nth, nx=side, ny=side, nth=nth)
+        self.ntab = tab
+        self.d_ntab = torch.from_numpy(tab.view(np.int32)).to(dev)
+        self.d_count = torch.full((1,), self.N, dtype=torch.int32, device=dev)
+        self.d_report = torch.empty(_lib.MCL_ADAPT_REPORT, dtype=torch.int64, device=dev)
+        self.adaptive = dict(n_min=n_min, bin_xy=bin_xy, bin_theta=bin_theta, epsilon=epsilon, z=z)
+
+    @property
+    def count(self):
+        """The number of live poses: the size of the set, or with ``adaptive`` the device's count word, downloaded."""
+        return self.N if self.adaptive is None else int(self.d_count.cpu()[0])
 
     # ---- the set ----
     def set_poses(self, poses):
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        if self.adaptive is not None:
+            if not 1 <= len(poses) <= self.N:
+                raise ValueError(f"{len(poses)} poses for a set of 1 .. {self.N}")
+            self.d_pose[self.cur][:len(poses)].copy_(torch.from_numpy(poses))
+            self.d_count.fill_(len(poses))
+            return poses
         if len(poses) != self.N:
             raise ValueError(f"{len(poses)} poses for a set of {self.N}")
         self.d_pose[self.cur].copy_(torch.from_numpy(poses))
         return poses
 
-    def seed_at(self, pose, spread):
-        """The set around ``pose`` = (x, y, theta): pose + spread * g / sqrt(4/3) per component, g the step's noise at draws 3-5 of
-        the current scan number.  ``spread``: one standard deviation for all three, or (sx, sy, stheta).  Returns the poses."""
-        return self.seed_from_peaks([pose], spread)
+    def _seed_count(self, count):
+        if count is None:
+            return self.N
+        if self.adaptive is None and int(count) != self.N:
+            raise ValueError(f"count = {count!r}: a set of fixed size holds {self.N} (see adaptive)")
+        if not 1 <= int(count) <= self.N:
+            raise ValueError(f"count wants 1 .. {self.N}, not {count!r}")
+        return int(count)
 
-    def seed_from_peaks(self, peaks, spread):
+    def seed_at(self, pose, spread, count=None):
+        """The set around ``pose`` = (x, y, theta): pose + spread * g / sqrt(4/3) per component, g the step's noise at draws 3-5 of
+        the current scan number.  ``spread``: one standard deviation for all three, or (sx, sy, stheta).  ``count``: how many
+        poses, with ``adaptive`` (default: the capacity).  Returns the poses."""
+        return self.seed_from_peaks([pose], spread, count)
+
+    def seed_from_peaks(self, peaks, spread, count=None):
         """The set shared out in turn among ``peaks`` -- ``Peak``s of ``ScanMatcher.searchPoses`` or (x, y, theta) triples:
         particle n around peak n mod len(peaks), spread as in ``seed_at``."""
         centres = np.array([[float(p.x), float(p.y), float(p.theta)] if hasattr(p, "theta") else [float(v) for v in p[:3]] for p in peaks])
         if not len(centres):
             raise ValueError("no peaks")
         sp = np.broadcast_to(np.asarray(spread, dtype=np.float64), (3,))
-        g = noise(self.N, _DRAW_SPREAD, self.seed, self.scan)
-        return self.set_poses(centres[np.arange(self.N) % len(centres)] + (sp / _IH_STD) * g)
+        n = self._seed_count(count)
+        g = noise(n, _DRAW_SPREAD, self.seed, self.scan)
+        return self.set_poses(centres[np.arange(n) % len(centres)] + (sp / _IH_STD) * g)
 
-    def seed_uniform(self):
+    def seed_uniform(self, count=None):
         """The set uniform over the window and the full turn: words 0-2 of draw 6 of the current scan number, over 2^32."""
         cx, cy, half = self.window
-        u = _words(self.N, (_DRAW_UNIFORM,), self.seed, self.scan)[:, 0, :3].astype(np.float64) * 2.0 ** -32
+        u = _words(self._seed_count(count), (_DRAW_UNIFORM,), self.seed, self.scan)[:, 0, :3].astype(np.float64) * 2.0 ** -32
         return self.set_poses(np.column_stack([cx + (2 * u[:, 0] - 1) * half, cy + (2 * u[:, 1] - 1) * half, -math.pi + 2 * math.pi * u[:, 2]]))
 
     def poses(self):
-        """The current set, downloaded: [N, 3]."""
+        """The current set, downloaded: [N, 3]; with ``adaptive`` its first ``count`` rows."""
+        if self.adaptive is not None:
+            return self.d_pose[self.cur][:self.count].cpu().numpy()
         return self.d_pose[self.cur].cpu().numpy()
 
     # ---- the filter ----
     def _enqueue(self, d_ranges, motion, d_report):
         eng = self.eng
+        if self.adaptive is not None:
+            eng.mcl_step_adaptive(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], self.N, self.d_count, motion, self.amp,
+                                  self.seed, self.scan, d_ranges, self.outside_cost, self.d_lut, self.shift, self.bins, self.d_ntab, d_report,
+                                  self.d_ancestor)
+            self.cur = 1 - self.cur
+            self.scan += 1
+            return
         eng.mcl_step(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], self.N, motion, self.amp, self.seed, self.scan,
                      d_ranges, self.outside_cost, self.d_lut, self.shift, d_report, self.d_ancestor)
         self.cur = 1 - self.cur
@@ -148,21 +212,23 @@ class Localiser:
     def step(self, reading_or_ranges, motion):
         """One scan: the set moved by ``motion`` = (dfwd, dside, dturn) in the robot's own previous frame, weighed against the scan
         and resampled.  One call, one download of 128 bytes: the report as ``engine.mcl_report_host`` decodes it --
-        ``mean_pose`` is the estimate."""
+        ``mean_pose`` is the estimate (192 bytes and ``engine.mcl_adapt_report_host`` with ``adaptive``)."""
         self.d_ranges.copy_(torch.from_numpy(_ranges_of(reading_or_ranges, self.d_ranges.numel())))
         self._enqueue(self.d_ranges, motion, self.d_report)
-        return mcl_report_host(self.d_report)
+        return mcl_report_host(self.d_report) if self.adaptive is None else mcl_adapt_report_host(self.d_report)
 
     def run(self, readings):
         """A log: the motion of scan i is the step from raw odometry pose i - 1 to i in the frame of pose i - 1 (nothing for the
-        first scan).  Every scan is enqueued without a synchronisation, the reports go to one [S, 16] device array, and ONE
-        download ends the call.  Returns the list of decoded reports."""
+        first scan).  Every scan is enqueued without a synchronisation, the reports go to one [S, 16] device array ([S, 24] with
+        ``adaptive``, whose count goes from call to call on the device), and ONE download ends the call.  Returns the list of
+        decoded reports."""
         beams = self.d_ranges.numel()
         rng = np.stack([_ranges_of(r, beams) for r in readings])
         with pinned_stream():
             d_rng = torch.from_numpy(rng).to(self.eng.device)
-            d_rep = torch.empty((len(readings), _lib.MCL_REPORT), dtype=torch.int64, device=self.eng.device)
+            words = _lib.MCL_REPORT if self.adaptive is None else _lib.MCL_ADAPT_REPORT
+            d_rep = torch.empty((len(readings), words), dtype=torch.int64, device=self.eng.device)
             for i in range(len(readings)):
                 self._enqueue(d_rng[i], odometry_motion(readings[i - 1], readings[i]) if i else (0.0, 0.0, 0.0), d_rep[i])
             host = d_rep.cpu().numpy()
-        return [mcl_report_host(row) for row in host]
+        return [mcl_report_host(row) if self.adaptive is None else mcl_adapt_report_host(row) for row in host]
