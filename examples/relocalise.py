@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Global re-localisation in a finished map with ScanMatcher.scorePoses: where in the map was this scan taken?
 
-    python examples/relocalise.py [--scans 3] [--step 0.1] [--headings 120] [--level fine] [--on-device]
+    python examples/relocalise.py [--scans 3] [--step 0.1] [--headings 120] [--level fine] [--on-device] [--likelihood [SIGMA]]
 
 Maps a seeded walk of 40 scans through a synthetic world (OccupancyGrid.update_many at the walk's poses), then for a few of
 the walk's scans scores a whole lattice of candidate poses -- x, y every --step metres over the map, --headings headings: 3.1
@@ -10,7 +10,9 @@ well does this scan fit at these poses", for any pose set.
 
 With --on-device the lattice search runs in the library instead (ScanMatcher.searchPoses, slam2d_search_lattice): no pose is
 uploaded, the best heading and its cost per position come back -- an image of 161 x 161 words instead of 3.1 million rows --
-and the well-separated runner-up positions are printed beside the best.
+and the well-separated runner-up positions are printed beside the best.  --likelihood (with --on-device) searches the likelihood
+field instead of the blurred one (slam2d_field_build_distance; SIGMA in metres, default 0.2): its peak is as wide as SIGMA, not
+as the blur, so a coarser --step still finds it.
 
 `beam_score` (the field's cost summed over every beam) ranks the candidates, not `score` (summed over the set of cells the beams
 end in, the reference's own score): the latter rewards a pose that folds the scan into few cells.  The peak at the true pose is
@@ -62,7 +64,10 @@ def main():
     ap.add_argument("--headings", type=int, default=120)
     ap.add_argument("--level", choices=("coarse", "fine"), default="fine")
     ap.add_argument("--on-device", action="store_true", help="search the lattice with ScanMatcher.searchPoses")
+    ap.add_argument("--likelihood", type=float, nargs="?", const=0.2, default=None, metavar="SIGMA",
+                    help="with --on-device: search the likelihood field of this sigma in metres (default 0.2)")
     args = ap.parse_args()
+    lik = dict(likelihood=dict(sigma=args.likelihood)) if args.likelihood is not None else {}
     pkg = importlib.import_module("slam-2d-lidar-scan_amd")
     og, readings, window = synthetic(pkg, args.scans)
     sm = pkg.ScanMatcher(og, *SM_PARAMS)
@@ -71,17 +76,17 @@ def main():
           f"{len(readings[0]['range'])} beams; the {args.level} level")
     sm.scorePoses(poses[:8], readings[0], level=args.level, window=window)           # (warm-up: level allocation, first launches)
     if args.on_device:
-        sm.searchPoses(readings[0], window, step=args.step, headings=args.headings, level=args.level)
+        sm.searchPoses(readings[0], window, step=args.step, headings=args.headings, level=args.level, **lik)
     for r in readings:
         t0 = time.perf_counter()
         if args.on_device:
-            found = sm.searchPoses(r, window, step=args.step, headings=args.headings, level=args.level, top=4)
+            found = sm.searchPoses(r, window, step=args.step, headings=args.headings, level=args.level, top=4, **lik)
             dt = time.perf_counter() - t0
             p = found["peaks"][0]
             iy, ix = int(np.argmin(np.abs(found["ys"] - p.y))), int(np.argmin(np.abs(found["xs"] - p.x)))
             best = (iy * len(found["xs"]) + ix) * args.headings + int(found["heading"][iy, ix])
             bx, by, bth = p.x, p.y, p.theta
-            s = sm.scorePoses([(bx, by, bth)], r, level=args.level, window=window)      # (the best pose's own row, for the line below)
+            s = sm.scorePoses([(bx, by, bth)], r, level=args.level, window=window, **lik)      # (the best pose's own row, for the line below)
             s = {k: {best: v[0]} for k, v in s.items()}
         else:
             s = sm.scorePoses(poses, r, level=args.level, window=window)

@@ -662,6 +662,41 @@ int slam2d_mcl_step_adaptive(const Slam2dLidar* lidar, const Slam2dLevel* level,
                              const Slam2dMclBins* bins, const uint32_t* d_ntab, int32_t ntab_n,
                              int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream);
 
+/* Exact wall distances as a search field: another way to fill the slots of a level, for the calls that read a full field
+ * (slam2d_score_poses, slam2d_search_lattice, slam2d_mcl_step, slam2d_mcl_step_adaptive) -- the likelihood field of Monte-Carlo
+ * localisation (Thrun, Burgard, Fox, Probabilistic Robotics, 6.4) instead of the blurred probSP, whose reach ends at
+ * SLAM2D_MAX_BLUR_RADIUS cells; and, through d_dist2, the clearance map of the occupancy grid.  An added symbol: no struct and no
+ * existing signature changed, the ABI number stays.  For particle p:
+ *   a. frame, axis tables and occupied image are what slam2d_field_build produces for the same arguments: level->frames[p] as the
+ *      frame kernel leaves it (field_min = floor_value, redo = 0, min_known = 0, field_max = 0: zero bounds every field value from
+ *      above; the call does not measure the field), axis_x, axis_y, and a byte of level->occ[p] equals the generation stamp
+ *      (occ_gen, or 1 when occ_gen == 0) iff a map cell of the window is occupied there (occ_bits); the memset when occ_gen == 0
+ *      and the 8 x 8 block flags (tilemask) as in the full build; the same fault bits in d_flags[p]
+ *      (SLAM2D_F_WINDOW_OUTSIDE_MAP, SLAM2D_F_FIELD_INDEX);
+ *   b. with O the set of occupied field cells (a, b) in [0, fh) x [0, fw): d2(i, j) = min over O of (a - i)^2 + (b - j)^2, an
+ *      exact integer (below 2^31 within fmax * fpitch < 2^29), +inf when O is empty; k(i, j) = min(d2(i, j), lut_n - 1);
+ *   c. field[p][i * fpitch + j] = d_lut[k(i, j)] for every (i, j) in [0, fh) x [0, fw) and, where d_dist2 is not NULL,
+ *      d_dist2[(p * fmax + i) * fpitch + j] = k(i, j).  Cells of either image outside the frame are unspecified; nothing outside
+ *      the P * fmax * fpitch words of either image is written;
+ *   d. the slots are handed back as SearchLevel.set_field does on the host: their tilestate is set to 1 and, where freerow is not
+ *      NULL, their freerow rows are zeroed, so a later slam2d_field_build or slam2d_match on the level rebuilds the reference's
+ *      field from scratch and finds no tile that supposedly holds the free-space constant.
+ * PRECONDITION of the consumers: the field holds costs at level->cost_scale -- the caller puts its table's scale there before it
+ * calls them (the build itself does not read cost_scale beyond slam2d_field_build's own check).
+ * Every join is a minimum of integers: the same inputs give the same bits on every call.  The result is clamped at lut_n - 1 <=
+ * 65535, so no cell needs occupancy farther than R = ceil(sqrt(lut_n - 1)) <= 256 rows or columns away: a column pass (rows to
+ * the nearest occupied cell of the column, saturated at R + 1, kept in `field`) and a row pass (min over |b - j| <= R of
+ * (b - j)^2 + g(i, b)^2, a row per block in LDS), each a launch of its own behind the frame and scatter launches.  No floating
+ * point.  Allocates nothing, does not synchronise, raises no fault bit beyond a.  SLAM2D_E_BADARG, before any HIP call: every
+ * case slam2d_field_build refuses, by the same checks, a NULL d_lut, lut_n < 1 or > SLAM2D_DISTANCE_MAX_TABLE, a level without
+ * frames, axis_x, axis_y or field, occ_gen outside 0 .. 255;
+ * SLAM2D_E_TOOLARGE: as in slam2d_field_build. */
+#define SLAM2D_DISTANCE_MAX_TABLE 65536
+int slam2d_field_build_distance(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2dMap* d_maps, int32_t P,
+                                const double* d_centre, int32_t centre_stride,
+                                const uint32_t* d_lut, int32_t lut_n, uint32_t* d_dist2,
+                                uint32_t* d_flags, void* stream);
+
 /* Particle.updateEstimatedPose for P particles (Algorithm/FastSlam.py:77-106): the pose prior of the
  * next scan from the previous matched poses and the raw odometry increment.
  *   d_prev_pose[p*3 + 0..2]  previous matched pose (prevMatchedReading)

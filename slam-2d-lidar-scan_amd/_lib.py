@@ -63,6 +63,7 @@ MCL_MAX_WEIGHT = 0xffffff            # largest integer weight of a particle (24 
 MCL_SCAN_BLOCK = 1024                # particles one block of slam2d_mcl_step's scan launch covers (csrc: MCL_SCAN_BLOCK)
 MCL_ADAPT_REPORT = 24                # 64-bit words of slam2d_mcl_step_adaptive's report
 MCL_MAX_BINS = 1 << 26               # most pose bins (nx * ny * nth) of its KLD count
+DISTANCE_MAX_TABLE = 65536           # most entries of slam2d_field_build_distance's table: squared distances are clamped below it
 
 STAGE_SWEEP,STAGE_BLUR, STAGE_SCATTER, STAGE_UPDATE, STAGE_SELECT, STAGE_ENDPOINTS, STAGE_BOUND, STAGE_EXACT = range(8)
 STAGE_NAMES = {STAGE_SWEEP: "k_sweep", STAGE_BLUR: "k_blur_clamp", STAGE_SCATTER: "k_occ_scatter",
@@ -173,6 +174,8 @@ SIGNATURES = {
     "slam2d_device_count": (C.c_int, []),
     "slam2d_field_build": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), _vp, C.c_int32, _vp, C.c_int32,
                                      _vp, _vp]),
+    "slam2d_field_build_distance": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), _vp, C.c_int32, _vp, C.c_int32,
+                                              _vp, C.c_int32, _vp, _vp, _vp]),
     "slam2d_sweep": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, _vp, C.c_int32, _vp,
                                C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "slam2d_match": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), _vp, C.c_int32, _vp, C.c_int32, _vp,

@@ -682,6 +682,74 @@ __device__ __forceinline__ void scatter_role(const Slam2dLidar& lid, const Slam2
     scatter_expand<NR>(lv, p, fr, w0, lane, words, fyk, ax_s);
 }
 
+// ------------------------------------------------------------------------------------
+// K2d  exact squared Euclidean distance to the nearest occupied field cell, clamped at cap = lut_n - 1, through a table
+//      (slam2d_field_build_distance).  Integers only; every join is a minimum.
+// ------------------------------------------------------------------------------------
+// The result is clamped at cap <= R * R, R = ceil(sqrt(cap)): a cell whose answer is below the cap has its nearest wall fewer
+// than R rows AND fewer than R columns away, so both passes of the separable transform look R cells far and no farther, and a
+// column distance saturated at R + 1 -- (R + 1)^2 > cap -- stands for "none in reach".
+//
+// Column pass: g(i, j) = rows from (i, j) to the nearest occupied cell of column j, saturated at R + 1, into the slot's field
+// image.  One thread = one column of a segment of S rows: down from R rows above the segment, then up from R rows below it, so
+// a thread writes only its own segment and reads nothing another thread writes.
+__global__ __launch_bounds__(256) void k_dist_cols(Slam2dLevel lv, const int R, const int S) {
+    const int p = blockIdx.z;
+    const FieldSize fs = frame_clip(lv, lv.frames[p]);
+    const int j = blockIdx.x * 256 + threadIdx.x, r0 = blockIdx.y * S, r1 = min(r0 + S, fs.fh);
+    if (j >= fs.fw || r0 >= fs.fh) return;
+    const uint8_t* __restrict__ occ = lv.occ + (size_t)p * lv.fmax * lv.fpitch + j;
+    uint32_t* g = lv.field + (size_t)p * lv.fmax * lv.fpitch + j;
+    const uint8_t stamp = occ_stamp(lv);
+    const int sat = R + 1;
+    int d = sat;
+#pragma unroll 4
+    for (int a = max(0, r0 - R); a < r1; ++a) {
+        d = occ[a * lv.fpitch] == stamp ? 0 : min(d + 1, sat);
+        if (a >= r0) g[a * lv.fpitch] = (uint32_t)d;
+    }
+    d = sat;
+#pragma unroll 4
+    for (int a = min(fs.fh, r1 + R) - 1; a >= r0; --a) {
+        d = occ[a * lv.fpitch] == stamp ? 0 : min(d + 1, sat);
+        if (a < r1 && (uint32_t)d < g[a * lv.fpitch]) g[a * lv.fpitch] = (uint32_t)d;
+    }
+}
+
+// Row pass: k(i, j) = min(cap, min over |b - j| <= R of (b - j)^2 + g(i, b)^2); field = lut[k], dist2 = k.  One block = one
+// row: the row of g goes from the field image into LDS as 16-bit values (0 .. 257; fmax <= 23170: 46 KB) before the block
+// overwrites it, so no block reads what another one writes.  A cell stops at the offset whose square reaches its minimum so
+// far; a row without a wall in reach of any of its cells is the cap throughout.
+__global__ __launch_bounds__(256) void k_dist_rows(Slam2dLevel lv, const uint32_t* __restrict__ lut, const int cap, const int R,
+                                                   uint32_t* __restrict__ dist2) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t dist_g_s[];
+    const int p = blockIdx.y, i = blockIdx.x;
+    const FieldSize fs = frame_clip(lv, lv.frames[p]);
+    if (i >= fs.fh) return;                                // (the whole block)
+    const size_t row = ((size_t)p * lv.fmax + i) * lv.fpitch;
+    uint32_t* f = lv.field + row;
+    int near = 0;
+    for (int j = threadIdx.x; j < fs.fw; j += 256) {
+        const uint32_t g = min(f[j], (uint32_t)(R + 1));
+        dist_g_s[j] = (uint16_t)g;
+        near |= g <= (uint32_t)R ? 1 : 0;
+    }
+    const int any = __syncthreads_or(near);
+    for (int j = threadIdx.x; j < fs.fw; j += 256) {
+        int best = cap;
+        if (any) {
+            const int g0 = dist_g_s[j];
+            best = min(best, g0 * g0);
+            for (int o = 1; o * o < best; ++o) {
+                if (j - o >= 0) { const int g = dist_g_s[j - o]; best = min(best, o * o + g * g); }
+                if (j + o < fs.fw) { const int g = dist_g_s[j + o]; best = min(best, o * o + g * g); }
+            }
+        }
+        f[j] = lut[best];
+        if (dist2) dist2[row + j] = (uint32_t)best;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_refresh_bits(const Slam2dMap* __restrict__ maps, const int32_t* __restrict__ index) {
     // one wave = 64 consecutive cells of a row: coalesced 256-byte read, one ballot, two words out
     const Slam2dMap m = maps[index ? index[blockIdx.y] : blockIdx.y];
@@ -5406,12 +5474,13 @@ static int launch_frames(const Slam2dLidar& lid, const Slam2dLevel& lv, const Sl
 static bool fold_field_check(const Slam2dLevel& lv, bool lazy, bool field_max_needed, bool bound_lds) {
     return lazy && (lv.bnb == 0 || (lv.bnb == 1 && bound_lds)) && !sweep_skips(lv) && !field_max_needed && lv.sync != nullptr;
 }
+static void launch_scatter(const Slam2dLevel& lv, const Slam2dMap* d_maps, int P, hipStream_t s) {
+    StageScope prof(SLAM2D_STAGE_SCATTER, s);
+    k_occ_scatter<<<dim3(cdiv(cdiv(lv.wmax, 32) + 1, 64), cdiv(lv.wmax, SCATTER_ROWS), P), dim3(64, 4), (size_t)lv.wmax * sizeof(int32_t), s>>>(lv, d_maps);
+}
 static int launch_field(const Slam2dLevel& lv, const Slam2dMap* d_maps, int P, uint32_t* d_flags, bool lazy, hipStream_t s,
                         bool scattered = false, bool field_max_needed = true, bool bound_lds = false) {
-    if (!scattered) {
-        StageScope prof(SLAM2D_STAGE_SCATTER, s);
-        k_occ_scatter<<<dim3(cdiv(cdiv(lv.wmax, 32) + 1, 64), cdiv(lv.wmax, SCATTER_ROWS), P), dim3(64, 4), (size_t)lv.wmax * sizeof(int32_t), s>>>(lv, d_maps);
-    }
+    if (!scattered) launch_scatter(lv, d_maps, P, s);
     const int ntile = lv.tmax * lv.tmax;
     const bool folded = fold_field_check(lv, lazy, field_max_needed, bound_lds);
     {
@@ -5603,6 +5672,34 @@ int slam2d_field_build(const Slam2dLidar* lidar, const Slam2dLevel* level, const
     lv.bnb = 0;                                        // the full build has no pooled image
     if ((rc = launch_frames(*lidar, lv, d_maps, P, d_centre, centre_stride, d_flags, false, s))) return rc;
     if ((rc = launch_field(lv, d_maps, P, d_flags, false, s))) return rc;
+    return launch_status();
+}
+
+int slam2d_field_build_distance(const Slam2dLidar* lidar, const Slam2dLevel* level, const Slam2dMap* d_maps, int32_t P,
+                                const double* d_centre, int32_t centre_stride, const uint32_t* d_lut, int32_t lut_n,
+                                uint32_t* d_dist2, uint32_t* d_flags, void* stream) {
+    int rc = check_level(lidar, level, P);
+    if (rc) return rc;
+    if (!d_maps || !d_centre || !d_flags || centre_stride < 2) return SLAM2D_E_BADARG;
+    if (!d_lut || lut_n < 1 || lut_n > SLAM2D_DISTANCE_MAX_TABLE) return SLAM2D_E_BADARG;
+    if (!level->frames || !level->axis_x || !level->axis_y || !level->field) return SLAM2D_E_BADARG;
+    if (level->occ_gen < 0 || level->occ_gen > 255) return SLAM2D_E_BADARG;
+    { Slam2dLevel chk = *level; chk.bnb = 0; if ((rc = check_field_args(chk, P, false))) return rc; }
+    hipStream_t s = (hipStream_t)stream;
+    Slam2dLevel lv = *level;
+    lv.bnb = 0;                                        // as the full build: no pooled image
+    if ((rc = launch_frames(*lidar, lv, d_maps, P, d_centre, centre_stride, d_flags, false, s))) return rc;
+    launch_scatter(lv, d_maps, P, s);
+    const int cap = lut_n - 1;
+    int R = 0;
+    while (R * R < cap) ++R;                           // ceil(sqrt(cap)) <= 256
+    const int S = max(R, 32);                          // rows per thread of the column pass: it reads up to S + 2 R
+    k_dist_cols<<<dim3(cdiv(lv.fmax, 256), cdiv(lv.fmax, S), P), 256, 0, s>>>(lv, R, S);
+    k_dist_rows<<<dim3(lv.fmax, P), 256, ((size_t)lv.fmax * sizeof(uint16_t) + 15) & ~(size_t)15, s>>>(lv, d_lut, cap, R, d_dist2);
+    // the slots no longer hold what slam2d_field_build left there (SearchLevel.set_field on the host)
+    const size_t ntile = (size_t)lv.tmax * lv.tmax;
+    if ((rc = (int)hipMemsetAsync(lv.tilestate, 1, (size_t)P * ntile, s))) return rc;
+    if (lv.freerow && (rc = (int)hipMemsetAsync(lv.freerow, 0, (size_t)P * 64 * sizeof(unsigned long long), s))) return rc;
     return launch_status();
 }
 

@@ -248,6 +248,41 @@ def weight_table(cost_scale, temperature=1.0, entries=4096):
     raise ValueError(f"no shift up to 43 lets a table of {entries} entries reach a weight of 0 at a scale of {scale:g}")
 
 
+def likelihood_table(step, sigma, z_hit=0.95, z_rand=0.05, max_dist=None):
+    """The table of slam2d_field_build_distance for the likelihood field of Monte-Carlo localisation (Thrun, Burgard, Fox,
+    Probabilistic Robotics, 6.4): ``(lut, cost_scale)``, lut uint32 [n] indexed by the SQUARED distance, in cells of ``step``
+    metres, from a beam's endpoint to the nearest wall.  p(i) = z_hit * exp(-(i * step^2) / (2 sigma^2)) + z_rand, cost(i) =
+    log(z_hit + z_rand) - log p(i) -- cost(0) = 0 --, c_max = log(z_hit + z_rand) - log(z_rand), cost_scale =
+    cost_scale_for(-c_max), lut[i] = rint(cost(i) * cost_scale).  n is the least length >= 2 whose last entry equals the
+    saturation value rint(c_max * cost_scale); with ``max_dist`` (metres) n is at most floor((max_dist / step)^2) + 2 and the
+    last entry is forced to the saturation value: beyond max_dist a beam is a random measurement."""
+    step, sigma, z_hit, z_rand = float(step), float(sigma), float(z_hit), float(z_rand)
+    for name, v in (("step", step), ("sigma", sigma), ("z_hit", z_hit), ("z_rand", z_rand)):
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError(f"{name} wants a finite positive number, not {v!r}")
+    limit = _lib.DISTANCE_MAX_TABLE
+    longest = limit + 1                                        # one entry more than the call takes: to tell "too long"
+    if max_dist is not None:
+        max_dist = float(max_dist)
+        if not (math.isfinite(max_dist) and max_dist > 0):
+            raise ValueError(f"max_dist wants a finite positive number, not {max_dist!r}")
+        longest = min(longest, math.floor((max_dist / step) ** 2) + 2)
+    c_max = math.log(z_hit + z_rand) - math.log(z_rand)
+    scale = cost_scale_for(-c_max)
+    saturated = np.rint(c_max * scale)
+    i = np.arange(longest, dtype=np.float64)
+    cost = math.log(z_hit + z_rand) - np.log(z_hit * np.exp(-(i * (step * step)) / (2.0 * sigma * sigma)) + z_rand)
+    lut = np.rint(cost * scale)
+    at = np.flatnonzero(lut[1:] == saturated)
+    n = int(at[0]) + 2 if len(at) else longest
+    if n > limit:
+        raise ValueError(f"the table needs more than {limit} entries at a step of {step:g} m and sigma = {sigma:g} m: "
+                         "raise the step or lower sigma / max_dist")
+    lut = lut[:n].copy()
+    lut[-1] = saturated
+    return lut.astype(np.uint32), scale
+
+
 def mcl_report_host(words):
     """The sixteen words of slam2d_mcl_step's report (include/slam2d.h) as a dict: ``cmin``, ``best``, ``W``, ``positive`` (weights
     above zero), ``u0``, ``in_range``, ``distinct`` (ancestors), ``best_pose`` (the best particle's moved pose), ``M`` (offspring
@@ -1138,6 +1173,35 @@ class ParticleEngine:
         self._built[id(level)] = level.serial
         check(self.L.slam2d_field_build(C.byref(self.lidar_c), C.byref(level.c), _ptr(self.d_maps), self.P,
                                         _ptr(d_centre), stride, _ptr(self.flags), _stream()), "slam2d_field_build")
+
+    def field_build_distance(self, level, d_centre, stride, table, dist2=False):
+        """The slots of ``level`` filled from exact wall distances instead of the blur (include/slam2d.h,
+        slam2d_field_build_distance): field = lut[min(d2, len(lut) - 1)], d2 the squared distance in cells to the nearest
+        occupied field cell of the frame ``field_build`` would make.  ``table`` = (lut uint32 [n], cost_scale), e.g.
+        ``likelihood_table``; it is uploaded once and kept with the level, and the level's ``cost_scale`` becomes the table's:
+        the scoring calls read the field at that scale.  ``dist2``: return the clamped squared distances as well, int32
+        [P, fmax, fpitch] on the device (cells outside a frame are unspecified).  A later ``field_build`` or ``match`` on the level
+        rebuilds the blurred field from scratch -- but its ``cost_scale`` stays the table's until the caller puts its own back."""
+        lut, scale = table
+        lut = np.ascontiguousarray(lut, dtype=np.uint32)
+        scale = float(scale)
+        if lut.ndim != 1 or not 1 <= len(lut) <= _lib.DISTANCE_MAX_TABLE:
+            raise ValueError(f"a table of 1 .. {_lib.DISTANCE_MAX_TABLE} entries, not one of shape {lut.shape}")
+        if not (math.isfinite(scale) and scale > 0):
+            raise ValueError("the table's cost_scale wants a positive number")
+        kept = getattr(level, "_distance_lut", None)
+        if kept is None or kept[0] != lut.tobytes():
+            with _on_launch_stream():
+                kept = level._distance_lut = (lut.tobytes(), torch.from_numpy(lut.view(np.int32)).to(self.device))
+        self.refresh_bits()
+        level.next_generation()
+        self._built[id(level)] = level.serial
+        level.c.cost_scale = level.cost_scale = scale
+        out = torch.empty((self.P, level.fmax, level.fpitch), dtype=torch.int32, device=self.device) if dist2 else None
+        check(self.L.slam2d_field_build_distance(C.byref(self.lidar_c), C.byref(level.c), _ptr(self.d_maps), self.P, _ptr(d_centre), stride,
+                                                 _ptr(kept[1]), len(lut), _ptr(out), _ptr(self.flags), _stream()),
+              "slam2d_field_build_distance")
+        return out
 
     def sweep(self, level, d_est, stride, d_ranges, est_moving_dist, d_psi_cs, d_uniform, d_out):
         check(self.L.slam2d_sweep(C.byref(self.lidar_c), C.byref(level.c), self.P, _ptr(d_est), stride,

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import encode_cost, kld_table, mcl_adapt_report_host, mcl_report_host, pinned_stream, weight_table
+from .engine import kld_table, mcl_adapt_report_host, mcl_report_host, pinned_stream, weight_table
 from .matcher import covering_window
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -72,6 +72,9 @@ class Localiser:
     deviations of the motion noise per step (metres, metres, radians; the step's amplitudes are these / sqrt(4/3));
     ``temperature``: of the weights (``engine.weight_table``; 1.0 is the reference's soft-max); ``seed``: the generator's key;
     ``outside_cost``: what an in-range beam that ends outside the field pays (default: free space as the field encodes it).
+    ``likelihood``: None, or the dict of ``ScanMatcher.covering_level``: the poses are weighed against the likelihood field --
+    a table of the exact distance to the nearest wall, slam2d_field_build_distance -- instead of the blurred one, and the default
+    ``outside_cost`` is the table's last entry.
     Seed the set with ``seed_at``, ``seed_from_peaks`` or ``seed_uniform``, then ``step`` or ``run``.
 
     ``adaptive``: None -- the set keeps its size -- or a dict of ``n_min``, ``bin_xy`` (0.5 m), ``bin_theta`` (10 degrees, in
@@ -83,7 +86,7 @@ class Localiser:
     ``count`` from 1 to the capacity."""
 
     def __init__(self, matcher, window, particles=4096, level="fine", sigma=(0.05, 0.05, 0.02), temperature=1.0, seed=0,
-                 outside_cost=None, adaptive=None):
+                 outside_cost=None, adaptive=None, likelihood=None):
         self.matcher = matcher
         self.N = int(particles)
         if not 1 <= self.N <= _lib.MCL_MAX_PARTICLES:
@@ -96,14 +99,14 @@ class Localiser:
         self.scan = 0                                          # the number of the next scan: part of the generator's counter
         cx, cy, half = self.window = covering_window(None, window)
         og = matcher.og
-        lv = self.level = matcher.covering_level(level, half, shared=False)
-        self.outside_cost = int(encode_cost(lv.floor_value, lv.cost_scale)) if outside_cost is None else int(outside_cost)
-        lut, self.shift = weight_table(lv.cost_scale, temperature)
+        lv = self.level = matcher.covering_level(level, half, shared=False, likelihood=likelihood)
+        self.outside_cost = matcher.outside_cost_of(lv) if outside_cost is None else int(outside_cost)
         with pinned_stream():
             og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
             eng = self.eng = og.engine()
-            eng.field_build(lv, eng.to_device([[cx, cy]]), 2)
+            matcher.build_cover(eng, lv, cx, cy)
             eng.take_flags()
+        lut, self.shift = weight_table(lv.cost_scale, temperature)          # (the distance build has put its table's scale there)
         dev = eng.device
         self.d_lut = torch.from_numpy(lut.view(np.int32)).to(dev)
         self.d_pose = [torch.zeros((self.N, 3), dtype=torch.float64, device=dev) for _ in range(2)]     # ping-pong

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import MATCH_DOUBLES, _MATCH_DTYPE, Lattice, ParticleEngine, SearchLevel, encode_cost, pinned_stream
+from .engine import MATCH_DOUBLES, _MATCH_DTYPE, Lattice, ParticleEngine, SearchLevel, encode_cost, likelihood_table, pinned_stream
 
 _level_cache = {}
 
@@ -143,6 +143,31 @@ def covering_radius(half, max_range, step, unit):
             return ctor
     raise ValueError(f"window: a half-edge of {half:g} m at a step of {step:g} m needs "
                      f"{field_build_limits(1.1 * max_range + exact, step, unit)}; score a smaller window or use the coarse level")
+
+
+def distance_table_of(likelihood, step):
+    """(table, cache key) of a covering level's ``likelihood``: (None, ()) for None, else ``engine.likelihood_table`` at ``step``
+    for a dict of ``sigma`` and, optionally, ``z_hit``, ``z_rand``, ``max_dist``."""
+    if likelihood is None:
+        return None, ()
+    if not isinstance(likelihood, dict):
+        raise ValueError(f"likelihood is None or a dict of sigma, z_hit, z_rand, max_dist, not {likelihood!r}")
+    unknown = set(likelihood) - {"sigma", "z_hit", "z_rand", "max_dist"}
+    if unknown or "sigma" not in likelihood:
+        raise ValueError(f"likelihood wants sigma and at most z_hit, z_rand, max_dist, not {sorted(likelihood)}")
+    return likelihood_table(step, **likelihood), tuple(sorted((k, None if v is None else float(v)) for k, v in likelihood.items()))
+
+
+def clearance_table_of(max_dist, step):
+    """(table, cache key) of ``ScanMatcher.clearance``: the identity table -- entry i is i, the field is the clamped squared
+    distance itself --, as long as the call takes, or floor((max_dist / step)^2) + 2 entries."""
+    n = _lib.DISTANCE_MAX_TABLE
+    if max_dist is not None:
+        max_dist = float(max_dist)
+        if not (math.isfinite(max_dist) and max_dist > 0):
+            raise ValueError(f"max_dist wants a finite positive number, not {max_dist!r}")
+        n = min(n, math.floor((max_dist / step) ** 2) + 2)
+    return (np.arange(n, dtype=np.uint32), 1.0), ("clearance", n)
 
 
 # ---- the lattice of ScanMatcher.searchPoses and the peaks of its image, on the host ----
@@ -324,10 +349,18 @@ class ScanMatcher:
             return dict(pose_mean=(est[0] + mean[0], est[1] + mean[1], est[2] + mean[2]), cov=mom["cov"][0], sum_w=sum_w,
                         log_confidence=float(mom["best_score"][0]) + math.log(sum_w) if sum_w > 0 else float("nan"))
 
-    def covering_level(self, level, half, shared=True):
+    def covering_level(self, level, half, shared=True, likelihood=None):
         """The cached level whose field covers a window of half-edge ``half`` at this matcher's fine or coarse configuration
         (step, sigma and miss probability exactly as fine_level() / coarse_level() derive them), with a cube of one angle.
-        ``shared=False``: a level of the caller's own, for a field that has to outlive the call (Localiser)."""
+        ``shared=False``: a level of the caller's own, for a field that has to outlive the call (Localiser).
+        ``likelihood``: None -- the blurred field -- or a dict of ``sigma`` (metres) and, optionally, ``z_hit``, ``z_rand``,
+        ``max_dist``: the level carries ``engine.likelihood_table`` at its step (``lv.distance_table``) and is to be filled by
+        ``ParticleEngine.field_build_distance`` (``build_cover`` does); its ``cost_scale`` becomes the table's, so a shared
+        one is cached under a key of its own and never handed to a caller that expects the blurred field."""
+        return self._covering_level(level, half, shared, lambda step: distance_table_of(likelihood, step))
+
+    def _covering_level(self, level, half, shared, table_of):
+        """``covering_level`` with the distance table, if any, as ``table_of(step)`` = (table, cache key)."""
         if level not in ("fine", "coarse"):
             raise ValueError("level is 'fine' or 'coarse'")
         unit = self.og.unitGridSize
@@ -338,12 +371,56 @@ class ScanMatcher:
         ctor = covering_radius(half, self.og.lidarMaxRange, step, unit)
         kw = dict(step=step, sigma=sigma, miss_prob=miss, search_radius_ctor=ctor, radius=step, half_rad=0.0, fine=True,
                   move_sigma=self.moveRSigma, max_move_dev=self.maxMoveDeviation, turn_sigma=self.turnSigma)
+        table, table_key = table_of(step)
         if not shared:
-            return SearchLevel(self.og.lidar, 1, self.og.device, bnb=False, **kw)
-        key = ("cover", step, sigma, miss, ctor, self.moveRSigma, self.maxMoveDeviation, self.turnSigma)
-        return _shared_level(self.og, key, **kw)
+            lv = SearchLevel(self.og.lidar, 1, self.og.device, bnb=False, **kw)
+        else:
+            key = ("cover", step, sigma, miss, ctor, self.moveRSigma, self.maxMoveDeviation, self.turnSigma)
+            lv = _shared_level(self.og, key if table is None else key + ("distance",) + table_key, **kw)
+        if table is not None:
+            lv.distance_table = table
+        return lv
 
-    def scorePoses(self, poses, reading_or_ranges, level="fine", window=None):
+    @staticmethod
+    def build_cover(eng, lv, cx, cy, dist2=False):
+        """The covering level's field around (cx, cy): the blurred build, or -- a level with a ``distance_table`` -- the
+        distance build."""
+        table = getattr(lv, "distance_table", None)
+        if table is None:
+            return eng.field_build(lv, eng.to_device([[cx, cy]]), 2)
+        return eng.field_build_distance(lv, eng.to_device([[cx, cy]]), 2, table, dist2=dist2)
+
+    @staticmethod
+    def outside_cost_of(lv):
+        """What a beam that leaves the covering field pays by default: free space as the blurred field encodes it, or the
+        table's last entry -- such a beam is a random measurement."""
+        table = getattr(lv, "distance_table", None)
+        return int(encode_cost(lv.floor_value, lv.cost_scale)) if table is None else int(table[0][-1])
+
+    def clearance(self, window, level="fine", max_dist=None):
+        """How far every cell of the covering frame of ``window = (cx, cy, half)`` is from a wall: ``dict(dist, xs, ys)`` with
+        ``dist`` [fh, fw] in metres -- sqrt(k) * step, k the squared distance in cells to the nearest occupied field cell of
+        the frame (include/slam2d.h, slam2d_field_build_distance) --, ``xs`` [fw] and ``ys`` [fh] the cells' centres.  Distances
+        are exact up to ``max_dist`` metres (default and at most: 255 cells); ``inf`` beyond, and everywhere in a frame
+        without a wall.  Cells outside the frame are unknown, not walls."""
+        cx, cy, half = covering_window(None, window)
+        lv = self._covering_level(level, half, True, lambda step: clearance_table_of(max_dist, step))
+        with _Exclusive(lv), pinned_stream():
+            og = self.og
+            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = og.engine()
+            d2 = self.build_cover(eng, lv, cx, cy, dist2=True)
+            bits = int(eng.take_flags()[0])
+            self.last_flags = bits
+            fr = lv.frames()[0]
+            k = d2[0, :fr["fh"], :fr["fw"]].cpu().numpy().astype(np.int64)
+        dist = np.sqrt(k.astype(np.float64)) * lv.step
+        dist[k >= len(lv.distance_table[0]) - 1] = np.inf
+        self.last_cover = dict(level=lv, window=(cx, cy, half))
+        return dict(dist=dist, xs=float(fr["xlo"]) + (np.arange(int(fr["fw"])) + 0.5) * lv.step,
+                    ys=float(fr["ylo"]) + (np.arange(int(fr["fh"])) + 0.5) * lv.step)
+
+    def scorePoses(self, poses, reading_or_ranges, level="fine", window=None, likelihood=None):
         """How well a scan fits at N free poses anywhere in the map (include/slam2d.h, slam2d_score_poses): the reference's score
         of the scan -- convTotal of a fine search at zero offset, no prior (:129-130) -- at each pose ``poses[n] = (x, y,
         theta)``, in ONE launch.  ``reading_or_ranges``: a reading dict, ``[beams]`` ranges for every pose, or ``[N, beams]``, a
@@ -351,6 +428,7 @@ class ScanMatcher:
         bounding box of the finite poses -- or ``window = (cx, cy, half)`` -- plus lidarMaxRange; the map grows to hold that
         frame as in frameSearchSpace (:27).  Returns a dict of [N] host arrays: ``score``, ``cells``, ``beam_score``,
         ``inside``, ``in_range``, ``outside`` (ParticleEngine.score_host); ``self.last_cover`` keeps the level and its frame.
+        ``likelihood``: score against the likelihood field of ``covering_level`` instead of the blurred one.
         ValueError naming ``window`` when the frame is beyond what the field build accepts."""
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
         rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
@@ -361,12 +439,12 @@ class ScanMatcher:
         if rng.shape not in ((B,), (N, B)):
             raise ValueError(f"ranges of shape {rng.shape}: want ({B},) or ({N}, {B})")
         cx, cy, half = covering_window(poses, window)
-        lv = self.covering_level(level, half)
+        lv = self.covering_level(level, half, likelihood=likelihood)
         with _Exclusive(lv), pinned_stream():
             og = self.og
             og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
             eng = og.engine()
-            eng.field_build(lv, eng.to_device([[cx, cy]]), 2)
+            self.build_cover(eng, lv, cx, cy)
             rows = eng.score_poses(lv, 0, eng.to_device(poses), 3, N, eng.to_device(rng), 0 if rng.ndim == 1 else B)
             # one download: the rows and the build's fault word
             host = torch.cat([rows.reshape(-1), eng.flags[:1].to(torch.float64)]).cpu().numpy()
@@ -379,13 +457,15 @@ class ScanMatcher:
             self.last_cover = dict(level=lv, window=(cx, cy, half))
             return eng.score_host(host[:-1])
 
-    def searchPoses(self, reading_or_ranges, window, step=None, headings=120, level="fine", top=5, separation=None, outside_cost=None):
+    def searchPoses(self, reading_or_ranges, window, step=None, headings=120, level="fine", top=5, separation=None, outside_cost=None,
+                    likelihood=None):
         """Where in ``window = (cx, cy, half)`` could this scan have been taken (include/slam2d.h, slam2d_search_lattice): the
         best heading and its cost at every position of a lattice -- ``step`` metres apart (default: the level's step),
         ``headings`` headings over the full turn -- searched on the device: nothing but the scan is uploaded, one 8-byte word
         per POSITION comes back.  The field is the covering level of ``scorePoses`` for this window, built in full.  The cost
         of a pose is ``beam_score`` of ``scorePoses`` in the field's integers plus ``outside_cost`` for every in-range beam
-        that ends outside the field (default: the level's free-space value as the field encodes it).  Returns the arrays of
+        that ends outside the field (default: the level's free-space value as the field encodes it; with ``likelihood`` -- the
+        likelihood field of ``covering_level`` instead of the blurred one -- the table's last entry).  Returns the arrays of
         ``ParticleEngine.search_host`` -- ``cost``, ``heading``, ``score`` [ny, nx], ``xs``, ``ys``, ``thetas`` -- and
         ``peaks``: up to ``top`` ``Peak(x, y, theta, score, cost)``, lowest cost first, no two within ``separation`` metres
         (default: ten lattice steps) of each other on either axis (``lattice_peaks``).  ``self.last_cover`` keeps the level,
@@ -395,16 +475,16 @@ class ScanMatcher:
         if rng.shape != (self.og.numSamplesPerRev,):
             raise ValueError(f"ranges of shape {rng.shape}: want ({self.og.numSamplesPerRev},)")
         cx, cy, half = covering_window(None, window)
-        lv = self.covering_level(level, half)
+        lv = self.covering_level(level, half, likelihood=likelihood)
         lat = window_lattice((cx, cy, half), lv.step if step is None else step, headings)
         sep = 10 if separation is None else int(round(float(separation) / lat.dx))
         if outside_cost is None:
-            outside_cost = int(encode_cost(lv.floor_value, lv.cost_scale))
+            outside_cost = self.outside_cost_of(lv)
         with _Exclusive(lv), pinned_stream():
             og = self.og
             og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
             eng = og.engine()
-            eng.field_build(lv, eng.to_device([[cx, cy]]), 2)
+            self.build_cover(eng, lv, cx, cy)
             words = eng.search_lattice(lv, 0, lat, eng.to_device(rng), outside_cost)
             # one download: the image and the build's fault word
             host = torch.cat([words.reshape(-1), eng.flags[:1].to(torch.int64)]).cpu().numpy()
