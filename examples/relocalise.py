@@ -10,7 +10,8 @@ well does this scan fit at these poses", for any pose set.
 
 With --on-device the lattice search runs in the library instead (ScanMatcher.searchPoses, slam2d_search_lattice): no pose is
 uploaded, the best heading and its cost per position come back -- an image of 161 x 161 words instead of 3.1 million rows --
-and the well-separated runner-up positions are printed beside the best.  --likelihood (with --on-device) searches the likelihood
+and the well-separated runner-up positions are printed beside the best, every one of them refined in one more call
+(ScanMatcher.refinePoses, slam2d_refine_poses: a local search about each peak, below the lattice's step).  --likelihood (with --on-device) searches the likelihood
 field instead of the blurred one (slam2d_field_build_distance; SIGMA in metres, default 0.2): its peak is as wide as SIGMA, not
 as the blur, so a coarser --step still finds it.
 
@@ -100,8 +101,12 @@ def main():
               f"over {s['cells'][best]} cells  refined ({matched['x']:7.2f}, {matched['y']:7.2f}, {matched['theta']:6.3f})  "
               f"off by {np.hypot(matched['x'] - r['x'], matched['y'] - r['y']):.2f} m, {abs(dth):.3f} rad  [{1e3 * dt:.1f} ms for the lattice, build and download included]")
         if args.on_device:
-            for q in found["peaks"][1:]:
-                print(f"     runner-up ({q.x:7.2f}, {q.y:7.2f}, {q.theta:6.3f}) score {q.score:9.2f}")
+            # every peak refined in one call (ScanMatcher.refinePoses, slam2d_refine_poses): the best one beside matchScan's, the runners-up too
+            ref = sm.refinePoses([(q.x, q.y, q.theta) for q in found["peaks"]], r, level=args.level, window=window, **lik)
+            for i, (q, (x, y, th)) in enumerate(zip(found["peaks"], ref["poses"])):
+                print(f"     {'best     ' if i == 0 else 'runner-up'} ({q.x:7.2f}, {q.y:7.2f}, {q.theta:6.3f}) score {q.score:9.2f}  refinePoses "
+                      f"({x:7.3f}, {y:7.3f}, {th:6.3f}) score {ref['score'][i]:9.2f} (cost {int(ref['start_cost'][i])} -> {int(ref['cost'][i])})  "
+                      f"off by {np.hypot(x - r['x'], y - r['y']):.2f} m")
 
 
 if __name__ == "__main__":

@@ -550,6 +550,58 @@ int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, in
                           uint64_t* d_work, uint64_t* d_out, void* stream);
 int64_t slam2d_search_lattice_work(const Slam2dLidar* lidar, int32_t nx, int32_t ny, int32_t nth);
 
+/* A local correlative search around each of N free seed poses, all in ONE field, in one call: the scan matcher on the field of
+ * slam2d_score_poses -- every seed gets the best pose of a small lattice about it, and the result stays on the device, where the
+ * next stage or the next scan starts from it (added symbols: no struct and no existing signature changed, the ABI number stays).
+ * PRECONDITION: that of slam2d_score_poses (a FULL build -- slam2d_field_build or slam2d_field_build_distance -- has run for slot
+ * p_field of `level`, ordered in front of this call); the same members of `level` and `lidar` are read.  Everything below is an
+ * integer operation or ONE rounded IEEE operation at a time (no contraction), so NumPy reproduces it bit for bit.
+ *   a. MOVE.  (x, y, th) = d_pose_in[n * pose_stride + 0..2].  With motion = (dfwd, dside, dturn):  c = cos(th), s = sin(th),
+ *        xm = (x + c * dfwd) - s * dside,   ym = (y + s * dfwd) + c * dside,   tm = th + dturn
+ *      -- step b of slam2d_mcl_step with fx = dfwd, fy = dside and no noise term.  motion == NULL: (xm, ym, tm) = (x, y, th), bit
+ *      for bit.
+ *   b. CANDIDATES.  nx = 2 rx + 1, ny = 2 ry + 1, nth = 2 rt + 1; an axis index j counts from the centre outwards,
+ *        off(j) = ((j + 1) >> 1) * ((j & 1) ? +1 : -1)  =  0, +1, -1, +2, -2, ...
+ *      and candidate (jt, jy, jx), 0 <= jt < nth, 0 <= jy < ny, 0 <= jx < nx, is the pose
+ *        x' = xm + (double)off(jx) * dx,   y' = ym + (double)off(jy) * dy,   th' = tm + (double)off(jt) * dth
+ *      (a rounded product, then an add) with the flat index f = (jt * ny + jy) * nx + jx: f = 0 is the moved seed itself.
+ *   c. COST.  For the pose (x', y', th') and the scan at d_ranges + n * ranges_stride (ranges_stride 0: one scan for all seeds;
+ *      >= beams: a scan per seed), steps 1-4 of slam2d_score_poses define sum_b, the INSIDE beams and the beams IN RANGE, the true
+ *      division, the 1e9 guard and the truncation included;
+ *        cost(f) = sum_b + (uint64)(in_range - inside) * outside_cost           (slam2d_search_lattice's cost, below 2^44)
+ *   d. RESULT.  d_out[n * SLAM2D_REFINE_STRIDE + 0] = the 64-bit minimum over f of (cost(f) << 20 | f): among equal costs the
+ *      candidate nearest the seed in the order of b wins -- a scan without a return leaves the pose where the odometry put it;
+ *      the lowest-index rule of slam2d_search_lattice over a signed lattice would push it into a corner on every scan.
+ *      d_out[n * SLAM2D_REFINE_STRIDE + 1] = cost(0), the moved seed's own cost.
+ *      d_pose_out[n * pose_stride + 0..2] = (x', y', th') of the winning candidate, by the three operations of b (the other
+ *      slots of the stride are untouched).
+ *   e. A seed with a non-finite component has no inside beam at any candidate: every cost is in_range * outside_cost and f = 0
+ *      wins.  No quotient that fails the guard is converted to an integer; no field access leaves [0, fh) x [0, fw).
+ * d_pose_in and d_pose_out are different buffers (stages ping-pong between them).  d_work: slam2d_refine_work(N) = 3 * N 8-byte
+ * words of scratch (the moved seeds; the join needs none: it is on d_out).  The caller need not initialise d_work, d_out or
+ * d_pose_out; the same inputs give the same bits on every call.  The call allocates nothing, raises no fault bit, enqueues three
+ * launches on `stream` -- the move, a thread per seed, which also sets d_out's minima to all ones; the search, a block of 256
+ * threads per seed and group of headings, which evaluates cos / sin nth * beams times per seed (a table of endpoint offsets per
+ * heading in LDS), not once per candidate, and joins with a 64-bit integer atomicMin on d_out; the winning poses, a thread per
+ * seed -- and does not synchronise.  Few seeds spread over the card: a seed's headings are split over up to 1024 / N blocks.
+ * SLAM2D_E_BADARG, before any HIP call: the level and lidar cases of slam2d_score_poses, a NULL d_pose_in, d_pose_out, d_ranges,
+ * d_out or d_work, d_pose_in == d_pose_out, N < 1, pose_stride < 3, ranges_stride neither 0 nor >= beams, rx, ry or rt < 0, a
+ * non-finite dx, dy, dth or motion component; SLAM2D_E_TOOLARGE: nx * ny * nth > SLAM2D_REFINE_MAX_CANDIDATES (the product in 64
+ * bits), more than SLAM2D_REFINE_MAX_BLOCKS blocks in the search launch -- N * ceil(nth / hc), hc = min(max(1, 2048 / beams),
+ * ceil(nth / ceil(1024 / N))) headings per block: N <= 2^23 seeds where nth <= 2048 / beams, N = 2^20 up to eight times that --,
+ * fmax * fpitch >= 2^29.  slam2d_refine_work makes no HIP call; < 0 means SLAM2D_E_* (N < 1: BADARG; N >
+ * SLAM2D_REFINE_MAX_BLOCKS: TOOLARGE). */
+#define SLAM2D_REFINE_STRIDE 2
+#define SLAM2D_REFINE_MAX_CANDIDATES (1 << 20)
+#define SLAM2D_REFINE_MAX_BLOCKS (1 << 23)
+int64_t slam2d_refine_work(int32_t N);
+int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N,
+                        const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                        const double* d_ranges, int32_t ranges_stride,
+                        const double motion[3],                 /* NULL: none */
+                        int32_t rx, int32_t ry, int32_t rt, double dx, double dy, double dth,
+                        uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out, void* stream);
+
 /* One step of Monte-Carlo localisation in a known map: N pose hypotheses are moved by the odometry increment, weighed against the
  * ONE field of slot p_field with slam2d_score_poses' measurement model, resampled, and left on the device -- no host decision in
  * between (an added symbol: no struct and no existing signature changed, the ABI number stays).  PRECONDITION: that of

@@ -12,7 +12,9 @@ with ``importlib.import_module("slam-2d-lidar-scan_amd")`` or through the
 batched counterpart of Algorithm/FastSlam.py's.  ``map_from_poses`` builds the map of a log at
 given poses (Utils/OccupancyGrid.py:main).  ``ScanMatcher.matchMoments`` / ``ParticleFilter.match_moments`` give the pose
 mean and covariance of the last match over its whole pose cube (``ParticleEngine.match_moments``).  ``Localiser`` follows a robot
-through a finished map: Monte-Carlo localisation, one device call per scan (``ParticleEngine.mcl_step``).  All of them need the HIP library
+through a finished map: Monte-Carlo localisation, one device call per scan (``ParticleEngine.mcl_step``); ``Tracker`` follows it with
+one pose and a local search per scan, and ``ScanMatcher.refinePoses`` refines any set of poses that way
+(``ParticleEngine.refine_poses``).  All of them need the HIP library
 (``libslam2d_hip.so``, built by ``__graft_entry__.build()``) and a GPU; there is no
 CPU fallback.
 """
@@ -34,6 +36,8 @@ _LAZY = {
     "MapState": ("engine", "MapState"),
     "map_from_poses": ("mapping", "map_from_poses"),
     "Localiser": ("localise", "Localiser"),
+    "Tracker": ("localise", "Tracker"),
+    "TrackReport": ("localise", "TrackReport"),
 }
 
 

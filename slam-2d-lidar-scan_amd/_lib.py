@@ -57,6 +57,11 @@ PREDICT_STRIDE = 4                   # doubles per (pose, beam) of slam2d_predic
 SCORE_STRIDE = 8                     # doubles per pose of slam2d_score_poses' output: score, |U|, beam score, inside, in range, sum_u, sum_b, 0
 SEARCH_CHUNK = 8                     # headings per block row of slam2d_search_lattice's search launch, at least (csrc: SEARCH_CHUNK)
 SEARCH_WAVES = 4096                  # ... and more where fewer than this many waves of 64 positions would not fill the card otherwise
+REFINE_STRIDE = 2                    # 64-bit words per seed of slam2d_refine_poses' output: cost << 20 | candidate, the seed's own cost
+REFINE_MAX_CANDIDATES = 1 << 20      # most candidates (nx * ny * nth) of one seed
+REFINE_MAX_BLOCKS = 1 << 23          # most blocks of its search launch: seeds x block rows of headings
+REFINE_TABLE = 2048                  # endpoint offsets one block's LDS table holds: at most REFINE_TABLE // beams headings per block row (csrc: REFINE_TABLE)
+REFINE_BLOCKS = 1024                 # ... and fewer, down to one, where fewer than this many seeds would not fill the card (csrc: REFINE_BLOCKS)
 MCL_REPORT = 16                      # 64-bit words of slam2d_mcl_step's report
 MCL_MAX_PARTICLES = 1 << 20
 MCL_MAX_WEIGHT = 0xffffff            # largest integer weight of a particle (24 bits: the weights' sum stays below 2^44)
@@ -188,6 +193,10 @@ SIGNATURES = {
     "slam2d_search_lattice": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_uint32, _vp, _vp, _vp]),
     "slam2d_search_lattice_work": (C.c_int64, [C.POINTER(Slam2dLidar), C.c_int32, C.c_int32, C.c_int32]),
+    "slam2d_refine_work": (C.c_int64, [C.c_int32]),
+    "slam2d_refine_poses": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_int32,
+                                      C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                      C.c_uint32, _vp, _vp, _vp]),
     "slam2d_mcl_work": (C.c_int64, [C.c_int32]),
     "slam2d_mcl_step": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_uint64, _vp, C.c_uint32,

@@ -4462,10 +4462,37 @@ __global__ __launch_bounds__(256) void k_search_table(Slam2dLidar lid, int nth, 
     E[(size_t)it * B + k] = make_double2(cos(a) * r, sin(a) * r);                // :87-88
 }
 
+// The cost of the pose at (x, y) whose heading's endpoint offsets are e[0 .. n_rng): slam2d_search_lattice's cost, for its search
+// launch and slam2d_refine_poses'.  The lane sums the inside beams' costs and counts them in registers -- a beam that is not
+// inside loads cell 0 of the image and adds nothing: no branch in the loop, so the gathers of SEARCH_UNROLL beams are in flight
+// together (the table entries first: one wait for all of them).  n_rng is the same for every lane of the wave.
+__device__ __forceinline__ unsigned long long offsets_cost(const double2* __restrict__ e, const int n_rng, const double x, const double y,
+                                                           const Slam2dFrame& fr, const double step, const FieldSize fs, const int fpitch,
+                                                           const uint32_t* __restrict__ field, const unsigned outside_cost) {
+    unsigned long long sum_b = 0ull;
+    int n_in = 0;
+    const auto beam = [&](const double2 d) {
+        int cx, cy;
+        const bool inside = score_cell(x + d.x, y + d.y, fr.xlo, fr.ylo, step, fs.fw, fs.fh, cx, cy);
+        const uint32_t cost = field[inside ? cy * fpitch + cx : 0];              // (fmax * fpitch < 2^29)
+        sum_b += inside ? cost : 0u;
+        n_in += inside;
+    };
+    int k = 0;
+    for (; k + SEARCH_UNROLL <= n_rng; k += SEARCH_UNROLL) {
+        double2 d[SEARCH_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SEARCH_UNROLL; ++u) d[u] = e[k + u];
+#pragma unroll
+        for (int u = 0; u < SEARCH_UNROLL; ++u) beam(d[u]);
+    }
+    for (; k < n_rng; ++k) beam(e[k]);
+    return sum_b + (unsigned long long)(n_rng - n_in) * outside_cost;
+}
+
 // Search launch: one thread per position (flat index iy * nx + ix: neighbouring lanes read neighbouring field cells), blockIdx.y
 // takes headings [y * hc, y * hc + hc).  The loops over headings and beams are the same for every lane and E is read at a
-// wave-uniform address.  Each lane sums the inside beams' costs and counts them in registers -- a beam that is not inside loads
-// cell 0 of the image and adds nothing: no branch in the loop, so the gathers of several beams are in flight together --, folds
+// wave-uniform address.  Each lane takes a heading's cost from offsets_cost, folds
 // cost << 16 | it into a 64-bit minimum per heading and joins the block rows with one integer atomicMin on d_out, which
 // k_search_table set to all ones in front of this launch on the same stream: a minimum of integers, whatever the order.  Reads
 // frames[p_field], the slot's field, E and the ranges; no fault bit.
@@ -4486,29 +4513,132 @@ __global__ __launch_bounds__(256) void k_search_lattice(Slam2dLidar lid, Slam2dL
     const int it0 = blockIdx.y * hc, it1 = min(nth, it0 + hc);
     unsigned long long best = ~0ull;
     for (int it = it0; it < it1; ++it) {
-        const double2* __restrict__ e = E + (size_t)it * B;
-        unsigned long long sum_b = 0ull;
-        int n_in = 0;
-        const auto beam = [&](const double2 d) {
-            int cx, cy;
-            const bool inside = score_cell(x + d.x, y + d.y, fr.xlo, fr.ylo, lv.step, fs.fw, fs.fh, cx, cy);
-            const uint32_t cost = field[inside ? cy * lv.fpitch + cx : 0];       // (fmax * fpitch < 2^29)
-            sum_b += inside ? cost : 0u;
-            n_in += inside;
-        };
-        int k = 0;
-        for (; k + SEARCH_UNROLL <= n_rng; k += SEARCH_UNROLL) {                 // (the table entries first: one wait for all of them)
-            double2 d[SEARCH_UNROLL];
-#pragma unroll
-            for (int u = 0; u < SEARCH_UNROLL; ++u) d[u] = e[k + u];
-#pragma unroll
-            for (int u = 0; u < SEARCH_UNROLL; ++u) beam(d[u]);
-        }
-        for (; k < n_rng; ++k) beam(e[k]);
-        const unsigned long long cost = sum_b + (unsigned long long)(n_rng - n_in) * outside_cost;
+        const unsigned long long cost = offsets_cost(E + (size_t)it * B, n_rng, x, y, fr, lv.step, fs, lv.fpitch, field, outside_cost);
         best = min(best, (cost << 16) | (unsigned long long)it);
     }
     atomicMin(&out[p], best);
+}
+
+// ---- a local search around each of N seed poses (slam2d_refine_poses) ----
+#define REFINE_TABLE 2048            // endpoint offsets (16 B each) of one block's LDS table: a block row takes at most REFINE_TABLE / beams headings, at least one
+#define REFINE_BLOCKS 1024           // blocks that fill the card (256 CUs x 4): with fewer seeds a seed's headings are split over block rows
+
+// the centre-first order of an axis: 0, +1, -1, +2, -2, ...
+__host__ __device__ __forceinline__ int refine_off(const int j) { return ((j + 1) >> 1) * ((j & 1) ? 1 : -1); }
+
+struct RefineLattice { int nx, ny, nth; double dx, dy, dth; };
+
+// headings per block row: all of them where the seeds alone fill the card, fewer -- down to one -- where they do not, and never
+// more than the LDS table holds
+static int refine_chunk(const int N, const int nth, const int beams) {
+    const int fit = REFINE_TABLE / beams > 1 ? REFINE_TABLE / beams : 1;
+    const long long rows = (REFINE_BLOCKS + (long long)N - 1) / N;                // block rows wanted per seed (>= 1)
+    const long long hc = ((long long)nth + rows - 1) / rows;
+    return hc < fit ? (int)hc : fit;
+}
+
+__device__ __forceinline__ unsigned long long wave64_min_u64(unsigned long long v) {            // (all 64 lanes active)
+    v = min(v, dpp_u64<0xB1>(v)); v = min(v, dpp_u64<0x4E>(v)); v = min(v, dpp_u64<0x141>(v)); v = min(v, dpp_u64<0x140>(v));
+    unsigned long long m = ~0ull;
+#pragma unroll
+    for (int l = 0; l < 64; l += 16)
+        m = min(m, ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l) << 32) |
+                       (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l));
+    return m;
+}
+
+// First launch, one thread per seed: the move (k_mcl_move's, without noise; no motion: the seed's bits) into moved[n][3], and
+// the identity of the search launch's atomicMin into out[2 n].
+__global__ __launch_bounds__(256) void k_refine_move(int N, const double* __restrict__ pose, int pstride, int has_motion, double dfwd, double dside,
+                                                     double dturn, double* __restrict__ moved, unsigned long long* __restrict__ out) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const double x = pose[(size_t)n * pstride], y = pose[(size_t)n * pstride + 1], th = pose[(size_t)n * pstride + 2];
+    double* m = moved + (size_t)n * 3;
+    if (has_motion) {
+        const double c = cos(th), s = sin(th);
+        m[0] = (x + c * dfwd) - s * dside;
+        m[1] = (y + s * dfwd) + c * dside;
+        m[2] = th + dturn;
+    } else {
+        m[0] = x; m[1] = y; m[2] = th;
+    }
+    out[(size_t)n * SLAM2D_REFINE_STRIDE] = ~0ull;
+}
+
+// Search launch: block blockIdx.x = n * rows + row takes headings [row * hc, row * hc + hc) of seed n (hc * beams <= REFINE_TABLE
+// or hc == 1: slam2d_refine_poses).  Three phases, a barrier between them:
+//   1. the scan's beams IN RANGE, compacted in beam order into bidx (ballots: a wave's count, the waves' counts through LDS);
+//   2. E[h][k] = (cos(a) * r, sin(a) * r) of the block's heading h and the k-th beam in range -- the only cos / sin of the search:
+//      a heading's are evaluated once per seed, not once per candidate; the products rounded here so that x + e is x + cos(a) * r;
+//   3. the block's candidates (h, jy, jx), jx fastest, over the threads: neighbouring lanes are neighbouring jx of one heading, so
+//      their gathers fall on neighbouring field cells; every lane runs the same beam loop (offsets_cost).
+// cost << 20 | f is folded per thread and per wave and joins the block rows -- and a block's waves -- with a 64-bit integer
+// atomicMin on out[2 n], which k_refine_move set to all ones: a minimum of integers, whatever the order.  The thread that holds
+// f == 0 stores its cost in out[2 n + 1].  Reads frames[p_field], the slot's field, the moved seeds and the ranges; no fault bit.
+__global__ __launch_bounds__(256) void k_refine_search(Slam2dLidar lid, Slam2dLevel lv, int p_field, int rows, int hc, RefineLattice lat,
+                                                       const double* __restrict__ moved, const double* __restrict__ ranges, int rstride,
+                                                       unsigned outside_cost, unsigned long long* __restrict__ out) {
+    __shared__ double2 E[REFINE_TABLE];
+    __shared__ unsigned short bidx[SLAM2D_MAX_BEAMS];
+    __shared__ int wcount[4];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int n = (int)(blockIdx.x / (unsigned)rows), row = (int)(blockIdx.x - (unsigned)n * (unsigned)rows);
+    const int jt0 = row * hc, hn = min(hc, lat.nth - jt0);
+    const Slam2dFrame fr = lv.frames[p_field];
+    const FieldSize fs = frame_clip(lv, fr);
+    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const double xm = moved[(size_t)n * 3], ym = moved[(size_t)n * 3 + 1], tm = moved[(size_t)n * 3 + 2];
+    const double* __restrict__ rg = ranges + (size_t)n * rstride;
+    const int B = lid.beams;
+    int n_rng = 0;                                                               // beams in range (block-uniform)
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int b = b0 + tid;
+        const bool in_range = b < B && rg[b] < lid.max_range;                    // :84 (NaN and +inf are out, 0 and negatives in)
+        const unsigned long long mask = __ballot(in_range);
+        if (lane == 0) wcount[wv] = __popcll(mask);
+        __syncthreads();
+        int base = n_rng;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int c = wcount[w];
+            if (w < wv) base += c;
+            n_rng += c;
+        }
+        if (in_range) bidx[base + __popcll(mask & ((1ull << lane) - 1ull))] = (unsigned short)b;
+        __syncthreads();
+    }
+    for (int i = tid; i < hn * n_rng; i += 256) {                                // (hn * n_rng <= REFINE_TABLE)
+        const int h = i / n_rng, b = bidx[i - h * n_rng];
+        const double r = rg[b];
+        const double a = fan_of(lid, tm + (double)refine_off(jt0 + h) * lat.dth).angle(b);
+        E[i] = make_double2(cos(a) * r, sin(a) * r);                             // :87-88
+    }
+    __syncthreads();
+    const int P = lat.nx * lat.ny, f0 = jt0 * P;                                 // (nx * ny * nth <= 2^20)
+    unsigned long long best = ~0ull;
+    for (int c = tid; c < hn * P; c += 256) {
+        const int h = c / P, p = c - h * P, jy = p / lat.nx, jx = p - jy * lat.nx;
+        const double x = xm + (double)refine_off(jx) * lat.dx, y = ym + (double)refine_off(jy) * lat.dy;
+        const unsigned long long cost = offsets_cost(E + h * n_rng, n_rng, x, y, fr, lv.step, fs, lv.fpitch, field, outside_cost);
+        if (f0 + c == 0) out[(size_t)n * SLAM2D_REFINE_STRIDE + 1] = cost;
+        best = min(best, (cost << 20) | (unsigned long long)(f0 + c));
+    }
+    best = wave64_min_u64(best);
+    if (lane == 0 && best != ~0ull) atomicMin(&out[(size_t)n * SLAM2D_REFINE_STRIDE], best);
+}
+
+// Last launch, one thread per seed: the winning candidate's pose from its flat index, by the candidates' own three operations
+__global__ __launch_bounds__(256) void k_refine_pose(int N, RefineLattice lat, const double* __restrict__ moved,
+                                                     const unsigned long long* __restrict__ out, double* __restrict__ pose, int pstride) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const int f = (int)(out[(size_t)n * SLAM2D_REFINE_STRIDE] & 0xfffffull);
+    const int P = lat.nx * lat.ny, jt = f / P, p = f - jt * P, jy = p / lat.nx, jx = p - jy * lat.nx;
+    double* o = pose + (size_t)n * pstride;
+    o[0] = moved[(size_t)n * 3] + (double)refine_off(jx) * lat.dx;
+    o[1] = moved[(size_t)n * 3 + 1] + (double)refine_off(jy) * lat.dy;
+    o[2] = moved[(size_t)n * 3 + 2] + (double)refine_off(jt) * lat.dth;
 }
 
 // ---- Monte-Carlo localisation in a known map (slam2d_mcl_step): move, weigh, resample, all in integers and rounded operations ----
@@ -5941,6 +6071,41 @@ int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, in
     k_search_table<<<(unsigned)((first + 255) / 256), 256, 0, s>>>(*lidar, nth, th0, dth, d_ranges, E, (unsigned long long*)d_out, positions);
     k_search_lattice<<<dim3((unsigned)blocks, (unsigned)rows), 256, 0, s>>>(*lidar, *level, p_field, nx, positions, nth, hc, x0, dx, y0, dy,
                                                                            d_ranges, E, outside_cost, (unsigned long long*)d_out);
+    return launch_status();
+}
+
+int64_t slam2d_refine_work(int32_t N) {
+    if (N < 1) return SLAM2D_E_BADARG;
+    if (N > SLAM2D_REFINE_MAX_BLOCKS) return SLAM2D_E_TOOLARGE;
+    return 3ll * N;                                                               // the moved seeds; the join is on d_out itself
+}
+
+int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose_in,
+                        double* d_pose_out, int32_t pose_stride, const double* d_ranges, int32_t ranges_stride, const double motion[3],
+                        int32_t rx, int32_t ry, int32_t rt, double dx, double dy, double dth, uint32_t outside_cost, uint64_t* d_work,
+                        uint64_t* d_out, void* stream) {
+    const int frc = check_scored_field(lidar, level, p_field);
+    if (frc == SLAM2D_E_BADARG) return frc;
+    if (!d_pose_in || !d_pose_out || !d_ranges || !d_out || !d_work || d_pose_in == d_pose_out) return SLAM2D_E_BADARG;
+    if (N < 1 || pose_stride < 3 || (ranges_stride != 0 && ranges_stride < lidar->beams) || rx < 0 || ry < 0 || rt < 0) return SLAM2D_E_BADARG;
+    if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
+    for (int i = 0; motion && i < 3; ++i)
+        if (!__builtin_isfinite(motion[i])) return SLAM2D_E_BADARG;
+    const long long nx = 2ll * rx + 1, ny = 2ll * ry + 1, nth = 2ll * rt + 1;     // (each below 2^32)
+    if (nx > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny * nth > SLAM2D_REFINE_MAX_CANDIDATES)
+        return SLAM2D_E_TOOLARGE;
+    const int hc = refine_chunk(N, (int)nth, lidar->beams);
+    const long long rows = (nth + hc - 1) / hc;
+    if (N > SLAM2D_REFINE_MAX_BLOCKS || N * rows > SLAM2D_REFINE_MAX_BLOCKS) return SLAM2D_E_TOOLARGE;       // (256 threads each: below 2^32)
+    if (frc) return frc;
+    hipStream_t s = (hipStream_t)stream;
+    const RefineLattice lat{(int)nx, (int)ny, (int)nth, dx, dy, dth};
+    double* moved = reinterpret_cast<double*>(d_work);
+    unsigned long long* out = (unsigned long long*)d_out;
+    k_refine_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion != nullptr, motion ? motion[0] : 0.0, motion ? motion[1] : 0.0,
+                                               motion ? motion[2] : 0.0, moved, out);
+    k_refine_search<<<(unsigned)(N * rows), 256, 0, s>>>(*lidar, *level, p_field, (int)rows, hc, lat, moved, d_ranges, ranges_stride, outside_cost, out);
+    k_refine_pose<<<cdiv(N, 256), 256, 0, s>>>(N, lat, moved, out, d_pose_out, pose_stride);
     return launch_status();
 }
 

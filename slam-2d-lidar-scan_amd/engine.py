@@ -283,6 +283,18 @@ def likelihood_table(step, sigma, z_hit=0.95, z_rand=0.05, max_dist=None):
     return lut.astype(np.uint32), scale
 
 
+def refine_offsets(r):
+    """The signed steps of one axis of slam2d_refine_poses' candidates in index order, int64 [2 r + 1]: centre first -- 0, +1, -1,
+    +2, -2, ..."""
+    j = np.arange(2 * int(r) + 1, dtype=np.int64)
+    return ((j + 1) >> 1) * np.where(j & 1, 1, -1)
+
+
+def refine_host(words, radii, steps, cost_scale):
+    """``ParticleEngine.refine_host`` (no engine needed)."""
+    return ParticleEngine.refine_host(words, radii, steps, cost_scale)
+
+
 def mcl_report_host(words):
     """The sixteen words of slam2d_mcl_step's report (include/slam2d.h) as a dict: ``cmin``, ``best``, ``W``, ``positive`` (weights
     above zero), ``u0``, ``in_range``, ``distinct`` (ancestors), ``best_pose`` (the best particle's moved pose), ``M`` (offspring
@@ -1315,6 +1327,50 @@ class ParticleEngine:
         cost = w >> np.uint64(16)
         return dict(cost=cost, heading=(w & np.uint64(0xffff)).astype(np.int64), score=-(cost.astype(np.float64) * (1.0 / cost_scale)),
                     xs=lat.xs, ys=lat.ys, thetas=lat.thetas)
+
+    def refine_poses(self, level, p_field, d_in, d_out, N, pose_stride, d_ranges, ranges_stride, radii, steps, outside_cost, motion=None,
+                     d_words=None):
+        """A local search around each of the N seed poses ``d_in[n * pose_stride + 0..2]`` in the field that a full build left in
+        slot ``p_field`` of ``level`` (include/slam2d.h, slam2d_refine_poses): the best of the (2 rx + 1)(2 ry + 1)(2 rt + 1)
+        candidates ``radii = (rx, ry, rt)`` steps of ``steps = (dx, dy, dth)`` about every seed -- moved by ``motion`` = (dfwd,
+        dside, dturn) first, if given -- goes to ``d_out`` (another buffer of the same stride), and ``[N, 2]`` int64 words come
+        back on the device (``d_words``, or a new tensor): cost << 20 | candidate, and the moved seed's own cost.
+        ``ranges_stride`` 0: the one scan ``d_ranges[0..beams)`` for every seed; >= beams: a scan per seed.  Three launches on the
+        current stream, no synchronisation; the scratch is kept and grown; ``refine_host`` decodes."""
+        if not 0 <= p_field < level.P:
+            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        n = int(self.L.slam2d_refine_work(N))
+        if n < 0:
+            check(n, "slam2d_refine_work")
+        if d_in.numel() < (N - 1) * pose_stride + 3 or d_out.numel() < (N - 1) * pose_stride + 3:
+            raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {N} poses, {pose_stride} doubles apart")
+        work = getattr(self, "_refine_work", None)
+        if work is None or work.numel() < n:
+            work = self._refine_work = torch.empty(n, dtype=torch.int64, device=self.device)
+        out = torch.empty((N, _lib.REFINE_STRIDE), dtype=torch.int64, device=self.device) if d_words is None else d_words
+        if out.numel() < N * _lib.REFINE_STRIDE or out.element_size() != 8:
+            raise ValueError(f"d_words wants {N} x {_lib.REFINE_STRIDE} 64-bit words")
+        rx, ry, rt = (int(v) for v in radii)
+        dx, dy, dth = (float(v) for v in steps)
+        check(self.L.slam2d_refine_poses(C.byref(self.lidar_c), C.byref(level.c), p_field, N, _ptr(d_in), _ptr(d_out), pose_stride,
+                                         _ptr(d_ranges), ranges_stride, None if motion is None else (C.c_double * 3)(*[float(v) for v in motion]),
+                                         rx, ry, rt, dx, dy, dth, int(outside_cost), _ptr(work), _ptr(out), _stream()), "slam2d_refine_poses")
+        return out
+
+    @staticmethod
+    def refine_host(words, radii, steps, cost_scale):
+        """The words of ``refine_poses`` as a dict of host arrays [N]: ``cost`` (uint64, the winning candidate's), ``index`` (its
+        flat index: 0 is the moved seed), ``offsets`` [N, 3] (int: its signed steps in x, y and theta), ``start_cost`` (uint64,
+        the moved seed's own), ``score`` = -cost / cost_scale and ``moved`` (bool: another candidate than the seed won)."""
+        w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
+        w = np.ascontiguousarray(w).view(np.uint64).reshape(-1, _lib.REFINE_STRIDE)
+        nx, ny, nth = (2 * int(r) + 1 for r in radii)
+        index = (w[:, 0] & np.uint64((1 << 20) - 1)).astype(np.int64)
+        cost = w[:, 0] >> np.uint64(20)
+        jt, jy, jx = index // (ny * nx), index // nx % ny, index % nx
+        offsets = np.stack([refine_offsets(radii[0])[jx], refine_offsets(radii[1])[jy], refine_offsets(radii[2])[np.minimum(jt, nth - 1)]], axis=1)
+        return dict(cost=cost, index=index, offsets=offsets, start_cost=w[:, 1].copy(), score=-(cost.astype(np.float64) / cost_scale),
+                    moved=index != 0)
 
     def mcl_step(self, level, p_field, d_in, d_out, N, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift, d_report,
                  d_ancestor=None):

@@ -1,4 +1,5 @@
-"""``Localiser``: Monte-Carlo localisation in a map that is already built -- follow a robot through it, scan by scan.
+"""``Localiser``: Monte-Carlo localisation in a map that is already built -- follow a robot through it, scan by scan.  ``Tracker``
+(below it): the same with ONE pose and a local search per scan, for a robot whose start is known.
 
 N pose hypotheses live on the device.  One call per scan (slam2d_mcl_step, include/slam2d.h) moves them by the odometry
 increment, weighs them against ONE field of the map built once, resamples them and leaves the new set where it was: a scan
@@ -6,14 +7,15 @@ costs an upload of its ranges and, if the estimate is wanted at once, a download
 and rounded IEEE operations, so a run is the same bits every time; the generator is restated here in NumPy for the host-side
 seeding of the set.
 """
+import collections
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from .engine import kld_table, mcl_adapt_report_host, mcl_report_host, pinned_stream, weight_table
-from .matcher import covering_window
+from .engine import kld_table, mcl_adapt_report_host, mcl_report_host, pinned_stream, refine_host, weight_table
+from .matcher import check_stages, covering_window
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 _MASK = np.uint64(0xffffffff)
@@ -235,3 +237,86 @@ class Localiser:
                 self._enqueue(d_rng[i], odometry_motion(readings[i - 1], readings[i]) if i else (0.0, 0.0, 0.0), d_rep[i])
             host = d_rep.cpu().numpy()
         return [mcl_report_host(row) if self.adaptive is None else mcl_adapt_report_host(row) for row in host]
+
+
+TrackReport = collections.namedtuple("TrackReport", "pose cost start_cost offsets")
+
+
+class Tracker:
+    """Position tracking in ``matcher``'s map, taken as static: ONE pose follows the robot, scan by scan -- the cheapest
+    localisation, for a robot whose start is known (``ScanMatcher.searchPoses`` finds one).
+
+    ``window = (cx, cy, half)``, ``level``, ``likelihood`` and ``outside_cost`` as for ``Localiser``: the constructor builds the
+    covering field ONCE, in a level of its own.  ``stages``: those of ``ScanMatcher.refinePoses`` (None: ``default_stages`` of
+    the level's step).  A scan moves the pose by the odometry increment and searches the stages' lattices about it
+    (slam2d_refine_poses, include/slam2d.h, with N = 1; the motion goes into the first stage): the pose lives on the device
+    across calls, a scan costs an upload of its ranges and, if the pose is wanted at once, a download of 24 + 16 bytes per
+    stage.  Integer costs and rounded operations: a run is the same bits every time."""
+
+    def __init__(self, matcher, window, level="fine", stages=None, likelihood=None, outside_cost=None):
+        self.matcher = matcher
+        cx, cy, half = self.window = covering_window(None, window)
+        og = matcher.og
+        lv = self.level = matcher.covering_level(level, half, shared=False, likelihood=likelihood)
+        self.stages = check_stages(stages, lv.step)
+        self.outside_cost = matcher.outside_cost_of(lv) if outside_cost is None else int(outside_cost)
+        with pinned_stream():
+            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = self.eng = og.engine()
+            matcher.build_cover(eng, lv, cx, cy)
+            eng.take_flags()
+        dev = eng.device
+        self.d_pose = [torch.zeros(3, dtype=torch.float64, device=dev) for _ in range(2)]               # ping-pong
+        self.cur = 0
+        self.d_ranges = torch.empty(og.numSamplesPerRev, dtype=torch.float64, device=dev)
+        # what one step downloads: the pose, then the stages' words (as doubles' bits)
+        self.d_report = torch.empty(3 + _lib.REFINE_STRIDE * len(self.stages), dtype=torch.float64, device=dev)
+
+    def set_pose(self, pose):
+        pose = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(3))
+        self.d_pose[self.cur].copy_(torch.from_numpy(pose))
+        return pose
+
+    def pose(self):
+        """The current pose, downloaded: (x, y, theta)."""
+        return tuple(float(v) for v in self.d_pose[self.cur].cpu().numpy())
+
+    def _enqueue(self, d_ranges, motion, d_pose_out, d_words):
+        """The stages of one scan; the last one's pose also goes to ``d_pose_out`` [3], the words to ``d_words`` [stages, 2] (int64)."""
+        for i, (radii, steps) in enumerate(self.stages):
+            self.eng.refine_poses(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], 1, 3, d_ranges, 0, radii, steps,
+                                  self.outside_cost, motion=motion if i == 0 else None, d_words=d_words[i])
+            self.cur = 1 - self.cur
+        d_pose_out.copy_(self.d_pose[self.cur])
+
+    def _report(self, pose, words):
+        dec = [refine_host(words[i], radii, steps, self.level.cost_scale) for i, (radii, steps) in enumerate(self.stages)]
+        return TrackReport(tuple(float(v) for v in pose), int(dec[-1]["cost"][0]), int(dec[0]["start_cost"][0]),
+                           np.stack([d["offsets"][0] for d in dec]))
+
+    def step(self, reading_or_ranges, motion):
+        """One scan: the pose moved by ``motion`` = (dfwd, dside, dturn) in the robot's own previous frame (None: not moved), then
+        refined against the scan.  One small download; returns ``TrackReport(pose, cost, start_cost, offsets)``: the new pose,
+        its cost, the cost of the moved pose before the search and the stages' signed steps [stages, 3]."""
+        self.d_ranges.copy_(torch.from_numpy(_ranges_of(reading_or_ranges, self.d_ranges.numel())))
+        with pinned_stream():
+            self._enqueue(self.d_ranges, motion, self.d_report[:3], self.d_report[3:].view(torch.int64).view(len(self.stages), _lib.REFINE_STRIDE))
+            host = self.d_report.cpu().numpy()
+        return self._report(host[:3], host[3:].view(np.uint64).reshape(len(self.stages), _lib.REFINE_STRIDE))
+
+    def run(self, readings):
+        """A log, as ``Localiser.run`` takes it: the motion of scan i is the step from raw odometry pose i - 1 to i in the frame of
+        pose i - 1 (nothing for the first scan).  Every scan is enqueued without a synchronisation; ONE download of the [S, 3]
+        poses and the [S, stages, 2] words ends the call.  Returns the list of ``TrackReport``s."""
+        beams = self.d_ranges.numel()
+        rng = np.stack([_ranges_of(r, beams) for r in readings])
+        S, T = len(readings), len(self.stages)
+        with pinned_stream():
+            dev = self.eng.device
+            d_rng = torch.from_numpy(rng).to(dev)
+            d_rep = torch.empty((S, 3 + _lib.REFINE_STRIDE * T), dtype=torch.float64, device=dev)
+            for i in range(S):
+                self._enqueue(d_rng[i], odometry_motion(readings[i - 1], readings[i]) if i else None, d_rep[i, :3],
+                              d_rep[i, 3:].view(torch.int64).view(T, _lib.REFINE_STRIDE))
+            host = d_rep.cpu().numpy()
+        return [self._report(row[:3], row[3:].view(np.uint64).reshape(T, _lib.REFINE_STRIDE)) for row in host]

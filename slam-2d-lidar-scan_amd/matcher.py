@@ -214,6 +214,34 @@ def lattice_peaks(cost, heading, top, separation_cells):
     return np.array(peaks, dtype=np.int64).reshape(-1, 3)
 
 
+# ---- the stages of ScanMatcher.refinePoses and Tracker ----
+def default_stages(step):
+    """The stages ((rx, ry, rt), (dx, dy, dth)) of a refinement at a level of this step: four cells and 0.08 rad either way at one
+    cell and 0.02 rad, then two half cells and 0.01 rad at half a cell and 0.005 rad."""
+    step = float(step)
+    return (((4, 4, 4), (step, step, 0.02)), ((2, 2, 2), (step / 2, step / 2, 0.005)))
+
+
+def check_stages(stages, step):
+    """``stages`` (None: ``default_stages(step)``) as a tuple of ((rx, ry, rt), (dx, dy, dth)) of ints >= 0 and finite floats,
+    each with at most 2^20 candidates; ValueError otherwise."""
+    out = []
+    for st in default_stages(step) if stages is None else stages:
+        try:
+            (rx, ry, rt), (dx, dy, dth) = st
+            radii, steps = (int(rx), int(ry), int(rt)), (float(dx), float(dy), float(dth))
+        except (TypeError, ValueError):
+            raise ValueError(f"a stage is ((rx, ry, rt), (dx, dy, dth)), not {st!r}") from None
+        if min(radii) < 0 or radii != (rx, ry, rt) or not all(math.isfinite(v) for v in steps):
+            raise ValueError(f"a stage wants whole radii >= 0 and finite steps, not {st!r}")
+        if (2 * radii[0] + 1) * (2 * radii[1] + 1) * (2 * radii[2] + 1) > _lib.REFINE_MAX_CANDIDATES:
+            raise ValueError(f"a stage of more than {_lib.REFINE_MAX_CANDIDATES} candidates: {st!r}")
+        out.append((radii, steps))
+    if not out:
+        raise ValueError("no stages")
+    return tuple(out)
+
+
 class ScanMatcher:
     def __init__(self, og, searchRadius, searchHalfRad, scanSigmaInNumGrid, moveRSigma, maxMoveDeviation, turnSigma,
                  missMatchProbAtCoarse, coarseFactor):
@@ -499,6 +527,55 @@ class ScanMatcher:
         res["peaks"] = [Peak(float(res["xs"][ix]), float(res["ys"][iy]), float(res["thetas"][it]), float(res["score"][iy, ix]),
                              int(res["cost"][iy, ix])) for iy, ix, it in lattice_peaks(res["cost"], res["heading"], top, sep)]
         return res
+
+    def refinePoses(self, poses, reading_or_ranges, stages=None, level="fine", window=None, likelihood=None, outside_cost=None):
+        """The best pose near each of N free seed poses (include/slam2d.h, slam2d_refine_poses): a local correlative search about
+        every ``poses[n] = (x, y, theta)`` in the covering level of ``scorePoses`` and ``searchPoses`` -- the same frame planning
+        (the bounding box of the finite seeds, or ``window``), the same ``likelihood`` and the same ``outside_cost`` default --,
+        with the cost of ``searchPoses``.  ``stages``: a sequence of ((rx, ry, rt), (dx, dy, dth)) -- radii in steps, steps in
+        metres and radians --, run in turn on the device, each from the poses the one before it left (None:
+        ``default_stages`` of the level's step).  ``reading_or_ranges``: a reading dict, ``[beams]`` ranges for every seed, or
+        ``[N, beams]``, a scan per seed.  One download.  Returns a dict of host arrays: ``poses`` [N, 3], ``cost`` (uint64, of
+        the last stage's winner), ``score`` = -cost / cost_scale, ``start_cost`` (the seed's own) and ``offsets`` [N, stages, 3]
+        (each stage's signed steps in x, y, theta); ``self.last_cover`` keeps the level and its window."""
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
+        rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
+        N, B = len(poses), self.og.numSamplesPerRev
+        if N == 0:
+            raise ValueError("no poses")
+        if rng.shape not in ((B,), (N, B)):
+            raise ValueError(f"ranges of shape {rng.shape}: want ({B},) or ({N}, {B})")
+        cx, cy, half = covering_window(poses, window)
+        lv = self.covering_level(level, half, likelihood=likelihood)
+        stages = check_stages(stages, lv.step)
+        if outside_cost is None:
+            outside_cost = self.outside_cost_of(lv)
+        with _Exclusive(lv), pinned_stream():
+            og = self.og
+            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = og.engine()
+            self.build_cover(eng, lv, cx, cy)
+            d_pose = [eng.to_device(poses), torch.empty((N, 3), dtype=torch.float64, device=eng.device)]
+            d_rng = eng.to_device(rng)
+            words = torch.empty((len(stages), N, _lib.REFINE_STRIDE), dtype=torch.int64, device=eng.device)
+            for i, (radii, steps) in enumerate(stages):
+                eng.refine_poses(lv, 0, d_pose[i & 1], d_pose[1 - (i & 1)], N, 3, d_rng, 0 if rng.ndim == 1 else B, radii, steps, outside_cost,
+                                 d_words=words[i])
+            # one download: the poses, the stages' words and the build's fault word
+            host = torch.cat([d_pose[len(stages) & 1].reshape(-1), words.reshape(-1).view(torch.float64),
+                              eng.flags[:1].to(torch.float64)]).cpu().numpy()
+            bits = int(host[-1])
+            if bits:
+                eng.flags.zero_()
+                if bits & _lib.FATAL_FLAGS:
+                    raise _lib.Slam2dError(f"refinePoses: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
+            self.last_flags = bits
+            self.last_cover = dict(level=lv, window=(cx, cy, half), stages=stages)
+        w = host[3 * N:-1].view(np.uint64).reshape(len(stages), N, _lib.REFINE_STRIDE)
+        dec = [ParticleEngine.refine_host(w[i], radii, steps, lv.cost_scale) for i, (radii, steps) in enumerate(stages)]
+        return dict(poses=host[:3 * N].reshape(N, 3).copy(), cost=dec[-1]["cost"], score=dec[-1]["score"], start_cost=dec[0]["start_cost"],
+                    offsets=np.stack([d["offsets"] for d in dec], axis=1))
 
     def searchToMatch(self, probSP, estimatedX, estimatedY, estimatedTheta, rMeasure, xRangeList, yRangeList,
                       searchRadius, searchHalfRad, unitLength, estMovingDist, estMovingTheta, fineSearch=False,
