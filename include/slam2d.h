@@ -602,6 +602,61 @@ int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int3
                         int32_t rx, int32_t ry, int32_t rt, double dx, double dy, double dth,
                         uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out, void* stream);
 
+/* The two on-device searches for a SET OF POINTS in the robot's frame instead of one scan of one sensor: several scans joined by
+ * odometry, two sensors on one robot, a sensor off the robot's origin, a driver's own or de-skewed beam angles -- whatever the
+ * caller can express as points (added symbols: no struct and no existing signature changed, the ABI number stays).  The scan
+ * forms look at a beam in one place only, the table of endpoint offsets per heading; here that table is R(theta) q, and
+ * everything behind it is slam2d_search_lattice's and slam2d_refine_poses'.  PRECONDITION: that of slam2d_score_poses (a FULL
+ * build -- slam2d_field_build or slam2d_field_build_distance -- has run for slot p_field of `level`, ordered in front of this
+ * call); the same members of `level` are read.  No Slam2dLidar is taken: nothing of one is read.  Everything below is an integer
+ * operation or ONE rounded IEEE operation at a time (no contraction), so NumPy reproduces it bit for bit.
+ * Point k of a set, 0 <= k < M, is (qx, qy) = d_points[k * point_stride + 0..1] in the robot's frame: x forward, y to the left,
+ * metres (the other slots of the stride are not read).  For a pose (x, y, th):
+ *   1. point k is VALID iff qx and qy are both finite; invalid points are dropped, as beams out of range are.  valid = their
+ *      number: it does not depend on the pose;
+ *   2. c = cos(th), s = sin(th);  ex = (c * qx) - (s * qy),  ey = (s * qx) + (c * qy);
+ *   3. px = x + ex, py = y + ey, and from there steps 3-4 of slam2d_score_poses as written there: the true division
+ *      (px - xlo) / step, the 1e9 guard in front of the conversion, the truncation, 0 <= cx < fw and 0 <= cy < fh; sum_b = the
+ *      sum of field[cy * fpitch + cx] over the INSIDE points, duplicates counted;
+ *   4. cost = sum_b + (uint64)(valid - inside) * outside_cost                  (below 2^44 at SLAM2D_MAX_POINTS points)
+ * A valid point whose rotated offset overflows, or a non-finite pose component, leaves the point not inside: it pays
+ * outside_cost.  No quotient that fails the guard reaches a conversion to an integer; no field access leaves [0, fh) x [0, fw).
+ * A set without a valid point costs 0 at every pose.
+ * slam2d_search_points is slam2d_search_lattice with that cost: the same lattice poses x0 + (double)ix * dx, y0 + (double)iy * dy,
+ * th0 + (double)it * dth, the same word d_out[iy * nx + ix] = the 64-bit minimum over it of (cost << 16 | it), the same two
+ * launches -- the table E[it][k] = (ex, ey) of the k-th valid point in d_work (slam2d_search_points_work(M, nx, ny, nth) =
+ * 2 * nth * M 8-byte words) with the initial all-ones of d_out, a block per heading; then the search with its atomicMin join.
+ * cos / sin are evaluated nth times, not nth * M times.
+ * slam2d_refine_points is slam2d_refine_poses with that cost: the same MOVE (a), CANDIDATES (b: off(j), the flat index f) and
+ * RESULT (d: cost << 20 | f, cost(0) in word 1, the winning pose by the candidates' three operations; e: a seed with a
+ * non-finite component keeps f = 0), d_work of slam2d_refine_work(N) words and the same three launches; the search block keeps
+ * its table in LDS, at most 2048 / M headings per block row, a seed's headings split over up to 1024 / N blocks.  cos / sin are
+ * evaluated once per heading and seed.  set_stride 0: the one set d_points for every seed; set_stride >= M * point_stride
+ * doubles: a set per seed, seed n's at d_points + n * set_stride.
+ * In both the caller need not initialise d_work, d_out or d_pose_out; the same inputs give the same bits on every call; nothing
+ * is allocated, no fault bit is raised, nothing synchronises.  SLAM2D_E_BADARG, before any HIP call: the level cases of
+ * slam2d_score_poses (a NULL level, no field or frames, p_field < 0, !(step > 0), !(cost_scale > 0), fmax <= 0 or fpitch <
+ * fmax), a NULL d_points, d_out, d_work, d_pose_in or d_pose_out, M < 1 or > SLAM2D_MAX_POINTS, point_stride < 2, set_stride
+ * neither 0 nor >= M * point_stride, N < 1, pose_stride < 3, d_pose_in == d_pose_out, rx, ry or rt < 0, nx, ny or nth < 1,
+ * nth > 65536, a non-finite dx, dy, dth or motion component; SLAM2D_E_TOOLARGE: nx * ny >= 2^31 (search); nx * ny * nth >
+ * SLAM2D_REFINE_MAX_CANDIDATES or more than SLAM2D_REFINE_MAX_BLOCKS blocks -- N * ceil(nth / hc), hc = min(max(1, 2048 / M),
+ * ceil(nth / ceil(1024 / N))) -- (refine); fmax * fpitch >= 2^29.  slam2d_search_points_work makes no HIP call; < 0 means
+ * SLAM2D_E_* (the M, nx, ny, nth cases above).
+ * The set-of-cells score of slam2d_score_poses and slam2d_mcl_step have no point form. */
+#define SLAM2D_MAX_POINTS SLAM2D_MAX_BEAMS        /* 2048: cost stays below 2^44, one heading fits REFINE_TABLE */
+int64_t slam2d_search_points_work(int32_t M, int32_t nx, int32_t ny, int32_t nth);   /* 2 * nth * M words */
+int slam2d_search_points(const Slam2dLevel* level, int32_t p_field,
+                         int32_t nx, int32_t ny, int32_t nth,
+                         double x0, double dx, double y0, double dy, double th0, double dth,
+                         const double* d_points, int32_t point_stride, int32_t M,
+                         uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out, void* stream);
+int slam2d_refine_points(const Slam2dLevel* level, int32_t p_field, int32_t N,
+                         const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                         const double* d_points, int32_t point_stride, int32_t M, int32_t set_stride,
+                         const double motion[3],                /* NULL: none */
+                         int32_t rx, int32_t ry, int32_t rt, double dx, double dy, double dth,
+                         uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out, void* stream);
+
 /* One step of Monte-Carlo localisation in a known map: N pose hypotheses are moved by the odometry increment, weighed against the
  * ONE field of slot p_field with slam2d_score_poses' measurement model, resampled, and left on the device -- no host decision in
  * between (an added symbol: no struct and no existing signature changed, the ABI number stays).  PRECONDITION: that of

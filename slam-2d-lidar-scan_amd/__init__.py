@@ -14,7 +14,9 @@ given poses (Utils/OccupancyGrid.py:main).  ``ScanMatcher.matchMoments`` / ``Par
 mean and covariance of the last match over its whole pose cube (``ParticleEngine.match_moments``).  ``Localiser`` follows a robot
 through a finished map: Monte-Carlo localisation, one device call per scan (``ParticleEngine.mcl_step``); ``Tracker`` follows it with
 one pose and a local search per scan, and ``ScanMatcher.refinePoses`` refines any set of poses that way
-(``ParticleEngine.refine_poses``).  All of them need the HIP library
+(``ParticleEngine.refine_poses``).  ``ScanMatcher.searchPoints`` / ``refinePoints`` and ``Tracker.step_points`` take a set of points
+in the robot's frame instead of one scan -- several scans joined by odometry, two sensors, a driver's own beam angles (the
+``points`` module prepares them).  All of them need the HIP library
 (``libslam2d_hip.so``, built by ``__graft_entry__.build()``) and a GPU; there is no
 CPU fallback.
 """

@@ -62,6 +62,7 @@ REFINE_MAX_CANDIDATES = 1 << 20      # most candidates (nx * ny * nth) of one se
 REFINE_MAX_BLOCKS = 1 << 23          # most blocks of its search launch: seeds x block rows of headings
 REFINE_TABLE = 2048                  # endpoint offsets one block's LDS table holds: at most REFINE_TABLE // beams headings per block row (csrc: REFINE_TABLE)
 REFINE_BLOCKS = 1024                 # ... and fewer, down to one, where fewer than this many seeds would not fill the card (csrc: REFINE_BLOCKS)
+MAX_POINTS = MAX_BEAMS               # most points of a set of slam2d_search_points / slam2d_refine_points (SLAM2D_MAX_POINTS)
 MCL_REPORT = 16                      # 64-bit words of slam2d_mcl_step's report
 MCL_MAX_PARTICLES = 1 << 20
 MCL_MAX_WEIGHT = 0xffffff            # largest integer weight of a particle (24 bits: the weights' sum stays below 2^44)
@@ -197,6 +198,13 @@ SIGNATURES = {
     "slam2d_refine_poses": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_int32,
                                       C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
                                       C.c_uint32, _vp, _vp, _vp]),
+    "slam2d_search_points_work": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "slam2d_search_points": (C.c_int, [C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_int32, C.c_int32,
+                                       C.c_uint32, _vp, _vp, _vp]),
+    "slam2d_refine_points": (C.c_int, [C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                       C.c_uint32, _vp, _vp, _vp]),
     "slam2d_mcl_work": (C.c_int64, [C.c_int32]),
     "slam2d_mcl_step": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_uint64, _vp, C.c_uint32,

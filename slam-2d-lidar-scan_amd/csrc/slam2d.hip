@@ -4641,6 +4641,144 @@ __global__ __launch_bounds__(256) void k_refine_pose(int N, RefineLattice lat, c
     o[2] = moved[(size_t)n * 3 + 2] + (double)refine_off(jt) * lat.dth;
 }
 
+// ---- the two searches for a set of points in the robot's frame (slam2d_search_points, slam2d_refine_points) ----
+// The table is the only place where the searches look at their input: E[heading][k] = R(heading) q of the k-th VALID point q, and
+// offsets_cost, the packed minima and the joins behind it are the scan forms'.  A heading costs ONE cos / sin, whatever M.
+#define POINTS_HEADS 128             // headings whose cos / sin one pass of k_refine_points' table phase holds in LDS
+
+// point k of a set is VALID iff both of its coordinates are finite (include/slam2d.h, step 1)
+__device__ __forceinline__ bool point_valid(const double* __restrict__ pts, const int pstride, const int k) {
+    return __builtin_isfinite(pts[(size_t)k * pstride]) && __builtin_isfinite(pts[(size_t)k * pstride + 1]);
+}
+// R(th) q from c = cos(th), s = sin(th): two rounded products and one rounded add or subtract per component (step 2)
+__device__ __forceinline__ double2 point_offset(const double c, const double s, const double qx, const double qy) {
+    return make_double2(c * qx - s * qy, s * qx + c * qy);
+}
+// The block's share of a compaction in point order: whether this thread's item is kept -> its slot; `total` runs on, the same in
+// every thread.  Ballots for a wave's count, the four waves' counts through LDS; both barriers are the block's.
+__device__ __forceinline__ int block_compact_slot(const bool keep, int* wcount, const int wv, const int lane, int& total) {
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wcount[wv] = __popcll(mask);
+    __syncthreads();
+    int base = total;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int c = wcount[w];
+        if (w < wv) base += c;
+        total += c;
+    }
+    __syncthreads();
+    return base + __popcll(mask & ((1ull << lane) - 1ull));
+}
+
+// First launch of the search: block `it` < nth writes heading it's row E[it][0 .. valid) -- thread 0 evaluates the heading's cos /
+// sin, the only ones of the search, the block compacts the valid points in point order and rotates them -- and every block sets
+// its 256 words of d_out to all ones, the identity of the search launch's atomicMin (the grid covers both: slam2d_search_points).
+__global__ __launch_bounds__(256) void k_points_table(int nth, double th0, double dth, const double* __restrict__ pts, int pstride, int M,
+                                                      double2* __restrict__ E, unsigned long long* __restrict__ out, int positions) {
+    __shared__ double2 cs;
+    __shared__ int wcount[4];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;                           // (positions < 2^31: no wrap)
+    if (i < (unsigned)positions) out[i] = ~0ull;
+    if (blockIdx.x >= (unsigned)nth) return;                                     // (block-uniform)
+    const int it = (int)blockIdx.x;
+    if (tid == 0) {
+        const double th = th0 + (double)it * dth;
+        cs = make_double2(cos(th), sin(th));
+    }
+    __syncthreads();
+    const double c = cs.x, s = cs.y;
+    double2* __restrict__ row = E + (size_t)it * M;
+    int valid = 0;
+    for (int k0 = 0; k0 < M; k0 += 256) {
+        const int k = k0 + tid;
+        const bool keep = k < M && point_valid(pts, pstride, k);
+        const int slot = block_compact_slot(keep, wcount, wv, lane, valid);
+        if (keep) row[slot] = point_offset(c, s, pts[(size_t)k * pstride], pts[(size_t)k * pstride + 1]);
+    }
+}
+
+// Search launch: k_search_lattice with the valid points counted in place of the beams in range (the same at every pose; the lanes
+// of a wave read a point at one address).  Reads frames[p_field], the slot's field, E and the points; no fault bit.
+__global__ __launch_bounds__(256) void k_points_lattice(Slam2dLevel lv, int p_field, int nx, int positions, int nth, int hc, double x0, double dx,
+                                                        double y0, double dy, const double* __restrict__ pts, int pstride, int M,
+                                                        const double2* __restrict__ E, unsigned outside_cost,
+                                                        unsigned long long* __restrict__ out) {
+    const unsigned p = blockIdx.x * 256u + threadIdx.x;                           // (positions < 2^31: no wrap)
+    if (p >= (unsigned)positions) return;
+    const Slam2dFrame fr = lv.frames[p_field];
+    const FieldSize fs = frame_clip(lv, fr);
+    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const int iy = (int)p / nx, ix = (int)p - iy * nx;
+    const double x = x0 + (double)ix * dx, y = y0 + (double)iy * dy;
+    int valid = 0;
+    for (int k = 0; k < M; ++k) valid += point_valid(pts, pstride, k);
+    const int it0 = blockIdx.y * hc, it1 = min(nth, it0 + hc);
+    unsigned long long best = ~0ull;
+    for (int it = it0; it < it1; ++it) {
+        const unsigned long long cost = offsets_cost(E + (size_t)it * M, valid, x, y, fr, lv.step, fs, lv.fpitch, field, outside_cost);
+        best = min(best, (cost << 16) | (unsigned long long)it);
+    }
+    atomicMin(&out[p], best);
+}
+
+// Search launch of the refinement: k_refine_search's block -- blockIdx.x = n * rows + row takes headings [row * hc, row * hc + hc)
+// of seed n, hc * M <= REFINE_TABLE or hc == 1 -- with the first two phases for points:
+//   1. the set's VALID points, compacted in point order into kidx;
+//   2. E[h][k] = R(tm + off(jt0 + h) * dth) q of the block's heading h and the k-th valid point q: the headings' cos / sin first,
+//      one per heading and seed and POINTS_HEADS of them at a time, then the rotations;
+//   3. the candidates, the packed minimum, the join and cost(0) as k_refine_search has them.
+// Reads frames[p_field], the slot's field, the moved seeds and the points; no fault bit.
+__global__ __launch_bounds__(256) void k_refine_points(Slam2dLevel lv, int p_field, int rows, int hc, RefineLattice lat,
+                                                       const double* __restrict__ moved, const double* __restrict__ points, int pstride, int M,
+                                                       int sstride, unsigned outside_cost, unsigned long long* __restrict__ out) {
+    __shared__ double2 E[REFINE_TABLE];
+    __shared__ double2 cs[POINTS_HEADS];
+    __shared__ unsigned short kidx[SLAM2D_MAX_POINTS];
+    __shared__ int wcount[4];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int n = (int)(blockIdx.x / (unsigned)rows), row = (int)(blockIdx.x - (unsigned)n * (unsigned)rows);
+    const int jt0 = row * hc, hn = min(hc, lat.nth - jt0);
+    const Slam2dFrame fr = lv.frames[p_field];
+    const FieldSize fs = frame_clip(lv, fr);
+    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const double xm = moved[(size_t)n * 3], ym = moved[(size_t)n * 3 + 1], tm = moved[(size_t)n * 3 + 2];
+    const double* __restrict__ pts = points + (size_t)n * sstride;
+    int valid = 0;                                                               // (block-uniform)
+    for (int k0 = 0; k0 < M; k0 += 256) {
+        const int k = k0 + tid;
+        const bool keep = k < M && point_valid(pts, pstride, k);
+        const int slot = block_compact_slot(keep, wcount, wv, lane, valid);
+        if (keep) kidx[slot] = (unsigned short)k;
+    }
+    __syncthreads();
+    for (int h0 = 0; h0 < hn; h0 += POINTS_HEADS) {                              // (one pass from 16 points on: hn * valid <= REFINE_TABLE)
+        const int h1 = min(hn, h0 + POINTS_HEADS);
+        if (tid < h1 - h0) {
+            const double th = tm + (double)refine_off(jt0 + h0 + tid) * lat.dth;
+            cs[tid] = make_double2(cos(th), sin(th));
+        }
+        __syncthreads();
+        for (int i = h0 * valid + tid; i < h1 * valid; i += 256) {
+            const int h = i / valid, k = kidx[i - h * valid];
+            E[i] = point_offset(cs[h - h0].x, cs[h - h0].y, pts[(size_t)k * pstride], pts[(size_t)k * pstride + 1]);
+        }
+        __syncthreads();
+    }
+    const int P = lat.nx * lat.ny, f0 = jt0 * P;                                 // (nx * ny * nth <= 2^20)
+    unsigned long long best = ~0ull;
+    for (int c = tid; c < hn * P; c += 256) {
+        const int h = c / P, p = c - h * P, jy = p / lat.nx, jx = p - jy * lat.nx;
+        const double x = xm + (double)refine_off(jx) * lat.dx, y = ym + (double)refine_off(jy) * lat.dy;
+        const unsigned long long cost = offsets_cost(E + h * valid, valid, x, y, fr, lv.step, fs, lv.fpitch, field, outside_cost);
+        if (f0 + c == 0) out[(size_t)n * SLAM2D_REFINE_STRIDE + 1] = cost;
+        best = min(best, (cost << 20) | (unsigned long long)(f0 + c));
+    }
+    best = wave64_min_u64(best);
+    if (lane == 0 && best != ~0ull) atomicMin(&out[(size_t)n * SLAM2D_REFINE_STRIDE], best);
+}
+
 // ---- Monte-Carlo localisation in a known map (slam2d_mcl_step): move, weigh, resample, all in integers and rounded operations ----
 #define MCL_WAVES 4                  // particles (waves) per block of the scoring launch
 #define MCL_UNROLL 2                 // trips of 64 beams its beam loop takes at a time: their gathers are in flight together
@@ -6105,6 +6243,85 @@ int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int3
     k_refine_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion != nullptr, motion ? motion[0] : 0.0, motion ? motion[1] : 0.0,
                                                motion ? motion[2] : 0.0, moved, out);
     k_refine_search<<<(unsigned)(N * rows), 256, 0, s>>>(*lidar, *level, p_field, (int)rows, hc, lat, moved, d_ranges, ranges_stride, outside_cost, out);
+    k_refine_pose<<<cdiv(N, 256), 256, 0, s>>>(N, lat, moved, out, d_pose_out, pose_stride);
+    return launch_status();
+}
+
+// What slam2d_search_points and slam2d_refine_points ask of the level: check_scored_field's level cases (no lidar is read).
+static int check_points_field(const Slam2dLevel* level, int p_field) {
+    if (!level || !level->field || !level->frames || p_field < 0) return SLAM2D_E_BADARG;
+    if (!(level->step > 0.0) || !(level->cost_scale > 0.0)) return SLAM2D_E_BADARG;                  // (the negated forms refuse a NaN)
+    if (level->fmax <= 0 || level->fpitch < level->fmax) return SLAM2D_E_BADARG;
+    if ((long long)level->fmax * level->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;
+    return 0;
+}
+
+// the checks slam2d_search_points and its work size share; *words: the 8-byte words of d_work (the offset table)
+static int check_search_points(int M, int nx, int ny, int nth, long long* words) {
+    if (M < 1 || M > SLAM2D_MAX_POINTS || nx < 1 || ny < 1 || nth < 1 || nth > 65536) return SLAM2D_E_BADARG;
+    if ((long long)nx * ny >= (1ll << 31)) return SLAM2D_E_TOOLARGE;
+    *words = 2ll * nth * M;                                                       // (at most 2^28)
+    if (*words > (1ll << 31)) return SLAM2D_E_TOOLARGE;
+    return 0;
+}
+
+int64_t slam2d_search_points_work(int32_t M, int32_t nx, int32_t ny, int32_t nth) {
+    long long words = 0;
+    const int rc = check_search_points(M, nx, ny, nth, &words);
+    return rc ? rc : words;
+}
+
+int slam2d_search_points(const Slam2dLevel* level, int32_t p_field, int32_t nx, int32_t ny, int32_t nth, double x0, double dx, double y0,
+                         double dy, double th0, double dth, const double* d_points, int32_t point_stride, int32_t M, uint32_t outside_cost,
+                         uint64_t* d_work, uint64_t* d_out, void* stream) {
+    const int frc = check_points_field(level, p_field);
+    if (frc == SLAM2D_E_BADARG) return frc;
+    if (!d_points || !d_out || !d_work || point_stride < 2) return SLAM2D_E_BADARG;
+    if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
+    long long words = 0;
+    const int rc = check_search_points(M, nx, ny, nth, &words);
+    if (rc) return rc;
+    if (frc) return frc;
+    const int positions = nx * ny;
+    const int hc = search_chunk(positions, nth);
+    const long long blocks = ((long long)positions + 255) / 256, rows = cdiv(nth, hc);
+    // (heading chunks exist only below SEARCH_WAVES waves of positions, at most 8192 of them: the launch stays below 2^32 threads)
+    hipStream_t s = (hipStream_t)stream;
+    double2* E = reinterpret_cast<double2*>(d_work);
+    k_points_table<<<(unsigned)(blocks > nth ? blocks : nth), 256, 0, s>>>(nth, th0, dth, d_points, point_stride, M, E, (unsigned long long*)d_out,
+                                                                            positions);
+    k_points_lattice<<<dim3((unsigned)blocks, (unsigned)rows), 256, 0, s>>>(*level, p_field, nx, positions, nth, hc, x0, dx, y0, dy, d_points,
+                                                                           point_stride, M, E, outside_cost, (unsigned long long*)d_out);
+    return launch_status();
+}
+
+int slam2d_refine_points(const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                         const double* d_points, int32_t point_stride, int32_t M, int32_t set_stride, const double motion[3], int32_t rx,
+                         int32_t ry, int32_t rt, double dx, double dy, double dth, uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out,
+                         void* stream) {
+    const int frc = check_points_field(level, p_field);
+    if (frc == SLAM2D_E_BADARG) return frc;
+    if (!d_pose_in || !d_pose_out || !d_points || !d_out || !d_work || d_pose_in == d_pose_out) return SLAM2D_E_BADARG;
+    if (N < 1 || pose_stride < 3 || M < 1 || M > SLAM2D_MAX_POINTS || point_stride < 2 || rx < 0 || ry < 0 || rt < 0) return SLAM2D_E_BADARG;
+    if (set_stride != 0 && (long long)set_stride < (long long)M * point_stride) return SLAM2D_E_BADARG;
+    if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
+    for (int i = 0; motion && i < 3; ++i)
+        if (!__builtin_isfinite(motion[i])) return SLAM2D_E_BADARG;
+    const long long nx = 2ll * rx + 1, ny = 2ll * ry + 1, nth = 2ll * rt + 1;     // (each below 2^32)
+    if (nx > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny * nth > SLAM2D_REFINE_MAX_CANDIDATES)
+        return SLAM2D_E_TOOLARGE;
+    const int hc = refine_chunk(N, (int)nth, M);
+    const long long rows = (nth + hc - 1) / hc;
+    if (N > SLAM2D_REFINE_MAX_BLOCKS || N * rows > SLAM2D_REFINE_MAX_BLOCKS) return SLAM2D_E_TOOLARGE;       // (256 threads each: below 2^32)
+    if (frc) return frc;
+    hipStream_t s = (hipStream_t)stream;
+    const RefineLattice lat{(int)nx, (int)ny, (int)nth, dx, dy, dth};
+    double* moved = reinterpret_cast<double*>(d_work);
+    unsigned long long* out = (unsigned long long*)d_out;
+    k_refine_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion != nullptr, motion ? motion[0] : 0.0, motion ? motion[1] : 0.0,
+                                               motion ? motion[2] : 0.0, moved, out);
+    k_refine_points<<<(unsigned)(N * rows), 256, 0, s>>>(*level, p_field, (int)rows, hc, lat, moved, d_points, point_stride, M, set_stride,
+                                                         outside_cost, out);
     k_refine_pose<<<cdiv(N, 256), 256, 0, s>>>(N, lat, moved, out, d_pose_out, pose_stride);
     return launch_status();
 }

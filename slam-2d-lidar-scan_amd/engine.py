@@ -1372,6 +1372,59 @@ class ParticleEngine:
         return dict(cost=cost, index=index, offsets=offsets, start_cost=w[:, 1].copy(), score=-(cost.astype(np.float64) / cost_scale),
                     moved=index != 0)
 
+    def search_points(self, level, p_field, lattice, d_points, M, outside_cost, point_stride=2):
+        """``search_lattice`` for a set of points in the robot's frame instead of a scan (include/slam2d.h, slam2d_search_points):
+        point k is ``d_points[k * point_stride + 0..1]`` -- x forward, y to the left, metres; a row with a NaN or an infinity is
+        dropped.  The same ``[ny, nx]`` int64 words, cost << 16 | heading, where a valid point that ends outside the field pays
+        ``outside_cost``.  Two launches on the current stream; the scratch is kept and grown; ``search_host`` decodes."""
+        if not 0 <= p_field < level.P:
+            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        lat = Lattice(*lattice)
+        M, point_stride = int(M), int(point_stride)
+        n = int(self.L.slam2d_search_points_work(M, lat.nx, lat.ny, lat.nth))
+        if n < 0:
+            check(n, "slam2d_search_points_work")
+        if point_stride < 2 or d_points.numel() < (M - 1) * point_stride + 2:
+            raise ValueError(f"d_points {tuple(d_points.shape)}: want {M} points, {point_stride} doubles apart")
+        work = getattr(self, "_search_work", None)
+        if work is None or work.numel() < n:
+            work = self._search_work = torch.empty(n, dtype=torch.int64, device=self.device)
+        out = torch.empty((lat.ny, lat.nx), dtype=torch.int64, device=self.device)
+        check(self.L.slam2d_search_points(C.byref(level.c), p_field, lat.nx, lat.ny, lat.nth,
+                                          float(lat.x0), float(lat.dx), float(lat.y0), float(lat.dy), float(lat.th0), float(lat.dth),
+                                          _ptr(d_points), point_stride, M, int(outside_cost), _ptr(work), _ptr(out), _stream()),
+              "slam2d_search_points")
+        return out
+
+    def refine_points(self, level, p_field, d_in, d_out, N, pose_stride, d_points, M, set_stride, radii, steps, outside_cost, motion=None,
+                      d_words=None, point_stride=2):
+        """``refine_poses`` for a set of points in the robot's frame instead of a scan (include/slam2d.h, slam2d_refine_points):
+        ``set_stride`` 0: the one set ``d_points`` (``M`` points, ``point_stride`` doubles apart) for every seed; >= M *
+        point_stride: a set per seed, that many doubles apart.  The same ``[N, 2]`` int64 words and the same winning poses in
+        ``d_out``.  Three launches on the current stream, no synchronisation; ``refine_host`` decodes."""
+        if not 0 <= p_field < level.P:
+            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        n = int(self.L.slam2d_refine_work(N))
+        if n < 0:
+            check(n, "slam2d_refine_work")
+        M, point_stride, set_stride = int(M), int(point_stride), int(set_stride)
+        if d_in.numel() < (N - 1) * pose_stride + 3 or d_out.numel() < (N - 1) * pose_stride + 3:
+            raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {N} poses, {pose_stride} doubles apart")
+        if M < 1 or point_stride < 2 or d_points.numel() < (N - 1) * set_stride + (M - 1) * point_stride + 2:
+            raise ValueError(f"d_points {tuple(d_points.shape)}: want {M} points, {point_stride} doubles apart, sets {set_stride} apart")
+        work = getattr(self, "_refine_work", None)
+        if work is None or work.numel() < n:
+            work = self._refine_work = torch.empty(n, dtype=torch.int64, device=self.device)
+        out = torch.empty((N, _lib.REFINE_STRIDE), dtype=torch.int64, device=self.device) if d_words is None else d_words
+        if out.numel() < N * _lib.REFINE_STRIDE or out.element_size() != 8:
+            raise ValueError(f"d_words wants {N} x {_lib.REFINE_STRIDE} 64-bit words")
+        rx, ry, rt = (int(v) for v in radii)
+        dx, dy, dth = (float(v) for v in steps)
+        check(self.L.slam2d_refine_points(C.byref(level.c), p_field, N, _ptr(d_in), _ptr(d_out), pose_stride, _ptr(d_points), point_stride, M,
+                                          set_stride, None if motion is None else (C.c_double * 3)(*[float(v) for v in motion]),
+                                          rx, ry, rt, dx, dy, dth, int(outside_cost), _ptr(work), _ptr(out), _stream()), "slam2d_refine_points")
+        return out
+
     def mcl_step(self, level, p_field, d_in, d_out, N, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift, d_report,
                  d_ancestor=None):
         """One step of Monte-Carlo localisation (include/slam2d.h, slam2d_mcl_step): the N poses of ``d_in`` moved by ``motion`` =

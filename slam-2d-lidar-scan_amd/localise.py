@@ -304,6 +304,26 @@ class Tracker:
             host = self.d_report.cpu().numpy()
         return self._report(host[:3], host[3:].view(np.uint64).reshape(len(self.stages), _lib.REFINE_STRIDE))
 
+    def step_points(self, points, motion):
+        """``step`` for a set of points in the robot's frame instead of a scan (slam2d_refine_points, include/slam2d.h):
+        ``points`` is ``[M, 2]`` -- x forward, y to the left, metres; rows with a NaN or an infinity are dropped --, M <=
+        ``_lib.MAX_POINTS``, as the ``points`` module prepares them.  The field is the one the constructor built: a point that
+        ends outside it pays ``outside_cost``.  The same stages, the same download, the same ``TrackReport``."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        if pts.ndim != 2 or pts.shape[1] != 2 or not 1 <= len(pts) <= _lib.MAX_POINTS:
+            raise ValueError(f"points of shape {pts.shape}: want (M, 2), 1 <= M <= {_lib.MAX_POINTS}")
+        T = len(self.stages)
+        with pinned_stream():
+            d_pts = torch.from_numpy(pts).to(self.eng.device)
+            d_words = self.d_report[3:].view(torch.int64).view(T, _lib.REFINE_STRIDE)
+            for i, (radii, steps) in enumerate(self.stages):
+                self.eng.refine_points(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], 1, 3, d_pts, len(pts), 0, radii, steps,
+                                       self.outside_cost, motion=motion if i == 0 else None, d_words=d_words[i])
+                self.cur = 1 - self.cur
+            self.d_report[:3].copy_(self.d_pose[self.cur])
+            host = self.d_report.cpu().numpy()
+        return self._report(host[:3], host[3:].view(np.uint64).reshape(T, _lib.REFINE_STRIDE))
+
     def run(self, readings):
         """A log, as ``Localiser.run`` takes it: the motion of scan i is the step from raw odometry pose i - 1 to i in the frame of
         pose i - 1 (nothing for the first scan).  Every scan is enqueued without a synchronisation; ONE download of the [S, 3]

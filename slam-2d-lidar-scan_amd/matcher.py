@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from .engine import MATCH_DOUBLES, _MATCH_DTYPE, Lattice, ParticleEngine, SearchLevel, encode_cost, likelihood_table, pinned_stream
+from .points import reach as points_reach
 
 _level_cache = {}
 
@@ -570,6 +571,99 @@ class ScanMatcher:
                 eng.flags.zero_()
                 if bits & _lib.FATAL_FLAGS:
                     raise _lib.Slam2dError(f"refinePoses: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
+            self.last_flags = bits
+            self.last_cover = dict(level=lv, window=(cx, cy, half), stages=stages)
+        w = host[3 * N:-1].view(np.uint64).reshape(len(stages), N, _lib.REFINE_STRIDE)
+        dec = [ParticleEngine.refine_host(w[i], radii, steps, lv.cost_scale) for i, (radii, steps) in enumerate(stages)]
+        return dict(poses=host[:3 * N].reshape(N, 3).copy(), cost=dec[-1]["cost"], score=dec[-1]["score"], start_cost=dec[0]["start_cost"],
+                    offsets=np.stack([d["offsets"] for d in dec], axis=1))
+
+    def points_level(self, level, half, points, likelihood=None, shared=True):
+        """The covering level of ``searchPoints`` / ``refinePoints``: that of ``searchPoses`` for the same window -- the same
+        cached level -- while no valid point lies further from the robot than lidarMaxRange; else the level of a window wider by
+        the excess, so that the points of a pose in the window still end in the field, where slam2d_field_build accepts that
+        level (``field_build_limits``).  Where it does not, the far points simply pay ``outside_cost``."""
+        extra = max(0.0, points_reach(points) - self.og.lidarMaxRange)
+        if extra > 0.0:
+            try:
+                return self.covering_level(level, half + extra, shared=shared, likelihood=likelihood)
+            except ValueError:
+                pass
+        return self.covering_level(level, half, shared=shared, likelihood=likelihood)
+
+    def searchPoints(self, points, window, step=None, headings=120, level="fine", top=5, separation=None, outside_cost=None,
+                     likelihood=None):
+        """``searchPoses`` for a set of points in the robot's frame instead of one scan (include/slam2d.h, slam2d_search_points):
+        ``points`` is ``[M, 2]`` -- x forward, y to the left, metres; rows with a NaN or an infinity are dropped --, M <=
+        ``_lib.MAX_POINTS``: several scans joined by odometry (``points.merge_scans``), two sensors, a sensor off the robot's
+        origin, a driver's own beam angles (``points.polar_points``).  The same lattice, cost, peaks and return value; the
+        field is ``points_level``'s.  ``self.last_cover`` keeps the level, its window and the ``Lattice``."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        if pts.ndim != 2 or pts.shape[1] != 2 or not 1 <= len(pts) <= _lib.MAX_POINTS:
+            raise ValueError(f"points of shape {pts.shape}: want (M, 2), 1 <= M <= {_lib.MAX_POINTS}")
+        cx, cy, half = covering_window(None, window)
+        lv = self.points_level(level, half, pts, likelihood)
+        lat = window_lattice((cx, cy, half), lv.step if step is None else step, headings)
+        sep = 10 if separation is None else int(round(float(separation) / lat.dx))
+        if outside_cost is None:
+            outside_cost = self.outside_cost_of(lv)
+        with _Exclusive(lv), pinned_stream():
+            og = self.og
+            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = og.engine()
+            self.build_cover(eng, lv, cx, cy)
+            words = eng.search_points(lv, 0, lat, eng.to_device(pts), len(pts), outside_cost)
+            # one download: the image and the build's fault word
+            host = torch.cat([words.reshape(-1), eng.flags[:1].to(torch.int64)]).cpu().numpy()
+            bits = int(host[-1]) & 0xffffffff
+            if bits:
+                eng.flags.zero_()
+                if bits & _lib.FATAL_FLAGS:
+                    raise _lib.Slam2dError(f"searchPoints: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
+            self.last_flags = bits
+            self.last_cover = dict(level=lv, window=(cx, cy, half), lattice=lat)
+            res = eng.search_host(host[:-1], lat, lv.cost_scale)
+        res["peaks"] = [Peak(float(res["xs"][ix]), float(res["ys"][iy]), float(res["thetas"][it]), float(res["score"][iy, ix]),
+                             int(res["cost"][iy, ix])) for iy, ix, it in lattice_peaks(res["cost"], res["heading"], top, sep)]
+        return res
+
+    def refinePoints(self, poses, points, stages=None, level="fine", window=None, likelihood=None, outside_cost=None):
+        """``refinePoses`` for a set of points in the robot's frame instead of a scan (include/slam2d.h, slam2d_refine_points):
+        ``points`` is ``[M, 2]``, one set for every seed, or ``[N, M, 2]``, a set per seed (rows with a NaN or an infinity are
+        dropped, so sets of different sizes are padded with NaN rows).  The same stages, frame planning and return value; the
+        field is ``points_level``'s."""
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+        N = len(poses)
+        if N == 0:
+            raise ValueError("no poses")
+        if pts.ndim not in (2, 3) or pts.shape[-1] != 2 or not 1 <= pts.shape[-2] <= _lib.MAX_POINTS or (pts.ndim == 3 and len(pts) != N):
+            raise ValueError(f"points of shape {pts.shape}: want (M, 2) or ({N}, M, 2), 1 <= M <= {_lib.MAX_POINTS}")
+        M = pts.shape[-2]
+        cx, cy, half = covering_window(poses, window)
+        lv = self.points_level(level, half, pts, likelihood)
+        stages = check_stages(stages, lv.step)
+        if outside_cost is None:
+            outside_cost = self.outside_cost_of(lv)
+        with _Exclusive(lv), pinned_stream():
+            og = self.og
+            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = og.engine()
+            self.build_cover(eng, lv, cx, cy)
+            d_pose = [eng.to_device(poses), torch.empty((N, 3), dtype=torch.float64, device=eng.device)]
+            d_pts = eng.to_device(pts)
+            words = torch.empty((len(stages), N, _lib.REFINE_STRIDE), dtype=torch.int64, device=eng.device)
+            for i, (radii, steps) in enumerate(stages):
+                eng.refine_points(lv, 0, d_pose[i & 1], d_pose[1 - (i & 1)], N, 3, d_pts, M, 0 if pts.ndim == 2 else 2 * M, radii, steps,
+                                  outside_cost, d_words=words[i])
+            # one download: the poses, the stages' words and the build's fault word
+            host = torch.cat([d_pose[len(stages) & 1].reshape(-1), words.reshape(-1).view(torch.float64),
+                              eng.flags[:1].to(torch.float64)]).cpu().numpy()
+            bits = int(host[-1])
+            if bits:
+                eng.flags.zero_()
+                if bits & _lib.FATAL_FLAGS:
+                    raise _lib.Slam2dError(f"refinePoints: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
             self.last_flags = bits
             self.last_cover = dict(level=lv, window=(cx, cy, half), stages=stages)
         w = host[3 * N:-1].view(np.uint64).reshape(len(stages), N, _lib.REFINE_STRIDE)
