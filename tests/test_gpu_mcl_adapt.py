@@ -95,13 +95,16 @@ def c_bins(bins):
     return _lib.Slam2dMclBins(x0=b.x0, y0=b.y0, cell=b.cell, turn=b.turn, nx=b.nx, ny=b.ny, nth=b.nth)
 
 
-def launch(scene, poses, n_in, motion, amp, seed, scan, ranges, bins=BINS, ntab=TAB3, outside=None, lut=None, shift=None, ancestor=True):
+def launch(scene, poses, n_in, motion, amp, seed, scan, ranges, bins=BINS, ntab=TAB3, outside=None, lut=None, shift=None, ancestor=True,
+           level=None, p=0):
     """slam2d_mcl_step_adaptive at the C ABI with buffers of its own, all of them poisoned with 0xff bytes (the output count
-    word too: another word than the input's).  ``poses``: [n_cap, stride], ``n_in``: the input count word.  Returns dict of
+    word too: another word than the input's).  ``poses``: [n_cap, stride], ``n_in``: the input count word; ``level``, ``p``: the
+    Slam2dLevel and its field slot (default: slot 0 of the scene's level).  Returns dict of
     ``out`` [n_cap, stride] as uint64 words, ``ancestors`` ([n_cap]; None without), ``report`` (uint64 [24]), ``n_out``."""
     import torch
     engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
-    eng, lv = scene["eng"], scene["lv"]
+    eng = scene["eng"]
+    lvc = scene["lv"].c if level is None else level
     poses = np.ascontiguousarray(poses, dtype=np.float64)
     n_cap, stride = poses.shape
     lid = _lib.Slam2dLidar.from_buffer_copy(eng.lidar_c)
@@ -118,7 +121,7 @@ def launch(scene, poses, n_in, motion, amp, seed, scan, ranges, bins=BINS, ntab=
     full = lambda shape, dt: torch.full(shape, -1, dtype=dt, device=eng.device)
     work, rep, out = full((n,), torch.int64), full((_lib.MCL_ADAPT_REPORT,), torch.int64), full((n_cap, stride), torch.int64)
     anc, d_n_out = full((n_cap,), torch.int32) if ancestor else None, full((1,), torch.int32)
-    _lib.check(eng.L.slam2d_mcl_step_adaptive(ctypes.byref(lid), ctypes.byref(lv.c), 0, n_cap, d_n_in.data_ptr(), d_n_out.data_ptr(),
+    _lib.check(eng.L.slam2d_mcl_step_adaptive(ctypes.byref(lid), ctypes.byref(lvc), p, n_cap, d_n_in.data_ptr(), d_n_out.data_ptr(),
                                               d_in.data_ptr(), out.data_ptr(), stride, (ctypes.c_double * 3)(*motion), (ctypes.c_double * 3)(*amp),
                                               seed, scan, d_rng.data_ptr(), scene["free"] if outside is None else outside, d_lut.data_ptr(),
                                               len(lut), scene["shift"] if shift is None else shift, ctypes.byref(cb), d_ntab.data_ptr(), len(ntab),

@@ -117,10 +117,12 @@ def rows_of(pts, point_stride):
     return rows
 
 
-def launch_search(ctx, p, lat, pts, outside=OUTSIDE, point_stride=2):
+def launch_search(ctx, p, lat, pts, outside=OUTSIDE, point_stride=2, level=None):
+    """The image as uint64 [ny, nx]; ``level``: the Slam2dLevel whose slot p is read (default: the context's level)."""
     import torch
     engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
-    eng, lv = ctx["eng"], ctx["lv"]
+    eng = ctx["eng"]
+    lvc = ctx["lv"].c if level is None else level
     nx, ny, nth = lat[:3]
     M = len(pts)
     n = eng.L.slam2d_search_points_work(M, nx, ny, nth)
@@ -128,17 +130,18 @@ def launch_search(ctx, p, lat, pts, outside=OUTSIDE, point_stride=2):
     d_pts = eng.to_device(rows_of(pts, point_stride))
     work = torch.full((n,), -1, dtype=torch.int64, device=eng.device)         # (0xff bytes: NaNs as doubles)
     out = torch.full((ny, nx), -1, dtype=torch.int64, device=eng.device)
-    _lib.check(eng.L.slam2d_search_points(ctypes.byref(lv.c), p, nx, ny, nth, *[float(v) for v in lat[3:]], d_pts.data_ptr(), point_stride, M,
+    _lib.check(eng.L.slam2d_search_points(ctypes.byref(lvc), p, nx, ny, nth, *[float(v) for v in lat[3:]], d_pts.data_ptr(), point_stride, M,
                                           int(outside), work.data_ptr(), out.data_ptr(), engine._stream()), "slam2d_search_points")
     return out.cpu().numpy().view(np.uint64)
 
 
-def launch_refine(ctx, p, seeds, radii, steps, pts, outside=OUTSIDE, motion=None, pose_stride=3, point_stride=2, pad=0):
+def launch_refine(ctx, p, seeds, radii, steps, pts, outside=OUTSIDE, motion=None, pose_stride=3, point_stride=2, pad=0, level=None):
     """(words uint64 [N, 2], the output pose buffer float64 [N, pose_stride]); ``pts`` [M, 2]: set_stride 0; [N, M, 2]: a set per
-    seed, ``pad`` doubles between the sets."""
+    seed, ``pad`` doubles between the sets; ``level``: the Slam2dLevel whose slot p is read (default: the context's level)."""
     import torch
     engine = importlib.import_module("slam-2d-lidar-scan_amd.engine")
-    eng, lv = ctx["eng"], ctx["lv"]
+    eng = ctx["eng"]
+    lvc = ctx["lv"].c if level is None else level
     seeds = np.asarray(seeds, dtype=np.float64).reshape(-1, 3)
     pts = np.asarray(pts, dtype=np.float64)
     N, M = len(seeds), pts.shape[-2]
@@ -152,7 +155,7 @@ def launch_refine(ctx, p, seeds, radii, steps, pts, outside=OUTSIDE, motion=None
     d_in, d_pts = eng.to_device(poses), eng.to_device(rows)
     full = lambda n: torch.full((n,), -1, dtype=torch.int64, device=eng.device)
     work, out, d_out = full(eng.L.slam2d_refine_work(N)), full(2 * N), full(N * pose_stride)
-    _lib.check(eng.L.slam2d_refine_points(ctypes.byref(lv.c), p, N, d_in.data_ptr(), d_out.data_ptr(), pose_stride, d_pts.data_ptr(), point_stride,
+    _lib.check(eng.L.slam2d_refine_points(ctypes.byref(lvc), p, N, d_in.data_ptr(), d_out.data_ptr(), pose_stride, d_pts.data_ptr(), point_stride,
                                           M, set_stride, None if motion is None else (ctypes.c_double * 3)(*motion), *[int(r) for r in radii],
                                           *[float(s) for s in steps], int(outside), work.data_ptr(), out.data_ptr(), engine._stream()),
                "slam2d_refine_points")
