@@ -798,6 +798,53 @@ __global__ __launch_bounds__(256) void k_refresh_bits(const Slam2dMap* __restric
 // Tiles are 16x16: walls are thin, so small tiles keep the blurred area close to the area that
 // actually differs from the constant (work ~ (T + 2r + 1) * (2 + 2r/T) per unit wall length has its
 // minimum near T = 2r).
+//
+// The tile body is one wave's work (k_blur_clamp's blocks are one wave; k_blur_check_redo's redo runs in its first wave alone):
+// a vote over the tile is a ballot, not a block reduction.
+__device__ __forceinline__ int blur_wave_any(const int pred) { return __ballot(pred != 0) != 0ull; }
+// base + a 32-bit BYTE offset: the address is a uniform base and one vector register (offsets into one particle's image,
+// field or block minima stay below 2^31: fmax * fpitch < 2^29 is checked at every entry point)
+template <typename T>
+__device__ __forceinline__ T* at_bytes(T* base, const uint32_t byte_offset) {
+    using B = std::conditional_t<std::is_const_v<T>, const char, char>;
+    return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + byte_offset);
+}
+// 0x01 in every byte of v that differs from the stamp byte (exact per byte), 0x00 where it equals it
+__device__ __forceinline__ uint32_t bytes_differ(const uint32_t v, const uint8_t stamp) {
+    const uint32_t t = v ^ (0x01010101u * stamp);
+    return ((((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) >> 7) & 0x01010101u;
+}
+// reflect_index for an index within one length of the range (every halo of a frame that is not smaller than the radius): two
+// selects; anything further out takes the general form with its division
+__device__ __forceinline__ int reflect_near(const int i, const int n) {
+    int m = i < 0 ? -1 - i : i;
+    m = m >= n ? 2 * n - 1 - m : m;
+    if (__builtin_expect((unsigned)m >= (unsigned)n, 0)) m = reflect_index(i, n);
+    return m;
+}
+// Slice i of a PER_ROW-wide array of TOTAL elements dealt over the wave, 64 at a time: the lane's (row, column).  Where the
+// wave covers whole rows the column is the lane's own in every slice and the rows are a constant apart (addresses differ by
+// immediates); a last, partial slice is clamped into the array (its lanes beyond the end are masked by blur_slice_valid).
+template <int PER_ROW, int TOTAL>
+__device__ __forceinline__ void blur_slice(const int tid, const int i, int& row, int& col) {
+    if constexpr (BLUR_THREADS % PER_ROW == 0) {
+        row = tid / PER_ROW + i * (BLUR_THREADS / PER_ROW);
+        col = tid % PER_ROW;
+        if ((i + 1) * BLUR_THREADS > TOTAL) row = min(row, TOTAL / PER_ROW - 1);
+    } else {
+        int idx = tid + i * BLUR_THREADS;
+        if ((i + 1) * BLUR_THREADS > TOTAL) idx = min(idx, TOTAL - 1);
+        row = idx / PER_ROW;
+        col = idx - row * PER_ROW;
+    }
+}
+template <int TOTAL>
+__device__ __forceinline__ bool blur_slice_valid(const int tid, const int i) {
+    return (i + 1) * BLUR_THREADS <= TOTAL || tid + i * BLUR_THREADS < TOTAL;
+}
+// The blur weights are uniform and constant for the launch: read through the constant address space they are scalar loads and
+// the taps take them from scalar registers.
+typedef const double __attribute__((address_space(4))) * BlurWeights;
 template <int RAD>
 struct BlurLds {
     static constexpr int EXT = RAD > 0 ? BLUR_TILE + 2 * RAD : BLUR_EXT;
@@ -833,7 +880,7 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
             const int yy = 2 * tby - k + tid / e, xx = 2 * tbx - k + tid % e;
             if (yy >= 0 && yy < nsy && xx >= 0 && xx < nsx) any = tiles[yy * flag_pitch(lv) + xx] == stamp;
         }
-        any = __syncthreads_or(any);
+        any = blur_wave_any(any);
     }
     if (any) {
         // word loads when the halo is interior and 4-byte aligned (r % 4 == 0), bytes + reflect otherwise
@@ -843,25 +890,29 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
         // HBM latency instead of one per 64-lane slice)
         if ((r & 3) == 0 && interior) {
             const int wpr = ext >> 2;
-            constexpr int NW = RAD > 0 ? ((BLUR_TILE + 2 * RAD) * ((BLUR_TILE + 2 * RAD) / 4) + BLUR_THREADS - 1) / BLUR_THREADS : 1;
             if constexpr (RAD > 0) {
+                // the address is the particle's image (uniform) plus a 32-bit byte offset (fmax * fpitch < 2^29)
+                constexpr int WPR = (BLUR_TILE + 2 * RAD) / 4, TOTAL = (BLUR_TILE + 2 * RAD) * WPR;
+                constexpr int NW = (TOTAL + BLUR_THREADS - 1) / BLUR_THREADS;
                 uint32_t v[NW];
 #pragma unroll
                 for (int i = 0; i < NW; ++i) {
-                    const int idx = min(tid + i * BLUR_THREADS, ext * wpr - 1);
-                    const int ly = idx / wpr, lw = idx - ly * wpr;
-                    v[i] = *reinterpret_cast<const uint32_t*>(occ + (size_t)(ty0 - r + ly) * lv.fpitch + (tx0 - r) + 4 * lw);
+                    int ly, lw;
+                    blur_slice<WPR, TOTAL>(tid, i, ly, lw);
+                    v[i] = *at_bytes(reinterpret_cast<const uint32_t*>(occ), (uint32_t)((ty0 - RAD + ly) * lv.fpitch + (tx0 - RAD) + 4 * lw));
                 }
+                uint32_t all_free = 0x01010101u;
 #pragma unroll
                 for (int i = 0; i < NW; ++i) {
-                    const int idx = tid + i * BLUR_THREADS;
-                    if (idx < ext * wpr) {
-                        const int ly = idx / wpr, lw = idx - ly * wpr;
-                        const uint32_t e = bytes_equal(v[i], stamp);
-                        *reinterpret_cast<uint32_t*>(&sm.occ[ly][4 * lw]) = e ^ 0x01010101u;                 // (RAD > 0: the LDS image holds 1 = free)
-                        exact |= (e != 0u);
+                    if (blur_slice_valid<TOTAL>(tid, i)) {
+                        int ly, lw;
+                        blur_slice<WPR, TOTAL>(tid, i, ly, lw);
+                        const uint32_t f = bytes_differ(v[i], stamp);                                        // (RAD > 0: the LDS image holds 1 = free)
+                        *reinterpret_cast<uint32_t*>(&sm.occ[ly][4 * lw]) = f;
+                        all_free &= f;
                     }
                 }
+                exact = all_free != 0x01010101u;                                                             // one test for the lane's words
             } else {
                 for (int idx = tid; idx < ext * wpr; idx += BLUR_THREADS) {
                     const int ly = idx / wpr, lw = idx - ly * wpr;
@@ -876,16 +927,16 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
             uint8_t v[NB];
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
-                const int idx = min(tid + i * BLUR_THREADS, EXT_C * EXT_C - 1);
-                const int ly = idx / EXT_C, lx = idx - ly * EXT_C;
-                const int gy = reflect_index(ty0 - r + ly, fh), gx = reflect_index(tx0 - r + lx, fw);
-                v[i] = occ[(size_t)gy * lv.fpitch + gx];
+                int ly, lx;
+                blur_slice<EXT_C, EXT_C * EXT_C>(tid, i, ly, lx);
+                const int gy = reflect_near(ty0 - r + ly, fh), gx = reflect_near(tx0 - r + lx, fw);
+                v[i] = *at_bytes(occ, (uint32_t)(gy * lv.fpitch + gx));
             }
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
-                const int idx = tid + i * BLUR_THREADS;
-                if (idx < EXT_C * EXT_C) {
-                    const int ly = idx / EXT_C, lx = idx - ly * EXT_C;
+                if (blur_slice_valid<EXT_C * EXT_C>(tid, i)) {
+                    int ly, lx;
+                    blur_slice<EXT_C, EXT_C * EXT_C>(tid, i, ly, lx);
                     const uint8_t o = v[i] == stamp;
                     sm.occ[ly][lx] = o ^ 1;
                     exact |= o;
@@ -900,7 +951,8 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
                 exact |= o;
             }
         }
-        any = __syncthreads_or(exact);
+        __syncthreads();                               // the image is in LDS
+        any = blur_wave_any(exact);
     }
     DBG_CLOCK(51, dbg);
     const double L = lv.log_miss;
@@ -908,6 +960,7 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
     const double thr = 0.5 * fmin_used;                                            // :44
     uint32_t* field = lv.field + (size_t)p * lv.fmax * lv.fpitch;
     const double* __restrict__ w = lv.blur_w;
+    const BlurWeights wc = (BlurWeights)(uintptr_t)lv.blur_w;                      // (RAD > 0)
     if (!any) {
         const double v = lv.floor_value;
         if (mode == 0 && minmax && tid == 0) {
@@ -939,16 +992,18 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
                 // 2 (L w) EXACTLY: with f = 0 / 1 and lw = L * w the tap is fma(f_a + f_b, lw, acc) -- the product inside is exact,
                 // the one rounding is the sum's, as in SciPy's acc + (a + b) * w -- two operations instead of three.  (The centre term
                 // is selected, not multiplied: 0.0 * lw would be -0.0.)
+                // The centre term is fma(f, lw, +0.0): lw + 0.0 = lw for a free cell, (-0.0) + (+0.0) = +0.0 for an occupied one -- the
+                // value a select gives, in one operation (0.0 * lw alone would be -0.0).
+                // One conversion per value (1 = free -> 1.0), both words of the double at once; the kernel's register bound (four
+                // waves per SIMD, k_blur_clamp) keeps the scheduler from holding all of them at once with everything else.
                 double f[8 + 2 * RAD], lw[RAD + 1];
 #pragma unroll
-                for (int k = 0; k < 8 + 2 * RAD; ++k) f[k] = __hiloint2double(sm.occ[g * 8 + k][lx] ? 0x3FF00000 : 0, 0);     // 1 = free -> 1.0 (a
-                    // v_cvt_f64_u32 here costs the kernel 17 VGPRs and a third of its waves; a multiply by 0x3FF00000 is a quarter-rate
-                    // v_mul_lo_u32 per value)
+                for (int k = 0; k < 8 + 2 * RAD; ++k) f[k] = (double)(uint32_t)sm.occ[g * 8 + k][lx];
 #pragma unroll
-                for (int j = 0; j <= RAD; ++j) lw[j] = L * w[j];
+                for (int j = 0; j <= RAD; ++j) lw[j] = L * wc[j];
 #pragma unroll
                 for (int o = 0; o < 8; ++o) {
-                    double acc = f[o + RAD] != 0.0 ? lw[RAD] : 0.0;
+                    double acc = __builtin_fma(f[o + RAD], lw[RAD], 0.0);
 #pragma unroll
                     for (int j = -RAD; j < 0; ++j) acc = __builtin_fma(f[o + RAD + j] + f[o + RAD - j], lw[RAD + j], acc);
                     sm.mid[g * 8 + o][lx] = acc;
@@ -962,28 +1017,50 @@ __device__ __forceinline__ void blur_tile(const Slam2dLevel& lv, BlurLds<RAD>& s
             double mrow[4 + 2 * RAD];
 #pragma unroll
             for (int k = 0; k < 4 + 2 * RAD; ++k) mrow[k] = sm.mid[y][x0 + k];
-            uint32_t cmin = 0xffffffffu;                   // of the lane's 4 stored costs: one row of an aligned 4x4 block
+            // The four values and their costs are computed for every lane (the LDS rows hold reflected values beyond the frame); the
+            // frame decides only what is stored and what enters the minima: ONE test per lane where its quad lies inside the frame
+            // (a 16-byte store, as fill_tile's), the per-cell tests for a frame's last columns.
+            double acc[4];
+            uint32_t cst[4];
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
-                double acc = mrow[o + RAD] * w[RAD];
+                double a = mrow[o + RAD] * wc[RAD];
 #pragma unroll
-                for (int j = -RAD; j < 0; ++j) acc = acc + (mrow[o + RAD + j] + mrow[o + RAD - j]) * w[RAD + j];
-                const int gy = ty0 + y, gx = tx0 + x0 + o;
-                if (gy < fh && gx < fw) {
-                    lmin = fmin(lmin, acc);
-                    lmax = fmax(lmax, acc);                // (clamped after the loop: the clamp is monotone)
-                    const uint32_t cst = acc > thr ? 0u : (uint32_t)rint(-acc * lv.cost_scale);
-                    field[(size_t)gy * lv.fpitch + gx] = cst;
-                    cmin = min(cmin, cst);
-                }
+                for (int j = -RAD; j < 0; ++j) a = a + (mrow[o + RAD + j] + mrow[o + RAD - j]) * wc[RAD + j];
+                acc[o] = a;
+                cst[o] = a > thr ? 0u : (uint32_t)rint(-a * lv.cost_scale);
             }
-            if (lmax > thr) lmax = 0.0;
+            const int gy = ty0 + y, gx = tx0 + x0;
+            const bool row_in = gy < fh;
+            const uint32_t cell = (uint32_t)(gy * lv.fpitch + gx);
+            uint32_t cmin = 0xffffffffu;                   // of the lane's 4 stored costs: one row of an aligned 4x4 block
+            if (row_in && gx + 3 < fw) {
+                *reinterpret_cast<uint4*>(at_bytes(field, 4u * cell)) = make_uint4(cst[0], cst[1], cst[2], cst[3]);
+                cmin = min(min(cst[0], cst[1]), min(cst[2], cst[3]));
+            } else if (row_in) {
+#pragma unroll
+                for (int o = 0; o < 4; ++o)
+                    if (gx + o < fw) {
+                        *at_bytes(field, 4u * (cell + o)) = cst[o];
+                        cmin = min(cmin, cst[o]);
+                    }
+            }
+            if (mode == 0 && minmax) {                     // (uniform: the minima of the values are read by the minimum check alone)
+#pragma unroll
+                for (int o = 0; o < 4; ++o)
+                    if (row_in && gx + o < fw) {
+                        lmin = fmin(lmin, acc[o]);
+                        lmax = fmax(lmax, acc[o]);         // (clamped after the loop: the clamp is monotone)
+                    }
+                if (lmax > thr) lmax = 0.0;
+            }
             if (lv.bnb) {                                  // rows y, y^1, y^2, y^3 of the block sit in lanes tid ^ 4, ^ 8
                 cmin = min(cmin, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)cmin, 0x124, 0xF, 0xF, false));   // row_ror:4
                 cmin = min(cmin, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)cmin, 0x128, 0xF, 0xF, false));   // row_ror:8
                 if ((y & 3) == 0) {
                     const int gp = lv.tmax << 2;
-                    lv.gmin[((size_t)p * gp + (ty0 >> 2) + (y >> 2)) * gp + (tx0 >> 2) + (tid & 3)] = cmin;
+                    uint32_t* gmin = lv.gmin + (size_t)p * gp * gp;
+                    *at_bytes(gmin, 4u * (uint32_t)(((ty0 >> 2) + (y >> 2)) * gp + (tx0 >> 2) + (tid & 3))) = cmin;
                 }
             }
         }
@@ -1223,7 +1300,7 @@ __device__ __forceinline__ void blur_check_tail(const Slam2dLevel& lv, BlurLds<R
     for (int t = 0; t < nty * ntx; ++t) blur_tile<RAD>(lv, sm, p, fr, t / ntx, t % ntx, 1, true);
 }
 template <int RAD>
-__global__ __launch_bounds__(BLUR_THREADS, BLUR_MIN_WAVES) void k_blur_clamp(Slam2dLevel lv, int P, int bpp, uint32_t* flags, int tail) {
+__global__ __launch_bounds__(BLUR_THREADS, RAD == 8 ? 4 : BLUR_MIN_WAVES) void k_blur_clamp(Slam2dLevel lv, int P, int bpp, uint32_t* flags, int tail) {
     __shared__ BlurLds<RAD> sm;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int p = (slot / bpp) * 8 + xcd, first = slot % bpp;
