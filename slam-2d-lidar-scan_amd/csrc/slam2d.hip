@@ -4441,6 +4441,13 @@ __device__ __forceinline__ bool score_cell(const double px, const double py, con
     return cx >= 0 && cx < fw && cy >= 0 && cy < fh;
 }
 
+// What every kernel of this layer reads of a level's slot p_field: its frame, the frame's clipped size, its field image
+struct SlotField { Slam2dFrame fr; FieldSize fs; const uint32_t* field; };
+__device__ __forceinline__ SlotField slot_field(const Slam2dLevel& lv, const int p_field) {
+    const Slam2dFrame fr = lv.frames[p_field];
+    return SlotField{fr, frame_clip(lv, fr), lv.field + (size_t)p_field * lv.fmax * lv.fpitch};
+}
+
 // One wave per pose, blockDim.x / 64 poses per block, beams interleaved over the lanes (beam = 64 i + lane: a wave's range loads
 // are contiguous).  out[n * SLAM2D_SCORE_STRIDE + 0..7] as include/slam2d.h lists them.  The hash set holds keys only: the lane
 // whose atomicCAS finds a slot empty owns the cell and adds its cost to sum_u, every inside beam adds to sum_b.  The wave's
@@ -4458,9 +4465,7 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar li
     for (int i = lane; i < hsize; i += 64) hkey[i] = INT_MAX;                    // (no key: cx < 2^15 leaves the low half below 0xffff)
     __syncthreads();
     if (n >= N) return;                                                          // (wave-uniform)
-    const Slam2dFrame fr = lv.frames[p_field];
-    const FieldSize fs = frame_clip(lv, fr);
-    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const SlotField sf = slot_field(lv, p_field);
     const double x = pose[(size_t)n * pstride], y = pose[(size_t)n * pstride + 1], th = pose[(size_t)n * pstride + 2];
     const double* __restrict__ rg = ranges + (size_t)n * rstride;
     const int B = lid.beams;
@@ -4478,10 +4483,10 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar li
             const double a = fan.angle(b);
             const double px = x + cos(a) * r, py = y + sin(a) * r;               // :87-88
             int cx, cy;
-            if (score_cell(px, py, fr.xlo, fr.ylo, lv.step, fs.fw, fs.fh, cx, cy)) {
+            if (score_cell(px, py, sf.fr.xlo, sf.fr.ylo, lv.step, sf.fs.fw, sf.fs.fh, cx, cy)) {
                 inside = true;
                 key = (cy << 16) | cx;
-                cost = field[(size_t)cy * lv.fpitch + cx];
+                cost = sf.field[(size_t)cy * lv.fpitch + cx];
             }
         }
         bool owns = false;
@@ -4567,33 +4572,40 @@ __device__ __forceinline__ unsigned long long offsets_cost(const double2* __rest
     return sum_b + (unsigned long long)(n_rng - n_in) * outside_cost;
 }
 
-// Search launch: one thread per position (flat index iy * nx + ix: neighbouring lanes read neighbouring field cells), blockIdx.y
-// takes headings [y * hc, y * hc + hc).  The loops over headings and beams are the same for every lane and E is read at a
-// wave-uniform address.  Each lane takes a heading's cost from offsets_cost, folds
-// cost << 16 | it into a 64-bit minimum per heading and joins the block rows with one integer atomicMin on d_out, which
-// k_search_table set to all ones in front of this launch on the same stream: a minimum of integers, whatever the order.  Reads
-// frames[p_field], the slot's field, E and the ranges; no fault bit.
+// Position p of the lattice (flat index iy * nx + ix), headings [it0, it1) of this block row: both search launches' thread.  E's
+// rows lie `pitch` entries apart and hold `count` offsets each.  The loops over headings and offsets are the same for every lane
+// and E is read at a wave-uniform address.  The lane takes a heading's cost from offsets_cost, folds cost << 16 | it into a
+// 64-bit minimum and joins the block rows with one integer atomicMin on d_out, which the table launch set to all ones in front of
+// this launch on the same stream: a minimum of integers, whatever the order.
+__device__ __forceinline__ void lattice_position(const unsigned p, const int nx, const int nth, const int hc, const double x0, const double dx,
+                                                 const double y0, const double dy, const double2* __restrict__ E, const int pitch, const int count,
+                                                 const Slam2dLevel& lv, const SlotField& sf, const unsigned outside_cost,
+                                                 unsigned long long* __restrict__ out) {
+    const int iy = (int)p / nx, ix = (int)p - iy * nx;
+    const double x = x0 + (double)ix * dx, y = y0 + (double)iy * dy;
+    const int it0 = blockIdx.y * hc, it1 = min(nth, it0 + hc);
+    unsigned long long best = ~0ull;
+    for (int it = it0; it < it1; ++it) {
+        const unsigned long long cost = offsets_cost(E + (size_t)it * pitch, count, x, y, sf.fr, lv.step, sf.fs, lv.fpitch, sf.field, outside_cost);
+        best = min(best, (cost << 16) | (unsigned long long)it);
+    }
+    atomicMin(&out[p], best);
+}
+
+// Search launch: one thread per position (neighbouring lanes read neighbouring field cells), blockIdx.y takes headings
+// [y * hc, y * hc + hc): lattice_position with the beams in range counted (the same at every pose; the lanes of a wave read
+// ranges[b] at one address).  Reads frames[p_field], the slot's field, E and the ranges; no fault bit.
 __global__ __launch_bounds__(256) void k_search_lattice(Slam2dLidar lid, Slam2dLevel lv, int p_field, int nx, int positions, int nth, int hc,
                                                         double x0, double dx, double y0, double dy, const double* __restrict__ ranges,
                                                         const double2* __restrict__ E, unsigned outside_cost,
                                                         unsigned long long* __restrict__ out) {
     const unsigned p = blockIdx.x * 256u + threadIdx.x;                           // (positions < 2^31: no wrap)
     if (p >= (unsigned)positions) return;
-    const Slam2dFrame fr = lv.frames[p_field];
-    const FieldSize fs = frame_clip(lv, fr);
-    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const SlotField sf = slot_field(lv, p_field);
     const int B = lid.beams;
-    const int iy = (int)p / nx, ix = (int)p - iy * nx;
-    const double x = x0 + (double)ix * dx, y = y0 + (double)iy * dy;
     int n_rng = 0;                                                               // beams in range: the same at every pose
     for (int b = 0; b < B; ++b) n_rng += ranges[b] < lid.max_range;
-    const int it0 = blockIdx.y * hc, it1 = min(nth, it0 + hc);
-    unsigned long long best = ~0ull;
-    for (int it = it0; it < it1; ++it) {
-        const unsigned long long cost = offsets_cost(E + (size_t)it * B, n_rng, x, y, fr, lv.step, fs, lv.fpitch, field, outside_cost);
-        best = min(best, (cost << 16) | (unsigned long long)it);
-    }
-    atomicMin(&out[p], best);
+    lattice_position(p, nx, nth, hc, x0, dx, y0, dy, E, B, n_rng, lv, sf, outside_cost, out);
 }
 
 // ---- a local search around each of N seed poses (slam2d_refine_poses) ----
@@ -4624,7 +4636,7 @@ __device__ __forceinline__ unsigned long long wave64_min_u64(unsigned long long 
     return m;
 }
 
-// First launch, one thread per seed: the move (k_mcl_move's, without noise; no motion: the seed's bits) into moved[n][3], and
+// First launch, one thread per seed: the move (mcl_move_particle's, without noise; no motion: the seed's bits) into moved[n][3], and
 // the identity of the search launch's atomicMin into out[2 n].
 __global__ __launch_bounds__(256) void k_refine_move(int N, const double* __restrict__ pose, int pstride, int has_motion, double dfwd, double dside,
                                                      double dturn, double* __restrict__ moved, unsigned long long* __restrict__ out) {
@@ -4643,16 +4655,60 @@ __global__ __launch_bounds__(256) void k_refine_move(int N, const double* __rest
     out[(size_t)n * SLAM2D_REFINE_STRIDE] = ~0ull;
 }
 
-// Search launch: block blockIdx.x = n * rows + row takes headings [row * hc, row * hc + hc) of seed n (hc * beams <= REFINE_TABLE
-// or hc == 1: slam2d_refine_poses).  Three phases, a barrier between them:
-//   1. the scan's beams IN RANGE, compacted in beam order into bidx (ballots: a wave's count, the waves' counts through LDS);
+// The block's share of a compaction in item order (beams, points): whether this thread's item is kept -> its slot; `total` runs on, the same in
+// every thread.  Ballots for a wave's count, the four waves' counts through LDS; both barriers are the block's.
+__device__ __forceinline__ int block_compact_slot(const bool keep, int* wcount, const int wv, const int lane, int& total) {
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wcount[wv] = __popcll(mask);
+    __syncthreads();
+    int base = total;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int c = wcount[w];
+        if (w < wv) base += c;
+        total += c;
+    }
+    __syncthreads();
+    return base + __popcll(mask & ((1ull << lane) - 1ull));
+}
+
+// What a block of the two refinement searches is given: blockIdx.x = n * rows + row takes headings [jt0, jt0 + hn) of seed n, whose
+// moved pose is (xm, ym, tm)
+struct RefineBlock { int n, jt0, hn; double xm, ym, tm; };
+__device__ __forceinline__ RefineBlock refine_block(const int rows, const int hc, const RefineLattice& lat, const double* __restrict__ moved) {
+    const int n = (int)(blockIdx.x / (unsigned)rows), row = (int)(blockIdx.x - (unsigned)n * (unsigned)rows);
+    const int jt0 = row * hc;
+    return RefineBlock{n, jt0, min(hc, lat.nth - jt0), moved[(size_t)n * 3], moved[(size_t)n * 3 + 1], moved[(size_t)n * 3 + 2]};
+}
+
+// The last phase of both refinement searches, behind the barrier that completes the block's table E[hn][count]: the block's
+// candidates (h, jy, jx), jx fastest, over the threads -- neighbouring lanes are neighbouring jx of one heading, so their gathers
+// fall on neighbouring field cells; every lane runs the same offset loop (offsets_cost).  cost << 20 | f is folded per thread and
+// per wave and joins the block rows -- and a block's waves -- with a 64-bit integer atomicMin on out[2 n], which k_refine_move set
+// to all ones: a minimum of integers, whatever the order.  The thread that holds f == 0 stores its cost in out[2 n + 1].
+__device__ __forceinline__ void refine_candidates(const RefineBlock& rb, const RefineLattice& lat, const double2* E, const int count,
+                                                  const Slam2dLevel& lv, const SlotField& sf, const unsigned outside_cost,
+                                                  unsigned long long* __restrict__ out) {
+    const int P = lat.nx * lat.ny, f0 = rb.jt0 * P;                              // (nx * ny * nth <= 2^20)
+    unsigned long long best = ~0ull;
+    for (int c = threadIdx.x; c < rb.hn * P; c += 256) {
+        const int h = c / P, p = c - h * P, jy = p / lat.nx, jx = p - jy * lat.nx;
+        const double x = rb.xm + (double)refine_off(jx) * lat.dx, y = rb.ym + (double)refine_off(jy) * lat.dy;
+        const unsigned long long cost = offsets_cost(E + h * count, count, x, y, sf.fr, lv.step, sf.fs, lv.fpitch, sf.field, outside_cost);
+        if (f0 + c == 0) out[(size_t)rb.n * SLAM2D_REFINE_STRIDE + 1] = cost;
+        best = min(best, (cost << 20) | (unsigned long long)(f0 + c));
+    }
+    best = wave64_min_u64(best);
+    if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(&out[(size_t)rb.n * SLAM2D_REFINE_STRIDE], best);
+}
+
+// Search launch: refine_block's headings of its seed (hc * beams <= REFINE_TABLE or hc == 1: slam2d_refine_poses).  Three
+// phases, a barrier between them:
+//   1. the scan's beams IN RANGE, compacted in beam order into bidx (block_compact_slot);
 //   2. E[h][k] = (cos(a) * r, sin(a) * r) of the block's heading h and the k-th beam in range -- the only cos / sin of the search:
 //      a heading's are evaluated once per seed, not once per candidate; the products rounded here so that x + e is x + cos(a) * r;
-//   3. the block's candidates (h, jy, jx), jx fastest, over the threads: neighbouring lanes are neighbouring jx of one heading, so
-//      their gathers fall on neighbouring field cells; every lane runs the same beam loop (offsets_cost).
-// cost << 20 | f is folded per thread and per wave and joins the block rows -- and a block's waves -- with a 64-bit integer
-// atomicMin on out[2 n], which k_refine_move set to all ones: a minimum of integers, whatever the order.  The thread that holds
-// f == 0 stores its cost in out[2 n + 1].  Reads frames[p_field], the slot's field, the moved seeds and the ranges; no fault bit.
+//   3. refine_candidates.
+// Reads frames[p_field], the slot's field, the moved seeds and the ranges; no fault bit.
 __global__ __launch_bounds__(256) void k_refine_search(Slam2dLidar lid, Slam2dLevel lv, int p_field, int rows, int hc, RefineLattice lat,
                                                        const double* __restrict__ moved, const double* __restrict__ ranges, int rstride,
                                                        unsigned outside_cost, unsigned long long* __restrict__ out) {
@@ -4660,49 +4716,26 @@ __global__ __launch_bounds__(256) void k_refine_search(Slam2dLidar lid, Slam2dLe
     __shared__ unsigned short bidx[SLAM2D_MAX_BEAMS];
     __shared__ int wcount[4];
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int n = (int)(blockIdx.x / (unsigned)rows), row = (int)(blockIdx.x - (unsigned)n * (unsigned)rows);
-    const int jt0 = row * hc, hn = min(hc, lat.nth - jt0);
-    const Slam2dFrame fr = lv.frames[p_field];
-    const FieldSize fs = frame_clip(lv, fr);
-    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
-    const double xm = moved[(size_t)n * 3], ym = moved[(size_t)n * 3 + 1], tm = moved[(size_t)n * 3 + 2];
-    const double* __restrict__ rg = ranges + (size_t)n * rstride;
+    const RefineBlock rb = refine_block(rows, hc, lat, moved);
+    const SlotField sf = slot_field(lv, p_field);
+    const double* __restrict__ rg = ranges + (size_t)rb.n * rstride;
     const int B = lid.beams;
     int n_rng = 0;                                                               // beams in range (block-uniform)
     for (int b0 = 0; b0 < B; b0 += 256) {
         const int b = b0 + tid;
         const bool in_range = b < B && rg[b] < lid.max_range;                    // :84 (NaN and +inf are out, 0 and negatives in)
-        const unsigned long long mask = __ballot(in_range);
-        if (lane == 0) wcount[wv] = __popcll(mask);
-        __syncthreads();
-        int base = n_rng;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int c = wcount[w];
-            if (w < wv) base += c;
-            n_rng += c;
-        }
-        if (in_range) bidx[base + __popcll(mask & ((1ull << lane) - 1ull))] = (unsigned short)b;
-        __syncthreads();
+        const int slot = block_compact_slot(in_range, wcount, wv, lane, n_rng);
+        if (in_range) bidx[slot] = (unsigned short)b;
     }
-    for (int i = tid; i < hn * n_rng; i += 256) {                                // (hn * n_rng <= REFINE_TABLE)
+    __syncthreads();
+    for (int i = tid; i < rb.hn * n_rng; i += 256) {                             // (hn * n_rng <= REFINE_TABLE)
         const int h = i / n_rng, b = bidx[i - h * n_rng];
         const double r = rg[b];
-        const double a = fan_of(lid, tm + (double)refine_off(jt0 + h) * lat.dth).angle(b);
+        const double a = fan_of(lid, rb.tm + (double)refine_off(rb.jt0 + h) * lat.dth).angle(b);
         E[i] = make_double2(cos(a) * r, sin(a) * r);                             // :87-88
     }
     __syncthreads();
-    const int P = lat.nx * lat.ny, f0 = jt0 * P;                                 // (nx * ny * nth <= 2^20)
-    unsigned long long best = ~0ull;
-    for (int c = tid; c < hn * P; c += 256) {
-        const int h = c / P, p = c - h * P, jy = p / lat.nx, jx = p - jy * lat.nx;
-        const double x = xm + (double)refine_off(jx) * lat.dx, y = ym + (double)refine_off(jy) * lat.dy;
-        const unsigned long long cost = offsets_cost(E + h * n_rng, n_rng, x, y, fr, lv.step, fs, lv.fpitch, field, outside_cost);
-        if (f0 + c == 0) out[(size_t)n * SLAM2D_REFINE_STRIDE + 1] = cost;
-        best = min(best, (cost << 20) | (unsigned long long)(f0 + c));
-    }
-    best = wave64_min_u64(best);
-    if (lane == 0 && best != ~0ull) atomicMin(&out[(size_t)n * SLAM2D_REFINE_STRIDE], best);
+    refine_candidates(rb, lat, E, n_rng, lv, sf, outside_cost, out);
 }
 
 // Last launch, one thread per seed: the winning candidate's pose from its flat index, by the candidates' own three operations
@@ -4731,23 +4764,6 @@ __device__ __forceinline__ bool point_valid(const double* __restrict__ pts, cons
 __device__ __forceinline__ double2 point_offset(const double c, const double s, const double qx, const double qy) {
     return make_double2(c * qx - s * qy, s * qx + c * qy);
 }
-// The block's share of a compaction in point order: whether this thread's item is kept -> its slot; `total` runs on, the same in
-// every thread.  Ballots for a wave's count, the four waves' counts through LDS; both barriers are the block's.
-__device__ __forceinline__ int block_compact_slot(const bool keep, int* wcount, const int wv, const int lane, int& total) {
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) wcount[wv] = __popcll(mask);
-    __syncthreads();
-    int base = total;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int c = wcount[w];
-        if (w < wv) base += c;
-        total += c;
-    }
-    __syncthreads();
-    return base + __popcll(mask & ((1ull << lane) - 1ull));
-}
-
 // First launch of the search: block `it` < nth writes heading it's row E[it][0 .. valid) -- thread 0 evaluates the heading's cos /
 // sin, the only ones of the search, the block compacts the valid points in point order and rotates them -- and every block sets
 // its 256 words of d_out to all ones, the identity of the search launch's atomicMin (the grid covers both: slam2d_search_points).
@@ -4776,36 +4792,26 @@ __global__ __launch_bounds__(256) void k_points_table(int nth, double th0, doubl
     }
 }
 
-// Search launch: k_search_lattice with the valid points counted in place of the beams in range (the same at every pose; the lanes
-// of a wave read a point at one address).  Reads frames[p_field], the slot's field, E and the points; no fault bit.
+// Search launch: k_search_lattice's, lattice_position with the valid points counted in place of the beams in range (the same at
+// every pose; the lanes of a wave read a point at one address).  Reads frames[p_field], the slot's field, E and the points; no
+// fault bit.
 __global__ __launch_bounds__(256) void k_points_lattice(Slam2dLevel lv, int p_field, int nx, int positions, int nth, int hc, double x0, double dx,
                                                         double y0, double dy, const double* __restrict__ pts, int pstride, int M,
                                                         const double2* __restrict__ E, unsigned outside_cost,
                                                         unsigned long long* __restrict__ out) {
     const unsigned p = blockIdx.x * 256u + threadIdx.x;                           // (positions < 2^31: no wrap)
     if (p >= (unsigned)positions) return;
-    const Slam2dFrame fr = lv.frames[p_field];
-    const FieldSize fs = frame_clip(lv, fr);
-    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
-    const int iy = (int)p / nx, ix = (int)p - iy * nx;
-    const double x = x0 + (double)ix * dx, y = y0 + (double)iy * dy;
+    const SlotField sf = slot_field(lv, p_field);
     int valid = 0;
     for (int k = 0; k < M; ++k) valid += point_valid(pts, pstride, k);
-    const int it0 = blockIdx.y * hc, it1 = min(nth, it0 + hc);
-    unsigned long long best = ~0ull;
-    for (int it = it0; it < it1; ++it) {
-        const unsigned long long cost = offsets_cost(E + (size_t)it * M, valid, x, y, fr, lv.step, fs, lv.fpitch, field, outside_cost);
-        best = min(best, (cost << 16) | (unsigned long long)it);
-    }
-    atomicMin(&out[p], best);
+    lattice_position(p, nx, nth, hc, x0, dx, y0, dy, E, M, valid, lv, sf, outside_cost, out);
 }
 
-// Search launch of the refinement: k_refine_search's block -- blockIdx.x = n * rows + row takes headings [row * hc, row * hc + hc)
-// of seed n, hc * M <= REFINE_TABLE or hc == 1 -- with the first two phases for points:
+// Search launch of the refinement: k_refine_search's block (hc * M <= REFINE_TABLE or hc == 1) with the first two phases for points:
 //   1. the set's VALID points, compacted in point order into kidx;
 //   2. E[h][k] = R(tm + off(jt0 + h) * dth) q of the block's heading h and the k-th valid point q: the headings' cos / sin first,
 //      one per heading and seed and POINTS_HEADS of them at a time, then the rotations;
-//   3. the candidates, the packed minimum, the join and cost(0) as k_refine_search has them.
+//   3. refine_candidates.
 // Reads frames[p_field], the slot's field, the moved seeds and the points; no fault bit.
 __global__ __launch_bounds__(256) void k_refine_points(Slam2dLevel lv, int p_field, int rows, int hc, RefineLattice lat,
                                                        const double* __restrict__ moved, const double* __restrict__ points, int pstride, int M,
@@ -4815,13 +4821,9 @@ __global__ __launch_bounds__(256) void k_refine_points(Slam2dLevel lv, int p_fie
     __shared__ unsigned short kidx[SLAM2D_MAX_POINTS];
     __shared__ int wcount[4];
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int n = (int)(blockIdx.x / (unsigned)rows), row = (int)(blockIdx.x - (unsigned)n * (unsigned)rows);
-    const int jt0 = row * hc, hn = min(hc, lat.nth - jt0);
-    const Slam2dFrame fr = lv.frames[p_field];
-    const FieldSize fs = frame_clip(lv, fr);
-    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
-    const double xm = moved[(size_t)n * 3], ym = moved[(size_t)n * 3 + 1], tm = moved[(size_t)n * 3 + 2];
-    const double* __restrict__ pts = points + (size_t)n * sstride;
+    const RefineBlock rb = refine_block(rows, hc, lat, moved);
+    const SlotField sf = slot_field(lv, p_field);
+    const double* __restrict__ pts = points + (size_t)rb.n * sstride;
     int valid = 0;                                                               // (block-uniform)
     for (int k0 = 0; k0 < M; k0 += 256) {
         const int k = k0 + tid;
@@ -4830,10 +4832,10 @@ __global__ __launch_bounds__(256) void k_refine_points(Slam2dLevel lv, int p_fie
         if (keep) kidx[slot] = (unsigned short)k;
     }
     __syncthreads();
-    for (int h0 = 0; h0 < hn; h0 += POINTS_HEADS) {                              // (one pass from 16 points on: hn * valid <= REFINE_TABLE)
-        const int h1 = min(hn, h0 + POINTS_HEADS);
+    for (int h0 = 0; h0 < rb.hn; h0 += POINTS_HEADS) {                           // (one pass from 16 points on: hn * valid <= REFINE_TABLE)
+        const int h1 = min(rb.hn, h0 + POINTS_HEADS);
         if (tid < h1 - h0) {
-            const double th = tm + (double)refine_off(jt0 + h0 + tid) * lat.dth;
+            const double th = rb.tm + (double)refine_off(rb.jt0 + h0 + tid) * lat.dth;
             cs[tid] = make_double2(cos(th), sin(th));
         }
         __syncthreads();
@@ -4843,17 +4845,7 @@ __global__ __launch_bounds__(256) void k_refine_points(Slam2dLevel lv, int p_fie
         }
         __syncthreads();
     }
-    const int P = lat.nx * lat.ny, f0 = jt0 * P;                                 // (nx * ny * nth <= 2^20)
-    unsigned long long best = ~0ull;
-    for (int c = tid; c < hn * P; c += 256) {
-        const int h = c / P, p = c - h * P, jy = p / lat.nx, jx = p - jy * lat.nx;
-        const double x = xm + (double)refine_off(jx) * lat.dx, y = ym + (double)refine_off(jy) * lat.dy;
-        const unsigned long long cost = offsets_cost(E + h * valid, valid, x, y, fr, lv.step, fs, lv.fpitch, field, outside_cost);
-        if (f0 + c == 0) out[(size_t)n * SLAM2D_REFINE_STRIDE + 1] = cost;
-        best = min(best, (cost << 20) | (unsigned long long)(f0 + c));
-    }
-    best = wave64_min_u64(best);
-    if (lane == 0 && best != ~0ull) atomicMin(&out[(size_t)n * SLAM2D_REFINE_STRIDE], best);
+    refine_candidates(rb, lat, E, valid, lv, sf, outside_cost, out);
 }
 
 // ---- Monte-Carlo localisation in a known map (slam2d_mcl_step): move, weigh, resample, all in integers and rounded operations ----
@@ -4914,20 +4906,17 @@ __device__ __forceinline__ unsigned long long block_scan_u64(unsigned long long 
     return v + off;
 }
 
-// First launch, one thread per particle: the three draws and the move, in the header's operations and order; thread 0 also sets
-// the identities of what the later launches join with integer atomics.  (Moving the pose inside the scoring launch, where a wave
-// holds one particle, costs that wave a cos / sin of its own: as much as 64 beams, a fourth trip beside the three of 180 beams --
-// profiles/r13_mcl_step.md.)
-__global__ __launch_bounds__(256) void k_mcl_move(int N, const double* __restrict__ pose, int pstride, double dfwd, double dside, double dturn,
-                                                  double amp0, double amp1, double amp2, uint64_t seed, uint64_t scan, MclWork wk,
-                                                  unsigned long long* __restrict__ report) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n == 0) {
-        *wk.key = ~0ull;
-        report[3] = 0ull; report[6] = 0ull;
-        for (int i = 10; i < 15; ++i) report[i] = 0ull;
-    }
-    if (n >= N) return;
+// The identities of what the later launches of a step join with integer atomics: the packed minimum and the report's words 3,
+// 6 and 10-14.  One thread of the first launch.
+__device__ __forceinline__ void mcl_reset_joined(const MclWork& wk, unsigned long long* __restrict__ report) {
+    *wk.key = ~0ull;
+    report[3] = 0ull; report[6] = 0ull;
+    for (int i = 10; i < 15; ++i) report[i] = 0ull;
+}
+// Particle n's three draws and its move, in the header's operations and order
+__device__ __forceinline__ void mcl_move_particle(const int n, const double* __restrict__ pose, const int pstride, const double dfwd, const double dside,
+                                                  const double dturn, const double amp0, const double amp1, const double amp2, const uint64_t seed,
+                                                  const uint64_t scan, const MclWork& wk) {
     const double x0 = pose[(size_t)n * pstride], y0 = pose[(size_t)n * pstride + 1], th0 = pose[(size_t)n * pstride + 2];
     const double fx = dfwd + amp0 * mcl_noise((uint32_t)n, 0u, seed, scan), fy = dside + amp1 * mcl_noise((uint32_t)n, 1u, seed, scan);
     const double c = cos(th0), s = sin(th0);
@@ -4935,6 +4924,18 @@ __global__ __launch_bounds__(256) void k_mcl_move(int N, const double* __restric
     m[0] = (x0 + c * fx) - s * fy;
     m[1] = (y0 + s * fx) + c * fy;
     m[2] = (th0 + dturn) + amp2 * mcl_noise((uint32_t)n, 2u, seed, scan);
+}
+
+// First launch, one thread per particle: mcl_move_particle; thread 0 also resets the joined words.  (Moving the pose inside the
+// scoring launch, where a wave holds one particle, costs that wave a cos / sin of its own: as much as 64 beams, a fourth trip
+// beside the three of 180 beams -- profiles/r13_mcl_step.md.)
+__global__ __launch_bounds__(256) void k_mcl_move(int N, const double* __restrict__ pose, int pstride, double dfwd, double dside, double dturn,
+                                                  double amp0, double amp1, double amp2, uint64_t seed, uint64_t scan, MclWork wk,
+                                                  unsigned long long* __restrict__ report) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0) mcl_reset_joined(wk, report);
+    if (n >= N) return;
+    mcl_move_particle(n, pose, pstride, dfwd, dside, dturn, amp0, amp1, amp2, seed, scan, wk);
 }
 
 // U trips of 64 beams of one particle, from beam b0: every cell first, then the gathers, then the sums.  A beam that is not inside
@@ -4967,18 +4968,13 @@ __device__ __forceinline__ void mcl_beams(const int b0, const int lane, const in
     for (int u = 0; u < U; ++u) sum_b += inside[u] ? cost[u] : 0u;
 }
 
-// Score: k_score_poses' shape -- one wave per particle, beams interleaved over the lanes, the ranges read contiguously -- without
-// its cell set, on the moved poses; the trips of 64 beams go MCL_UNROLL at a time, the rest one by one.  cost << 20 | n joins the
+// Particle n on this wave: k_score_poses' shape -- beams interleaved over the lanes, the ranges read contiguously -- without its
+// cell set, on the moved pose; the trips of 64 beams go MCL_UNROLL at a time, the rest one by one.  cost << 20 | n joins the
 // particles in one 64-bit integer atomicMin, sent only where it can lower the word as last read (a stale read costs an atomic,
-// never the result).  Reads frames[p_field], the slot's field, the moved poses and the ranges; writes the costs; no fault bit.
-__global__ __launch_bounds__(64 * MCL_WAVES) void k_mcl_score(Slam2dLidar lid, Slam2dLevel lv, int p_field, int N, const double* __restrict__ ranges,
-                                                              unsigned outside_cost, MclWork wk) {
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n = blockIdx.x * MCL_WAVES + wv;
-    if (n >= N) return;                                                          // (wave-uniform)
-    const Slam2dFrame fr = lv.frames[p_field];
-    const FieldSize fs = frame_clip(lv, fr);
-    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+// never the result).  Writes the particle's cost.
+__device__ __forceinline__ void mcl_score_particle(const int n, const int lane, const Slam2dLidar& lid, const Slam2dLevel& lv, const Slam2dFrame& fr,
+                                                   const FieldSize fs, const uint32_t* __restrict__ field, const double* __restrict__ ranges,
+                                                   const unsigned outside_cost, const MclWork& wk) {
     const double x = wk.moved[(size_t)n * 3], y = wk.moved[(size_t)n * 3 + 1], th = wk.moved[(size_t)n * 3 + 2];
     const int B = lid.beams, trips = (B + 63) >> 6;
     const BeamFan fan = fan_of(lid, th);
@@ -4997,10 +4993,22 @@ __global__ __launch_bounds__(64 * MCL_WAVES) void k_mcl_score(Slam2dLidar lid, S
     }
 }
 
-// Weigh and scan: block b takes particles [b * MCL_SCAN_BLOCK, ...), four consecutive ones per thread; their integer weights from
-// the table, the block-local inclusive prefix sums into csum, the block's sum into bsum[b], the weights above zero counted
-__global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcl_weigh(int N, const uint32_t* __restrict__ lut, int lut_n, int lut_shift, MclWork wk,
-                                                                  unsigned long long* __restrict__ report) {
+// Score: one wave per particle (mcl_score_particle).  Reads frames[p_field], the slot's field, the moved poses and the ranges;
+// writes the costs; no fault bit.
+__global__ __launch_bounds__(64 * MCL_WAVES) void k_mcl_score(Slam2dLidar lid, Slam2dLevel lv, int p_field, int N, const double* __restrict__ ranges,
+                                                              unsigned outside_cost, MclWork wk) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = blockIdx.x * MCL_WAVES + wv;
+    if (n >= N) return;                                                          // (wave-uniform)
+    const SlotField sf = slot_field(lv, p_field);
+    mcl_score_particle(n, lane, lid, lv, sf.fr, sf.fs, sf.field, ranges, outside_cost, wk);
+}
+
+// Weigh and scan, a block of MCL_SCAN_BLOCK / 4 threads: block b takes particles [b * MCL_SCAN_BLOCK, ...) below N, four
+// consecutive ones per thread; their integer weights from the table, the block-local inclusive prefix sums into csum, the block's
+// sum into bsum[b], the weights above zero counted.  Every thread of the block calls it: the barriers are the block's.
+__device__ __forceinline__ void mcl_weigh_block(const int N, const uint32_t* __restrict__ lut, const int lut_n, const int lut_shift, const MclWork& wk,
+                                                unsigned long long* __restrict__ report) {
     __shared__ unsigned long long lds[16];
     __shared__ unsigned n_pos;
     if (threadIdx.x == 0) n_pos = 0u;
@@ -5032,10 +5040,16 @@ __global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcl_weigh(int N, const u
     }
 }
 
-// One block: the scan blocks' sums become their exclusive prefix sums; W, the resampler's word and u0, and the report's words
-// that need no particle loop
-__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcl_sums(Slam2dLidar lid, int N, uint64_t seed, uint64_t scan, const double* __restrict__ ranges,
-                                                             MclWork wk, unsigned long long* __restrict__ report) {
+// Weigh and scan: mcl_weigh_block, a block per MCL_SCAN_BLOCK particles
+__global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcl_weigh(int N, const uint32_t* __restrict__ lut, int lut_n, int lut_shift, MclWork wk,
+                                                                  unsigned long long* __restrict__ report) {
+    mcl_weigh_block(N, lut, lut_n, lut_shift, wk, report);
+}
+
+// One block of MCL_SCAN_BLOCK threads: the scan blocks' sums become their exclusive prefix sums; W, the resampler's word and u0,
+// and the report's words 0-15 that need no particle loop
+__device__ __forceinline__ void mcl_sums_block(const Slam2dLidar& lid, const int N, const uint64_t seed, const uint64_t scan,
+                                               const double* __restrict__ ranges, const MclWork& wk, unsigned long long* __restrict__ report) {
     __shared__ unsigned long long lds[16];
     __shared__ unsigned n_rng;
     const int t = threadIdx.x, nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
@@ -5061,55 +5075,61 @@ __global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcl_sums(Slam2dLidar lid, in
     }
 }
 
-// Resample: one thread per offspring k.  t_k = floor((k W + u0) / N) < W (below 2^64: W <= N * 0xffffff, N <= 2^20); its ancestor
-// the least n with t_k < C_n, found in the scan blocks' prefix sums, then in that block's local ones.  k is its ancestor's FIRST
-// offspring iff t_(k-1) falls in front of the ancestor's share -- the count of those is the number of distinct ancestors.  The
-// sums of the report are joined per block, then with integer atomics.
-__global__ __launch_bounds__(256) void k_mcl_resample(int N, MclWork wk, double* __restrict__ out, int pstride, int32_t* __restrict__ ancestor,
-                                                      unsigned long long* __restrict__ report) {
-    __shared__ unsigned long long acc[6];
-    if (threadIdx.x < 6) acc[threadIdx.x] = 0ull;
-    __syncthreads();
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long W = report[2], u0 = report[4];
-    unsigned long long part[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};            // first offspring, M, the four sums
-    if (k < N) {
-        int a = k;
-        bool first = true;
-        if (W) {
-            const unsigned long long t = ((unsigned long long)k * W + u0) / (unsigned long long)N;
-            const int nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
-            int lo = 0, hi = nb - 1;                                             // the least block whose inclusive end is beyond t
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (t < wk.bsum[mid + 1]) hi = mid; else lo = mid + 1;           // (mid + 1 <= nb - 1: block mid's end is the next one's start)
-            }
-            const unsigned long long start = wk.bsum[lo], rel = t - start;
-            const int base = lo * MCL_SCAN_BLOCK;
-            int i0 = 0, i1 = min(MCL_SCAN_BLOCK, N - base) - 1;                  // rel < the block's sum = csum of its last particle
-            while (i0 < i1) {
-                const int mid = (i0 + i1) >> 1;
-                if (rel < wk.csum[base + mid]) i1 = mid; else i0 = mid + 1;
-            }
-            a = base + i0;
-            if (k > 0) {
-                const unsigned long long tp = ((unsigned long long)(k - 1) * W + u0) / (unsigned long long)N;
-                first = tp < start + (i0 > 0 ? wk.csum[a - 1] : 0ull);
-            }
-        }
-        const double x = wk.moved[(size_t)a * 3], y = wk.moved[(size_t)a * 3 + 1], th = wk.moved[(size_t)a * 3 + 2];
-        double* o = out + (size_t)k * pstride;
-        o[0] = x; o[1] = y; o[2] = th;
-        if (ancestor) ancestor[k] = a;
-        part[0] = first;
-        if (fabs(x) < 0x1p20 && fabs(y) < 0x1p20 && __builtin_isfinite(th)) {    // (a NaN fails the comparisons)
-            part[1] = 1ull;
-            part[2] = (unsigned long long)llrint(x * 65536.0);
-            part[3] = (unsigned long long)llrint(y * 65536.0);
-            part[4] = (unsigned long long)llrint(cos(th) * 0x1p30);
-            part[5] = (unsigned long long)llrint(sin(th) * 0x1p30);
-        }
+// Sums: mcl_sums_block, one block
+__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcl_sums(Slam2dLidar lid, int N, uint64_t seed, uint64_t scan, const double* __restrict__ ranges,
+                                                             MclWork wk, unsigned long long* __restrict__ report) {
+    mcl_sums_block(lid, N, seed, scan, ranges, wk, report);
+}
+
+// The resampler's pieces.  Offspring k of n_off has the ticket t_k = floor((k W + u0) / n_off) < W (below 2^64: W <= N * 0xffffff,
+// N and n_off <= 2^20).
+// The ancestor of ticket t among N particles: the least a with t < C_a, found in the scan blocks' prefix sums (block `start`s at
+// bsum[lo]), then in that block's local ones (a = its i0-th particle).
+struct MclAncestor { int a, i0; unsigned long long start; };
+__device__ __forceinline__ MclAncestor mcl_ancestor(const unsigned long long t, const int N, const MclWork& wk) {
+    const int nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
+    int lo = 0, hi = nb - 1;                                                     // the least block whose inclusive end is beyond t
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t < wk.bsum[mid + 1]) hi = mid; else lo = mid + 1;                   // (mid + 1 <= nb - 1: block mid's end is the next one's start)
     }
+    const unsigned long long start = wk.bsum[lo], rel = t - start;
+    const int base = lo * MCL_SCAN_BLOCK;
+    int i0 = 0, i1 = min(MCL_SCAN_BLOCK, N - base) - 1;                          // rel < the block's sum = csum of its last particle
+    while (i0 < i1) {
+        const int mid = (i0 + i1) >> 1;
+        if (rel < wk.csum[base + mid]) i1 = mid; else i0 = mid + 1;
+    }
+    return MclAncestor{base + i0, i0, start};
+}
+// k is its ancestor's FIRST offspring iff t_(k-1) falls in front of the ancestor's share -- the count of those is the number of
+// distinct ancestors
+__device__ __forceinline__ bool mcl_first_offspring(const int k, const MclAncestor& an, const unsigned long long W, const unsigned long long u0,
+                                                    const int n_off, const MclWork& wk) {
+    if (k <= 0) return true;                                                     // (offspring 0; k - 1 >= 0 below: an unsigned product)
+    const unsigned long long tp = ((unsigned long long)(k - 1) * W + u0) / (unsigned long long)n_off;
+    return tp < an.start + (an.i0 > 0 ? wk.csum[an.a - 1] : 0ull);
+}
+// Offspring k is particle a: the pose, the ancestor, and this thread's share of the report's sums into part[] -- first offspring,
+// M, the four sums
+__device__ __forceinline__ void mcl_emit_offspring(const int k, const int a, const bool first, const MclWork& wk, double* __restrict__ out,
+                                                   const int pstride, int32_t* __restrict__ ancestor, unsigned long long (&part)[6]) {
+    const double x = wk.moved[(size_t)a * 3], y = wk.moved[(size_t)a * 3 + 1], th = wk.moved[(size_t)a * 3 + 2];
+    double* o = out + (size_t)k * pstride;
+    o[0] = x; o[1] = y; o[2] = th;
+    if (ancestor) ancestor[k] = a;
+    part[0] += first;
+    if (fabs(x) < 0x1p20 && fabs(y) < 0x1p20 && __builtin_isfinite(th)) {        // (a NaN fails the comparisons)
+        part[1] += 1ull;
+        part[2] += (unsigned long long)llrint(x * 65536.0);
+        part[3] += (unsigned long long)llrint(y * 65536.0);
+        part[4] += (unsigned long long)llrint(cos(th) * 0x1p30);
+        part[5] += (unsigned long long)llrint(sin(th) * 0x1p30);
+    }
+}
+// The threads' part[] joined per block in acc[] (zeroed in front of a barrier), then with integer atomics into the report's words
+// 6 and 10-14.  Every thread of the block calls it.
+__device__ __forceinline__ void mcl_join_sums(const unsigned long long (&part)[6], unsigned long long* acc, unsigned long long* __restrict__ report) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) {                                                // (every lane is here: signed sums in two's complement)
         const unsigned long long s = wave64_sum_u64(part[i]);
@@ -5119,10 +5139,32 @@ __global__ __launch_bounds__(256) void k_mcl_resample(int N, MclWork wk, double*
     if (threadIdx.x < 6 && acc[threadIdx.x]) atomicAdd(&report[threadIdx.x == 0 ? 6 : 9 + threadIdx.x], acc[threadIdx.x]);
 }
 
+// Resample: one thread per offspring k of N.  W == 0: every particle is its own offspring.
+__global__ __launch_bounds__(256) void k_mcl_resample(int N, MclWork wk, double* __restrict__ out, int pstride, int32_t* __restrict__ ancestor,
+                                                      unsigned long long* __restrict__ report) {
+    __shared__ unsigned long long acc[6];
+    if (threadIdx.x < 6) acc[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long W = report[2], u0 = report[4];
+    unsigned long long part[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    if (k < N) {
+        int a = k;
+        bool first = true;
+        if (W) {
+            const MclAncestor an = mcl_ancestor(((unsigned long long)k * W + u0) / (unsigned long long)N, N, wk);
+            a = an.a;
+            first = mcl_first_offspring(k, an, W, u0, N, wk);
+        }
+        mcl_emit_offspring(k, a, first, wk, out, pstride, ancestor, part);
+    }
+    mcl_join_sums(part, acc, report);
+}
+
 // ---- slam2d_mcl_step_adaptive: the same step over a LIVE count N that only the device knows, sized by the occupied pose bins ----
 // No launch can be sized by N: every per-particle launch is a grid of at most MCLA_BLOCKS blocks (MCLA_SCORE_BLOCKS for the wave
 // per particle of the scoring launch) that strides over n < N, so its cost follows N and not the capacity.  The loop bodies are
-// those of the k_mcl_* kernels above, operation for operation.
+// the mcl_* bodies above, which the k_mcl_* kernels call too: one statement of each stage for both steps.
 #define MCLA_BLOCKS 1024             // blocks of 256 threads: four per compute unit, 2^18 threads -- four particles each at 2^20
 #define MCLA_SCORE_BLOCKS 2048       // blocks of MCL_WAVES waves: 32 waves per compute unit, a little more than its registers let it hold (28)
 #define MCLA_REF_BLOCKS 512          // blocks of the reference-ancestor launch: fewer and longer, so that a block's filter sees more of a bin
@@ -5134,123 +5176,47 @@ __device__ __forceinline__ int mcla_live(const uint32_t* __restrict__ n_in, cons
 }
 __host__ __device__ __forceinline__ long long mcla_bitmap_words(const long long n_bins) { return (n_bins + 64) / 64; }   // n_bins + 1 bits
 
-// k_mcl_move over n < N; thread 0 also zeroes the two counters of the tail, and the grid clears the bitmap
+// mcl_move_particle over n < N; thread 0 resets the joined words and the two counters of the tail, and the grid clears the bitmap
 __global__ __launch_bounds__(256) void k_mcla_move(const uint32_t* __restrict__ n_in, int n_cap, const double* __restrict__ pose, int pstride,
                                                    double dfwd, double dside, double dturn, double amp0, double amp1, double amp2,
                                                    uint64_t seed, uint64_t scan, MclWork wk, unsigned long long* __restrict__ bitmap, int words,
                                                    unsigned long long* __restrict__ tail, unsigned long long* __restrict__ report) {
     const int N = mcla_live(n_in, n_cap), t0 = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
     if (t0 == 0) {
-        *wk.key = ~0ull;
-        report[3] = 0ull; report[6] = 0ull;
-        for (int i = 10; i < 15; ++i) report[i] = 0ull;
+        mcl_reset_joined(wk, report);
         tail[0] = 0ull; tail[1] = 0ull;
     }
     for (int i = t0; i < words; i += stride) bitmap[i] = 0ull;
-    for (int n = t0; n < N; n += stride) {
-        const double x0 = pose[(size_t)n * pstride], y0 = pose[(size_t)n * pstride + 1], th0 = pose[(size_t)n * pstride + 2];
-        const double fx = dfwd + amp0 * mcl_noise((uint32_t)n, 0u, seed, scan), fy = dside + amp1 * mcl_noise((uint32_t)n, 1u, seed, scan);
-        const double c = cos(th0), s = sin(th0);
-        double* m = wk.moved + (size_t)n * 3;
-        m[0] = (x0 + c * fx) - s * fy;
-        m[1] = (y0 + s * fx) + c * fy;
-        m[2] = (th0 + dturn) + amp2 * mcl_noise((uint32_t)n, 2u, seed, scan);
-    }
+    for (int n = t0; n < N; n += stride) mcl_move_particle(n, pose, pstride, dfwd, dside, dturn, amp0, amp1, amp2, seed, scan, wk);
 }
 
-// k_mcl_score: a wave takes particles wave, wave + the grid's waves, ... below N
+// mcl_score_particle: a wave takes particles wave, wave + the grid's waves, ... below N
 __global__ __launch_bounds__(64 * MCL_WAVES) void k_mcla_score(Slam2dLidar lid, Slam2dLevel lv, int p_field, const uint32_t* __restrict__ n_in, int n_cap,
                                                                const double* __restrict__ ranges, unsigned outside_cost, MclWork wk) {
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int N = mcla_live(n_in, n_cap);
-    const Slam2dFrame fr = lv.frames[p_field];
-    const FieldSize fs = frame_clip(lv, fr);
-    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
-    const int B = lid.beams, trips = (B + 63) >> 6;
-    for (int n = blockIdx.x * MCL_WAVES + wv; n < N; n += gridDim.x * MCL_WAVES) {   // (wave-uniform)
-        const double x = wk.moved[(size_t)n * 3], y = wk.moved[(size_t)n * 3 + 1], th = wk.moved[(size_t)n * 3 + 2];
-        const BeamFan fan = fan_of(lid, th);
-        unsigned long long sum_b = 0ull;
-        int n_in_field = 0, n_rng = 0;
-        int t = 0;
-        for (; t + MCL_UNROLL <= trips; t += MCL_UNROLL)
-            mcl_beams<MCL_UNROLL>(64 * t, lane, B, ranges, lid.max_range, fan, x, y, fr, lv.step, fs, lv.fpitch, field, sum_b, n_in_field, n_rng);
-        for (; t < trips; ++t) mcl_beams<1>(64 * t, lane, B, ranges, lid.max_range, fan, x, y, fr, lv.step, fs, lv.fpitch, field, sum_b, n_in_field, n_rng);
-        sum_b = wave64_sum_u64(sum_b);
-        if (lane == 0) {
-            const unsigned long long cost = sum_b + (unsigned long long)(n_rng - n_in_field) * outside_cost;
-            wk.cost[n] = cost;
-            const unsigned long long v = (cost << 20) | (unsigned long long)n;
-            if (v < __hip_atomic_load(wk.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(wk.key, v);
-        }
-    }
+    const SlotField sf = slot_field(lv, p_field);
+    for (int n = blockIdx.x * MCL_WAVES + wv; n < N; n += gridDim.x * MCL_WAVES)   // (wave-uniform)
+        mcl_score_particle(n, lane, lid, lv, sf.fr, sf.fs, sf.field, ranges, outside_cost, wk);
 }
 
-// k_mcl_weigh, launched for the capacity: a block beyond N writes a zero sum and is done
+// mcl_weigh_block, launched for the capacity: a block beyond N writes a zero sum and is done
 __global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcla_weigh(const uint32_t* __restrict__ n_in, int n_cap, const uint32_t* __restrict__ lut, int lut_n,
                                                                    int lut_shift, MclWork wk, unsigned long long* __restrict__ report) {
-    __shared__ unsigned long long lds[16];
-    __shared__ unsigned n_pos;
     const int N = mcla_live(n_in, n_cap);
-    if (blockIdx.x * MCL_SCAN_BLOCK >= N) {                                      // (block-uniform)
+    if (blockIdx.x * MCL_SCAN_BLOCK >= N) {                                      // (block-uniform, in front of the first barrier)
         if (threadIdx.x == 0) wk.bsum[blockIdx.x] = 0ull;
         return;
     }
-    if (threadIdx.x == 0) n_pos = 0u;
-    const unsigned long long cmin = *wk.key >> 20;
-    const int n0 = blockIdx.x * MCL_SCAN_BLOCK + threadIdx.x * 4;
-    unsigned long long pre[4], run = 0ull;
-    unsigned pos = 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        uint32_t w = 0u;
-        if (n0 + i < N) {
-            const unsigned long long d = (wk.cost[n0 + i] - cmin) >> lut_shift;
-            w = min(lut[d < (unsigned long long)(lut_n - 1) ? (int)d : lut_n - 1], (uint32_t)SLAM2D_MCL_MAX_WEIGHT);
-        }
-        pos += w > 0u;
-        run += w;
-        pre[i] = run;
-    }
-    unsigned long long total;
-    const unsigned long long off = block_scan_u64(run, lds, total) - run;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (n0 + i < N) wk.csum[n0 + i] = off + pre[i];
-    if (pos) atomicAdd(&n_pos, pos);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        wk.bsum[blockIdx.x] = total;
-        if (n_pos) atomicAdd(&report[3], (unsigned long long)n_pos);
-    }
+    mcl_weigh_block(N, lut, lut_n, lut_shift, wk, report);
 }
 
-// k_mcl_sums; word 16 = N is what the last launch reads, as it may overwrite *n_in
+// mcl_sums_block; word 16 = N is what the last launch reads, as it may overwrite *n_in
 __global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcla_sums(Slam2dLidar lid, const uint32_t* __restrict__ n_in, int n_cap, uint64_t seed, uint64_t scan,
                                                               const double* __restrict__ ranges, MclWork wk, unsigned long long* __restrict__ report) {
-    __shared__ unsigned long long lds[16];
-    __shared__ unsigned n_rng;
     const int N = mcla_live(n_in, n_cap);
-    const int t = threadIdx.x, nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
-    if (t == 0) n_rng = 0u;
-    const unsigned long long v = t < nb ? wk.bsum[t] : 0ull;
-    unsigned long long W;
-    const unsigned long long incl = block_scan_u64(v, lds, W);
-    if (t < nb) wk.bsum[t] = incl - v;
-    unsigned cnt = 0u;
-    for (int b = t; b < lid.beams; b += MCL_SCAN_BLOCK) cnt += ranges[b] < lid.max_range;
-    if (cnt) atomicAdd(&n_rng, cnt);
-    __syncthreads();
-    if (t == 0) {
-        const unsigned long long key = *wk.key, best = key & 0xfffffull;
-        const unsigned long long r = philox4x32_10(0xffffffffu, 0u, (uint32_t)scan, (uint32_t)(scan >> 32), (uint32_t)seed, (uint32_t)(seed >> 32)).v[0];
-        report[0] = key >> 20;
-        report[1] = best;
-        report[2] = W;
-        report[4] = (W >> 32) * r + (((W & 0xffffffffull) * r) >> 32);
-        report[5] = n_rng;
-        for (int i = 0; i < 3; ++i) report[7 + i] = (unsigned long long)__double_as_longlong(wk.moved[best * 3 + i]);
-        report[15] = 0ull;
+    mcl_sums_block(lid, N, seed, scan, ranges, wk, report);
+    if (threadIdx.x == 0) {
         report[16] = (unsigned long long)N;
         for (int i = 20; i < 24; ++i) report[i] = 0ull;
     }
@@ -5326,8 +5292,8 @@ __global__ __launch_bounds__(256) void k_mcla_count(const unsigned long long* __
     if (threadIdx.x == 0 && n_set) atomicAdd(&tail[1], (unsigned long long)n_set);
 }
 
-// k_mcl_resample with N_out offspring of N particles: N from report word 16 (this launch writes *n_out, which may be *n_in),
-// N_out from the table at kbins.  W == 0: a_j = j mod N, first offspring where j < N.
+// k_mcl_resample's pieces with N_out offspring of N particles: N from report word 16 (this launch writes *n_out, which may be
+// *n_in), N_out from the table at kbins.  W == 0: a_j = j mod N, first offspring where j < N.
 __global__ __launch_bounds__(256) void k_mcla_resample(int n_cap, const uint32_t* __restrict__ ntab, int ntab_n, MclWork wk,
                                                        const unsigned long long* __restrict__ tail, double* __restrict__ out, int pstride,
                                                        int32_t* __restrict__ ancestor, uint32_t* __restrict__ n_out,
@@ -5345,52 +5311,18 @@ __global__ __launch_bounds__(256) void k_mcla_resample(int n_cap, const uint32_t
         report[19] = tail[0];
         *n_out = (uint32_t)N_out;
     }
-    const int nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
     unsigned long long part[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
     for (int j = blockIdx.x * 256 + threadIdx.x; j < N_out; j += gridDim.x * 256) {
         int a = j % N;
         bool first = j < N;
         if (W) {
-            const unsigned long long t = ((unsigned long long)j * W + u0) / (unsigned long long)N_out;
-            int lo = 0, hi = nb - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (t < wk.bsum[mid + 1]) hi = mid; else lo = mid + 1;
-            }
-            const unsigned long long start = wk.bsum[lo], rel = t - start;
-            const int base = lo * MCL_SCAN_BLOCK;
-            int i0 = 0, i1 = min(MCL_SCAN_BLOCK, N - base) - 1;
-            while (i0 < i1) {
-                const int mid = (i0 + i1) >> 1;
-                if (rel < wk.csum[base + mid]) i1 = mid; else i0 = mid + 1;
-            }
-            a = base + i0;
-            first = true;
-            if (j > 0) {
-                const unsigned long long tp = ((unsigned long long)(j - 1) * W + u0) / (unsigned long long)N_out;
-                first = tp < start + (i0 > 0 ? wk.csum[a - 1] : 0ull);
-            }
+            const MclAncestor an = mcl_ancestor(((unsigned long long)j * W + u0) / (unsigned long long)N_out, N, wk);
+            a = an.a;
+            first = mcl_first_offspring(j, an, W, u0, N_out, wk);
         }
-        const double x = wk.moved[(size_t)a * 3], y = wk.moved[(size_t)a * 3 + 1], th = wk.moved[(size_t)a * 3 + 2];
-        double* o = out + (size_t)j * pstride;
-        o[0] = x; o[1] = y; o[2] = th;
-        if (ancestor) ancestor[j] = a;
-        part[0] += first;
-        if (fabs(x) < 0x1p20 && fabs(y) < 0x1p20 && __builtin_isfinite(th)) {
-            part[1] += 1ull;
-            part[2] += (unsigned long long)llrint(x * 65536.0);
-            part[3] += (unsigned long long)llrint(y * 65536.0);
-            part[4] += (unsigned long long)llrint(cos(th) * 0x1p30);
-            part[5] += (unsigned long long)llrint(sin(th) * 0x1p30);
-        }
+        mcl_emit_offspring(j, a, first, wk, out, pstride, ancestor, part);
     }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const unsigned long long s = wave64_sum_u64(part[i]);
-        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&acc[i], s);
-    }
-    __syncthreads();
-    if (threadIdx.x < 6 && acc[threadIdx.x]) atomicAdd(&report[threadIdx.x == 0 ? 6 : 9 + threadIdx.x], acc[threadIdx.x]);
+    mcl_join_sums(part, acc, report);
 }
 
 // Sharded normaliser, merge half: every rank folds the gathered [world][3] partials in rank order
@@ -6218,17 +6150,20 @@ int slam2d_predict_scan(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32
     return launch_status();
 }
 
-// What slam2d_score_poses and slam2d_search_lattice ask of the lidar and of the level whose slot p_field they read.  Every
-// SLAM2D_E_BADARG of theirs comes before any SLAM2D_E_TOOLARGE, so a caller returns the former at once and the latter after
-// its own argument checks.
-static int check_scored_field(const Slam2dLidar* lidar, const Slam2dLevel* level, int p_field) {
-    if (!lidar || !level || !level->field || !level->frames || p_field < 0) return SLAM2D_E_BADARG;
-    if (lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS) return SLAM2D_E_BADARG;
-    if (!(lidar->max_range > 0.0) || !(level->step > 0.0) || !(level->cost_scale > 0.0)) return SLAM2D_E_BADARG;   // (the negated forms refuse a NaN)
+// What every call of this layer asks of the level whose slot p_field it reads (no lidar is read).  Every SLAM2D_E_BADARG comes
+// before any SLAM2D_E_TOOLARGE, so a caller returns the former at once and the latter after its own argument checks.
+static int check_level_field(const Slam2dLevel* level, int p_field) {
+    if (!level || !level->field || !level->frames || p_field < 0) return SLAM2D_E_BADARG;
+    if (!(level->step > 0.0) || !(level->cost_scale > 0.0)) return SLAM2D_E_BADARG;                  // (the negated forms refuse a NaN)
     // the field's limits as check_level has them: a cell key packs (row << 16 | column), offsets into one image stay below 2^31
     if (level->fmax <= 0 || level->fpitch < level->fmax) return SLAM2D_E_BADARG;
     if ((long long)level->fmax * level->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;
     return 0;
+}
+// The same for the calls that score a scan: the lidar's checks, all of them SLAM2D_E_BADARG, in front
+static int check_scored_field(const Slam2dLidar* lidar, const Slam2dLevel* level, int p_field) {
+    if (!lidar || lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS || !(lidar->max_range > 0.0)) return SLAM2D_E_BADARG;
+    return check_level_field(level, p_field);
 }
 
 int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose,
@@ -6263,6 +6198,14 @@ int64_t slam2d_search_lattice_work(const Slam2dLidar* lidar, int32_t nx, int32_t
     return rc ? rc : words;
 }
 
+// The launch geometry of the two lattice searches: a thread per position, a block row per hc headings.  (Heading chunks exist
+// only below SEARCH_WAVES waves of positions, at most 8192 of them: the launch stays below 2^32 threads.)
+struct SearchGrid { int positions, hc; long long blocks, rows; };
+static SearchGrid search_grid(int nx, int ny, int nth) {
+    const int positions = nx * ny, hc = search_chunk(positions, nth);
+    return SearchGrid{positions, hc, ((long long)positions + 255) / 256, cdiv(nth, hc)};
+}
+
 int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t nx, int32_t ny, int32_t nth,
                           double x0, double dx, double y0, double dy, double th0, double dth, const double* d_ranges,
                           uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out, void* stream) {
@@ -6276,16 +6219,13 @@ int slam2d_search_lattice(const Slam2dLidar* lidar, const Slam2dLevel* level, in
     if (words > 0 && !d_work) return SLAM2D_E_BADARG;
     if (rc) return rc;
     if (frc) return frc;
-    const int positions = nx * ny;
-    const int hc = search_chunk(positions, nth);
-    const long long blocks = ((long long)positions + 255) / 256, rows = cdiv(nth, hc);
-    // (heading chunks exist only below SEARCH_WAVES waves of positions, at most 8192 of them: the launch stays below 2^32 threads)
+    const SearchGrid g = search_grid(nx, ny, nth);
     hipStream_t s = (hipStream_t)stream;
     double2* E = reinterpret_cast<double2*>(d_work);
-    const long long first = positions > words / 2 ? positions : words / 2;
-    k_search_table<<<(unsigned)((first + 255) / 256), 256, 0, s>>>(*lidar, nth, th0, dth, d_ranges, E, (unsigned long long*)d_out, positions);
-    k_search_lattice<<<dim3((unsigned)blocks, (unsigned)rows), 256, 0, s>>>(*lidar, *level, p_field, nx, positions, nth, hc, x0, dx, y0, dy,
-                                                                           d_ranges, E, outside_cost, (unsigned long long*)d_out);
+    const long long first = g.positions > words / 2 ? g.positions : words / 2;
+    k_search_table<<<(unsigned)((first + 255) / 256), 256, 0, s>>>(*lidar, nth, th0, dth, d_ranges, E, (unsigned long long*)d_out, g.positions);
+    k_search_lattice<<<dim3((unsigned)g.blocks, (unsigned)g.rows), 256, 0, s>>>(*lidar, *level, p_field, nx, g.positions, nth, g.hc, x0, dx, y0, dy,
+                                                                               d_ranges, E, outside_cost, (unsigned long long*)d_out);
     return launch_status();
 }
 
@@ -6295,6 +6235,36 @@ int64_t slam2d_refine_work(int32_t N) {
     return 3ll * N;                                                               // the moved seeds; the join is on d_out itself
 }
 
+// The window of the two refinement calls (N >= 1 seeds, `items` table entries per heading: beams or points): radii to the
+// lattice, the headings per block row and the rows.  Every SLAM2D_E_BADARG comes before any SLAM2D_E_TOOLARGE.
+struct RefineWindow { RefineLattice lat; int hc; long long rows; };
+static int check_refine_window(int N, int items, int rx, int ry, int rt, double dx, double dy, double dth, const double* motion, RefineWindow* w) {
+    if (rx < 0 || ry < 0 || rt < 0) return SLAM2D_E_BADARG;
+    if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
+    for (int i = 0; motion && i < 3; ++i)
+        if (!__builtin_isfinite(motion[i])) return SLAM2D_E_BADARG;
+    const long long nx = 2ll * rx + 1, ny = 2ll * ry + 1, nth = 2ll * rt + 1;     // (each below 2^32)
+    if (nx > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny * nth > SLAM2D_REFINE_MAX_CANDIDATES)
+        return SLAM2D_E_TOOLARGE;
+    w->lat = RefineLattice{(int)nx, (int)ny, (int)nth, dx, dy, dth};
+    w->hc = refine_chunk(N, (int)nth, items);
+    w->rows = (nth + w->hc - 1) / w->hc;
+    if (N > SLAM2D_REFINE_MAX_BLOCKS || N * w->rows > SLAM2D_REFINE_MAX_BLOCKS) return SLAM2D_E_TOOLARGE;    // (256 threads each: below 2^32)
+    return 0;
+}
+// The three launches of a refinement: the move, the given search launch -- search(blocks, moved, out) -- and the winners' poses
+extern "C++" template <class Search>
+static int launch_refine(int N, const double* d_pose_in, double* d_pose_out, int pose_stride, const double* motion, const RefineWindow& w,
+                         uint64_t* d_work, uint64_t* d_out, hipStream_t s, Search search) {
+    double* moved = reinterpret_cast<double*>(d_work);
+    unsigned long long* out = (unsigned long long*)d_out;
+    k_refine_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion != nullptr, motion ? motion[0] : 0.0, motion ? motion[1] : 0.0,
+                                               motion ? motion[2] : 0.0, moved, out);
+    search((unsigned)(N * w.rows), moved, out);
+    k_refine_pose<<<cdiv(N, 256), 256, 0, s>>>(N, w.lat, moved, out, d_pose_out, pose_stride);
+    return launch_status();
+}
+
 int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose_in,
                         double* d_pose_out, int32_t pose_stride, const double* d_ranges, int32_t ranges_stride, const double motion[3],
                         int32_t rx, int32_t ry, int32_t rt, double dx, double dy, double dth, uint32_t outside_cost, uint64_t* d_work,
@@ -6302,35 +6272,15 @@ int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int3
     const int frc = check_scored_field(lidar, level, p_field);
     if (frc == SLAM2D_E_BADARG) return frc;
     if (!d_pose_in || !d_pose_out || !d_ranges || !d_out || !d_work || d_pose_in == d_pose_out) return SLAM2D_E_BADARG;
-    if (N < 1 || pose_stride < 3 || (ranges_stride != 0 && ranges_stride < lidar->beams) || rx < 0 || ry < 0 || rt < 0) return SLAM2D_E_BADARG;
-    if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
-    for (int i = 0; motion && i < 3; ++i)
-        if (!__builtin_isfinite(motion[i])) return SLAM2D_E_BADARG;
-    const long long nx = 2ll * rx + 1, ny = 2ll * ry + 1, nth = 2ll * rt + 1;     // (each below 2^32)
-    if (nx > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny * nth > SLAM2D_REFINE_MAX_CANDIDATES)
-        return SLAM2D_E_TOOLARGE;
-    const int hc = refine_chunk(N, (int)nth, lidar->beams);
-    const long long rows = (nth + hc - 1) / hc;
-    if (N > SLAM2D_REFINE_MAX_BLOCKS || N * rows > SLAM2D_REFINE_MAX_BLOCKS) return SLAM2D_E_TOOLARGE;       // (256 threads each: below 2^32)
+    if (N < 1 || pose_stride < 3 || (ranges_stride != 0 && ranges_stride < lidar->beams)) return SLAM2D_E_BADARG;
+    RefineWindow w;
+    const int wrc = check_refine_window(N, lidar->beams, rx, ry, rt, dx, dy, dth, motion, &w);
+    if (wrc) return wrc;
     if (frc) return frc;
     hipStream_t s = (hipStream_t)stream;
-    const RefineLattice lat{(int)nx, (int)ny, (int)nth, dx, dy, dth};
-    double* moved = reinterpret_cast<double*>(d_work);
-    unsigned long long* out = (unsigned long long*)d_out;
-    k_refine_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion != nullptr, motion ? motion[0] : 0.0, motion ? motion[1] : 0.0,
-                                               motion ? motion[2] : 0.0, moved, out);
-    k_refine_search<<<(unsigned)(N * rows), 256, 0, s>>>(*lidar, *level, p_field, (int)rows, hc, lat, moved, d_ranges, ranges_stride, outside_cost, out);
-    k_refine_pose<<<cdiv(N, 256), 256, 0, s>>>(N, lat, moved, out, d_pose_out, pose_stride);
-    return launch_status();
-}
-
-// What slam2d_search_points and slam2d_refine_points ask of the level: check_scored_field's level cases (no lidar is read).
-static int check_points_field(const Slam2dLevel* level, int p_field) {
-    if (!level || !level->field || !level->frames || p_field < 0) return SLAM2D_E_BADARG;
-    if (!(level->step > 0.0) || !(level->cost_scale > 0.0)) return SLAM2D_E_BADARG;                  // (the negated forms refuse a NaN)
-    if (level->fmax <= 0 || level->fpitch < level->fmax) return SLAM2D_E_BADARG;
-    if ((long long)level->fmax * level->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;
-    return 0;
+    return launch_refine(N, d_pose_in, d_pose_out, pose_stride, motion, w, d_work, d_out, s, [&](unsigned blocks, double* moved, unsigned long long* out) {
+        k_refine_search<<<blocks, 256, 0, s>>>(*lidar, *level, p_field, (int)w.rows, w.hc, w.lat, moved, d_ranges, ranges_stride, outside_cost, out);
+    });
 }
 
 // the checks slam2d_search_points and its work size share; *words: the 8-byte words of d_work (the offset table)
@@ -6351,7 +6301,7 @@ int64_t slam2d_search_points_work(int32_t M, int32_t nx, int32_t ny, int32_t nth
 int slam2d_search_points(const Slam2dLevel* level, int32_t p_field, int32_t nx, int32_t ny, int32_t nth, double x0, double dx, double y0,
                          double dy, double th0, double dth, const double* d_points, int32_t point_stride, int32_t M, uint32_t outside_cost,
                          uint64_t* d_work, uint64_t* d_out, void* stream) {
-    const int frc = check_points_field(level, p_field);
+    const int frc = check_level_field(level, p_field);
     if (frc == SLAM2D_E_BADARG) return frc;
     if (!d_points || !d_out || !d_work || point_stride < 2) return SLAM2D_E_BADARG;
     if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
@@ -6359,16 +6309,13 @@ int slam2d_search_points(const Slam2dLevel* level, int32_t p_field, int32_t nx, 
     const int rc = check_search_points(M, nx, ny, nth, &words);
     if (rc) return rc;
     if (frc) return frc;
-    const int positions = nx * ny;
-    const int hc = search_chunk(positions, nth);
-    const long long blocks = ((long long)positions + 255) / 256, rows = cdiv(nth, hc);
-    // (heading chunks exist only below SEARCH_WAVES waves of positions, at most 8192 of them: the launch stays below 2^32 threads)
+    const SearchGrid g = search_grid(nx, ny, nth);
     hipStream_t s = (hipStream_t)stream;
     double2* E = reinterpret_cast<double2*>(d_work);
-    k_points_table<<<(unsigned)(blocks > nth ? blocks : nth), 256, 0, s>>>(nth, th0, dth, d_points, point_stride, M, E, (unsigned long long*)d_out,
-                                                                            positions);
-    k_points_lattice<<<dim3((unsigned)blocks, (unsigned)rows), 256, 0, s>>>(*level, p_field, nx, positions, nth, hc, x0, dx, y0, dy, d_points,
-                                                                           point_stride, M, E, outside_cost, (unsigned long long*)d_out);
+    k_points_table<<<(unsigned)(g.blocks > nth ? g.blocks : nth), 256, 0, s>>>(nth, th0, dth, d_points, point_stride, M, E, (unsigned long long*)d_out,
+                                                                                g.positions);
+    k_points_lattice<<<dim3((unsigned)g.blocks, (unsigned)g.rows), 256, 0, s>>>(*level, p_field, nx, g.positions, nth, g.hc, x0, dx, y0, dy, d_points,
+                                                                               point_stride, M, E, outside_cost, (unsigned long long*)d_out);
     return launch_status();
 }
 
@@ -6376,31 +6323,19 @@ int slam2d_refine_points(const Slam2dLevel* level, int32_t p_field, int32_t N, c
                          const double* d_points, int32_t point_stride, int32_t M, int32_t set_stride, const double motion[3], int32_t rx,
                          int32_t ry, int32_t rt, double dx, double dy, double dth, uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out,
                          void* stream) {
-    const int frc = check_points_field(level, p_field);
+    const int frc = check_level_field(level, p_field);
     if (frc == SLAM2D_E_BADARG) return frc;
     if (!d_pose_in || !d_pose_out || !d_points || !d_out || !d_work || d_pose_in == d_pose_out) return SLAM2D_E_BADARG;
-    if (N < 1 || pose_stride < 3 || M < 1 || M > SLAM2D_MAX_POINTS || point_stride < 2 || rx < 0 || ry < 0 || rt < 0) return SLAM2D_E_BADARG;
+    if (N < 1 || pose_stride < 3 || M < 1 || M > SLAM2D_MAX_POINTS || point_stride < 2) return SLAM2D_E_BADARG;
     if (set_stride != 0 && (long long)set_stride < (long long)M * point_stride) return SLAM2D_E_BADARG;
-    if (!__builtin_isfinite(dx) || !__builtin_isfinite(dy) || !__builtin_isfinite(dth)) return SLAM2D_E_BADARG;
-    for (int i = 0; motion && i < 3; ++i)
-        if (!__builtin_isfinite(motion[i])) return SLAM2D_E_BADARG;
-    const long long nx = 2ll * rx + 1, ny = 2ll * ry + 1, nth = 2ll * rt + 1;     // (each below 2^32)
-    if (nx > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny > SLAM2D_REFINE_MAX_CANDIDATES || nx * ny * nth > SLAM2D_REFINE_MAX_CANDIDATES)
-        return SLAM2D_E_TOOLARGE;
-    const int hc = refine_chunk(N, (int)nth, M);
-    const long long rows = (nth + hc - 1) / hc;
-    if (N > SLAM2D_REFINE_MAX_BLOCKS || N * rows > SLAM2D_REFINE_MAX_BLOCKS) return SLAM2D_E_TOOLARGE;       // (256 threads each: below 2^32)
+    RefineWindow w;
+    const int wrc = check_refine_window(N, M, rx, ry, rt, dx, dy, dth, motion, &w);
+    if (wrc) return wrc;
     if (frc) return frc;
     hipStream_t s = (hipStream_t)stream;
-    const RefineLattice lat{(int)nx, (int)ny, (int)nth, dx, dy, dth};
-    double* moved = reinterpret_cast<double*>(d_work);
-    unsigned long long* out = (unsigned long long*)d_out;
-    k_refine_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion != nullptr, motion ? motion[0] : 0.0, motion ? motion[1] : 0.0,
-                                               motion ? motion[2] : 0.0, moved, out);
-    k_refine_points<<<(unsigned)(N * rows), 256, 0, s>>>(*level, p_field, (int)rows, hc, lat, moved, d_points, point_stride, M, set_stride,
-                                                         outside_cost, out);
-    k_refine_pose<<<cdiv(N, 256), 256, 0, s>>>(N, lat, moved, out, d_pose_out, pose_stride);
-    return launch_status();
+    return launch_refine(N, d_pose_in, d_pose_out, pose_stride, motion, w, d_work, d_out, s, [&](unsigned blocks, double* moved, unsigned long long* out) {
+        k_refine_points<<<blocks, 256, 0, s>>>(*level, p_field, (int)w.rows, w.hc, w.lat, moved, d_points, point_stride, M, set_stride, outside_cost, out);
+    });
 }
 
 int64_t slam2d_mcl_work(int32_t N) {
@@ -6409,19 +6344,28 @@ int64_t slam2d_mcl_work(int32_t N) {
     return mcl_work_words(N);
 }
 
+// What slam2d_mcl_step and slam2d_mcl_step_adaptive check alike, for n particles (or that capacity).  SLAM2D_E_BADARG comes
+// before SLAM2D_E_TOOLARGE -- n first, then the field's --, which a caller returns after its own argument checks.
+static int check_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int p_field, int n, const double* d_pose_in, const double* d_pose_out,
+                          int pose_stride, const double* motion, const double* amp, const double* d_ranges, const uint32_t* d_lut, int lut_n,
+                          int lut_shift, const uint64_t* d_work, const uint64_t* d_report) {
+    const int frc = check_scored_field(lidar, level, p_field);
+    if (frc == SLAM2D_E_BADARG) return frc;
+    if (!d_pose_in || !d_pose_out || !motion || !amp || !d_ranges || !d_lut || !d_work || !d_report) return SLAM2D_E_BADARG;
+    if (d_pose_in == d_pose_out || n < 1 || pose_stride < 3 || lut_n < 1 || lut_n > 65536 || lut_shift < 0 || lut_shift > 43)
+        return SLAM2D_E_BADARG;
+    for (int i = 0; i < 3; ++i)
+        if (!__builtin_isfinite(motion[i]) || !__builtin_isfinite(amp[i])) return SLAM2D_E_BADARG;
+    return n > SLAM2D_MCL_MAX_PARTICLES ? SLAM2D_E_TOOLARGE : frc;
+}
+
 int slam2d_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose_in,
                     double* d_pose_out, int32_t pose_stride, const double motion[3], const double amp[3], uint64_t seed, uint64_t scan,
                     const double* d_ranges, uint32_t outside_cost, const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
                     int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream) {
-    const int frc = check_scored_field(lidar, level, p_field);
-    if (frc == SLAM2D_E_BADARG) return frc;
-    if (!d_pose_in || !d_pose_out || !motion || !amp || !d_ranges || !d_lut || !d_work || !d_report) return SLAM2D_E_BADARG;
-    if (d_pose_in == d_pose_out || N < 1 || pose_stride < 3 || lut_n < 1 || lut_n > 65536 || lut_shift < 0 || lut_shift > 43)
-        return SLAM2D_E_BADARG;
-    for (int i = 0; i < 3; ++i)
-        if (!__builtin_isfinite(motion[i]) || !__builtin_isfinite(amp[i])) return SLAM2D_E_BADARG;
-    if (N > SLAM2D_MCL_MAX_PARTICLES) return SLAM2D_E_TOOLARGE;
-    if (frc) return frc;
+    const int rc = check_mcl_step(lidar, level, p_field, N, d_pose_in, d_pose_out, pose_stride, motion, amp, d_ranges, d_lut, lut_n, lut_shift,
+                                  d_work, d_report);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const MclWork wk = mcl_work_of(d_work, N);
     unsigned long long* report = (unsigned long long*)d_report;
@@ -6457,20 +6401,15 @@ int slam2d_mcl_step_adaptive(const Slam2dLidar* lidar, const Slam2dLevel* level,
                              const double amp[3], uint64_t seed, uint64_t scan, const double* d_ranges, uint32_t outside_cost,
                              const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift, const Slam2dMclBins* bins, const uint32_t* d_ntab,
                              int32_t ntab_n, int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream) {
-    const int frc = check_scored_field(lidar, level, p_field);
-    if (frc == SLAM2D_E_BADARG) return frc;
-    if (!d_pose_in || !d_pose_out || !motion || !amp || !d_ranges || !d_lut || !d_work || !d_report) return SLAM2D_E_BADARG;
+    const int rc = check_mcl_step(lidar, level, p_field, n_cap, d_pose_in, d_pose_out, pose_stride, motion, amp, d_ranges, d_lut, lut_n, lut_shift,
+                                  d_work, d_report);
+    if (rc == SLAM2D_E_BADARG) return rc;
     if (!d_n_in || !d_n_out || !d_ntab || ntab_n < 1 || ntab_n > 65536) return SLAM2D_E_BADARG;
-    if (d_pose_in == d_pose_out || n_cap < 1 || pose_stride < 3 || lut_n < 1 || lut_n > 65536 || lut_shift < 0 || lut_shift > 43)
-        return SLAM2D_E_BADARG;
-    for (int i = 0; i < 3; ++i)
-        if (!__builtin_isfinite(motion[i]) || !__builtin_isfinite(amp[i])) return SLAM2D_E_BADARG;
     long long n_bins = 0;
     const int brc = check_mcl_bins(bins, &n_bins);
     if (brc == SLAM2D_E_BADARG) return brc;
-    if (n_cap > SLAM2D_MCL_MAX_PARTICLES) return SLAM2D_E_TOOLARGE;
+    if (rc) return rc;
     if (brc) return brc;
-    if (frc) return frc;
     hipStream_t s = (hipStream_t)stream;
     const MclWork wk = mcl_work_of(d_work, n_cap);
     const int words = (int)mcla_bitmap_words(n_bins);                             // (at most 2^20 + 1)

@@ -153,10 +153,11 @@ def for_real(res):
 
 
 # ---- 1. equivalence ----
-@pytest.mark.parametrize("N", [1, 64, 65, K - 1, K, K + 1, 2 * K + 1])
+@pytest.mark.parametrize("N", [1, 64, 65, K - 1, K, K + 1, 2 * K + 1, 8193])
 def test_a_constant_table_at_the_capacity_is_slam2d_mcl_step(scene, N):
     """*d_n_in == n_cap and a table that returns n_cap: the poses, the ancestors and words 0-15 of slam2d_mcl_step(N = n_cap) ON
-    THE DEVICE, bit for bit; word 19 is word 6; and all of it is the yardstick's."""
+    THE DEVICE, bit for bit; word 19 is word 6; and all of it is the yardstick's.  N = 8193 is one particle beyond the scoring
+    launch's grid (MCLA_SCORE_BLOCKS blocks of four waves): its stride loop takes a second trip."""
     rng = scene["scans"][2]
     poses = cloud(scene, 2, N)
     args = (MOTIONS[3], AMP, 0xfeedfacecafebeef, (1 << 40) + N, rng)
@@ -166,6 +167,21 @@ def test_a_constant_table_at_the_capacity_is_slam2d_mcl_step(scene, N):
     assert np.array_equal(got["ancestors"], plain["ancestors"]) and np.array_equal(got["out"], plain["out"].view(np.uint64))
     assert [int(v) for v in got["report"][16:18]] == [N, N] and got["report"][19] == got["report"][6] and not got["report"][20:].any()
     same(got, expect(scene, poses, N, N, *args, ntab=[N]), f"N = {N}")
+
+
+def test_the_stride_loops_beyond_their_first_trip(scene):
+    """N = n_cap = 262144 + 257 and a constant table [N]: the second trip of every grid of MCLA_BLOCKS blocks of 256 threads and
+    the third of the reference launch's (MCLA_REF_BLOCKS).  On the device only -- the yardstick takes a minute at this size --:
+    the poses, the ancestors and words 0-15 of slam2d_mcl_step(N) bit for bit, the counts, word 19 is word 6, no padding word set."""
+    N = 1024 * 256 + 257
+    rng = scene["scans"][2]
+    poses = cloud(scene, 2, N)
+    args = (MOTIONS[3], AMP, 0xfeedfacecafebeef, (1 << 40) + N, rng)
+    plain = plain_launch(scene, poses, *args)
+    got = launch(scene, poses, N, *args, ntab=[N])
+    assert got["n_out"] == N and np.array_equal(got["report"][:16], plain["report"])
+    assert np.array_equal(got["ancestors"], plain["ancestors"]) and np.array_equal(got["out"], plain["out"].view(np.uint64))
+    assert [int(v) for v in got["report"][16:18]] == [N, N] and got["report"][19] == got["report"][6] and not got["report"][20:].any()
 
 
 # ---- 2. a live count below the capacity ----
