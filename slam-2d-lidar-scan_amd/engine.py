@@ -157,6 +157,25 @@ def _dev(a, device, dtype=None):
     return t.to(device)
 
 
+def _host(a):
+    """A tensor (downloaded) or anything array-like as a NumPy array: what every ``*_host`` decoder starts from."""
+    return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+_Double3 = C.c_double * 3
+
+
+def _triple(v):
+    """``const double[3]`` of a call -- a motion, the noise amplitudes -- from any three numbers (ctypes converts them as
+    ``float()`` does, at less than half the host time of a list of floats and an array type made per call)."""
+    return _Double3(*v)
+
+
+def _check_slot(level, p_field):
+    if not 0 <= p_field < level.P:
+        raise ValueError(f"field slot {p_field} of a level of {level.P}")
+
+
 # ----------------------------------------------------------------------------
 # Gaussian taps / analytic field floor
 # ----------------------------------------------------------------------------
@@ -291,8 +310,18 @@ def refine_offsets(r):
 
 
 def refine_host(words, radii, steps, cost_scale):
-    """``ParticleEngine.refine_host`` (no engine needed)."""
-    return ParticleEngine.refine_host(words, radii, steps, cost_scale)
+    """The words of ``refine_poses`` as a dict of host arrays [N]: ``cost`` (uint64, the winning candidate's), ``index`` (its
+    flat index: 0 is the moved seed), ``offsets`` [N, 3] (int: its signed steps in x, y and theta), ``start_cost`` (uint64,
+    the moved seed's own), ``score`` = -cost / cost_scale and ``moved`` (bool: another candidate than the seed won).  Also
+    ``ParticleEngine.refine_host``."""
+    w = np.ascontiguousarray(_host(words)).view(np.uint64).reshape(-1, _lib.REFINE_STRIDE)
+    nx, ny, nth = (2 * int(r) + 1 for r in radii)
+    index = (w[:, 0] & np.uint64((1 << 20) - 1)).astype(np.int64)
+    cost = w[:, 0] >> np.uint64(20)
+    jt, jy, jx = index // (ny * nx), index // nx % ny, index % nx
+    offsets = np.stack([refine_offsets(radii[0])[jx], refine_offsets(radii[1])[jy], refine_offsets(radii[2])[np.minimum(jt, nth - 1)]], axis=1)
+    return dict(cost=cost, index=index, offsets=offsets, start_cost=w[:, 1].copy(), score=-(cost.astype(np.float64) / cost_scale),
+                moved=index != 0)
 
 
 def mcl_report_host(words):
@@ -300,8 +329,7 @@ def mcl_report_host(words):
     above zero), ``u0``, ``in_range``, ``distinct`` (ancestors), ``best_pose`` (the best particle's moved pose), ``M`` (offspring
     that count), ``sums`` (the four signed sums) and ``mean_pose`` = (sum_x / (65536 M), sum_y / (65536 M), atan2(sum_sin,
     sum_cos)): sums of integers, the same bits on every call; NaNs when M == 0."""
-    w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
-    w = np.ascontiguousarray(w).reshape(-1).view(np.uint64)
+    w = np.ascontiguousarray(_host(words)).reshape(-1).view(np.uint64)
     if w.size != _lib.MCL_REPORT:
         raise ValueError(f"{w.size} words: want {_lib.MCL_REPORT}")
     M = int(w[10])
@@ -335,8 +363,7 @@ def mcl_adapt_report_host(words):
     """The 24 words of slam2d_mcl_step_adaptive's report as a dict: ``mcl_report_host``'s of the first sixteen, and ``n_in`` (the
     live count N the step ran over), ``n_out`` (the count it left), ``bins`` (occupied pose bins) and ``reference_distinct``
     (|A|: the distinct ancestors a resampling to N would have had)."""
-    w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
-    w = np.ascontiguousarray(w).reshape(-1).view(np.uint64)
+    w = np.ascontiguousarray(_host(words)).reshape(-1).view(np.uint64)
     if w.size != _lib.MCL_ADAPT_REPORT:
         raise ValueError(f"{w.size} words: want {_lib.MCL_ADAPT_REPORT}")
     out = mcl_report_host(w[:_lib.MCL_REPORT])
@@ -1066,8 +1093,7 @@ class SearchLevel:
     def moments_host(rows):
         """Rows of slam2d_match_moments ([P, MOMENTS_STRIDE], tensor or array) as host arrays: dict(sum_w [P], mean [P,3] -- the
         offset from the estimate in (m, m, rad) --, cov [P,3,3] symmetric, nan_count [P], best_score [P], poses [P])."""
-        r = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
-        r = r.reshape(-1, _lib.MOMENTS_STRIDE)
+        r = _host(rows).reshape(-1, _lib.MOMENTS_STRIDE)
         cov = np.empty((len(r), 3, 3))
         for k, (i, j) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
             cov[:, i, j] = cov[:, j, i] = r[:, 4 + k]
@@ -1266,7 +1292,7 @@ class ParticleEngine:
         """Rows of ``predict_scan`` as a dict of host arrays shaped like ``rows`` without its last axis: ``first`` (r_hit; +inf
         without a hit), ``far`` (r_far; -inf), ``cells`` (n_hit, int), ``hit`` (bool) and ``range`` = (first + far) / 2 where
         hit, else ``no_return`` -- lidarMaxRange unless given: the reference logs' value of a beam without return."""
-        r = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        r = _host(rows)
         first, far, cells = r[..., 0].copy(), r[..., 1].copy(), r[..., 2].astype(np.int64)
         hit = cells > 0
         rng = np.full(first.shape, float(self.lidar.max_range if no_return is None else no_return))
@@ -1278,8 +1304,7 @@ class ParticleEngine:
         build, not ``match`` -- left in slot ``p_field`` of ``level`` (include/slam2d.h, slam2d_score_poses):
         ``[N, SCORE_STRIDE]`` on the device.  ``ranges_stride`` 0: the one scan ``d_ranges[0..beams)`` for every pose; >= beams: a scan
         per pose.  One launch on the current stream; ``score_host`` unpacks the rows."""
-        if not 0 <= p_field < level.P:
-            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        _check_slot(level, p_field)
         out = torch.empty((N, _lib.SCORE_STRIDE), dtype=torch.float64, device=self.device)
         check(self.L.slam2d_score_poses(C.byref(self.lidar_c), C.byref(level.c), p_field, N, _ptr(d_pose), pose_stride,
                                         _ptr(d_ranges), ranges_stride, _ptr(out), _stream()), "slam2d_score_poses")
@@ -1290,31 +1315,44 @@ class ParticleEngine:
         """Rows of ``score_poses`` as a dict of host arrays [N]: ``score`` (the reference's score of the scan at the pose: minus
         the cost of the SET of cells its beams end in), ``cells`` (the size of that set), ``beam_score`` (the same sum over every
         beam inside the field, duplicates counted), ``inside``, ``in_range`` and ``outside`` = in_range - inside (int)."""
-        r = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
-        r = r.reshape(-1, _lib.SCORE_STRIDE)
+        r = _host(rows).reshape(-1, _lib.SCORE_STRIDE)
         inside, in_range = r[:, 3].astype(np.int64), r[:, 4].astype(np.int64)
         return dict(score=r[:, 0].copy(), cells=r[:, 1].astype(np.int64), beam_score=r[:, 2].copy(), inside=inside, in_range=in_range,
                     outside=in_range - inside)
+
+    def _scratch(self, attr, n, what):
+        """The int64 scratch kept as ``self.<attr>``, at least ``n`` words of it: ``n`` is the answer of the ``*_work`` function
+        ``what``, and below zero that function's error.  Kept while it is large enough, else allocated anew.  (No ``*_work``
+        answers 0 for arguments it accepts -- csrc/slam2d.hip --; max(n, 1) keeps the pointer off NULL all the same.)"""
+        n = int(n)
+        if n < 0:
+            check(n, what)
+        work = getattr(self, attr, None)
+        if work is None or work.numel() < n:
+            work = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+            setattr(self, attr, work)
+        return work
+
+    def _search(self, name, head, sized_by, level, p_field, lattice, source, outside_cost):
+        """The body of ``search_lattice`` and ``search_points``, the library's ``name`` and ``name``_work: the lattice, the shared
+        scratch, the output image.  ``head``: the call's arguments before the level; ``sized_by``: the work size's before the
+        lattice's counts; ``source``: the scan's or the point set's arguments."""
+        _check_slot(level, p_field)
+        lat = Lattice(*lattice)
+        work = self._scratch("_search_work", getattr(self.L, name + "_work")(sized_by, lat.nx, lat.ny, lat.nth), name + "_work")
+        out = torch.empty((lat.ny, lat.nx), dtype=torch.int64, device=self.device)
+        check(getattr(self.L, name)(*head, C.byref(level.c), p_field, lat.nx, lat.ny, lat.nth,
+                                    float(lat.x0), float(lat.dx), float(lat.y0), float(lat.dy), float(lat.th0), float(lat.dth),
+                                    *source, int(outside_cost), _ptr(work), _ptr(out), _stream()), name)
+        return out
 
     def search_lattice(self, level, p_field, lattice, d_ranges, outside_cost):
         """The best heading and its cost at every position of ``lattice`` (a ``Lattice``) for the one scan ``d_ranges[0..beams)``
         in the field that ``field_build`` left in slot ``p_field`` of ``level`` (include/slam2d.h, slam2d_search_lattice):
         ``[ny, nx]`` int64 words on the device, cost << 16 | heading.  A pose whose in-range beam ends outside the field pays
         ``outside_cost`` for it.  Two launches on the current stream; the scratch is kept and grown; ``search_host`` decodes."""
-        if not 0 <= p_field < level.P:
-            raise ValueError(f"field slot {p_field} of a level of {level.P}")
-        lat = Lattice(*lattice)
-        n = int(self.L.slam2d_search_lattice_work(C.byref(self.lidar_c), lat.nx, lat.ny, lat.nth))
-        if n < 0:
-            check(n, "slam2d_search_lattice_work")
-        work = getattr(self, "_search_work", None)
-        if work is None or work.numel() < n:
-            work = self._search_work = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
-        out = torch.empty((lat.ny, lat.nx), dtype=torch.int64, device=self.device)
-        check(self.L.slam2d_search_lattice(C.byref(self.lidar_c), C.byref(level.c), p_field, lat.nx, lat.ny, lat.nth,
-                                           float(lat.x0), float(lat.dx), float(lat.y0), float(lat.dy), float(lat.th0), float(lat.dth),
-                                           _ptr(d_ranges), int(outside_cost), _ptr(work), _ptr(out), _stream()), "slam2d_search_lattice")
-        return out
+        lidar = C.byref(self.lidar_c)
+        return self._search("slam2d_search_lattice", (lidar,), lidar, level, p_field, lattice, (_ptr(d_ranges),), outside_cost)
 
     @staticmethod
     def search_host(words, lattice, cost_scale):
@@ -1322,8 +1360,7 @@ class ParticleEngine:
         ``heading`` (int [ny, nx], its index: the lowest among equals), ``score`` = -(cost * (1 / cost_scale)), and the lattice's
         axes ``xs`` [nx], ``ys`` [ny], ``thetas`` [nth]."""
         lat = Lattice(*lattice)
-        w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
-        w = np.ascontiguousarray(w).view(np.uint64).reshape(lat.ny, lat.nx)
+        w = np.ascontiguousarray(_host(words)).view(np.uint64).reshape(lat.ny, lat.nx)
         cost = w >> np.uint64(16)
         return dict(cost=cost, heading=(w & np.uint64(0xffff)).astype(np.int64), score=-(cost.astype(np.float64) * (1.0 / cost_scale)),
                     xs=lat.xs, ys=lat.ys, thetas=lat.thetas)
@@ -1337,64 +1374,38 @@ class ParticleEngine:
         back on the device (``d_words``, or a new tensor): cost << 20 | candidate, and the moved seed's own cost.
         ``ranges_stride`` 0: the one scan ``d_ranges[0..beams)`` for every seed; >= beams: a scan per seed.  Three launches on the
         current stream, no synchronisation; the scratch is kept and grown; ``refine_host`` decodes."""
-        if not 0 <= p_field < level.P:
-            raise ValueError(f"field slot {p_field} of a level of {level.P}")
-        n = int(self.L.slam2d_refine_work(N))
-        if n < 0:
-            check(n, "slam2d_refine_work")
+        return self._refine("slam2d_refine_poses", (C.byref(self.lidar_c),), level, p_field, d_in, d_out, N, pose_stride,
+                            (_ptr(d_ranges), ranges_stride), radii, steps, outside_cost, motion, d_words)
+
+    def _refine(self, name, head, level, p_field, d_in, d_out, N, pose_stride, source, radii, steps, outside_cost, motion, d_words):
+        """The body of ``refine_poses`` and ``refine_points``, the library's ``name``: the two pose buffers, the shared scratch, the
+        words and the packing of radii, steps and motion.  ``head``: the call's arguments before the level; ``source``: the scans'
+        or the point sets' arguments."""
+        _check_slot(level, p_field)
+        work = self._scratch("_refine_work", self.L.slam2d_refine_work(N), "slam2d_refine_work")
         if d_in.numel() < (N - 1) * pose_stride + 3 or d_out.numel() < (N - 1) * pose_stride + 3:
             raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {N} poses, {pose_stride} doubles apart")
-        work = getattr(self, "_refine_work", None)
-        if work is None or work.numel() < n:
-            work = self._refine_work = torch.empty(n, dtype=torch.int64, device=self.device)
         out = torch.empty((N, _lib.REFINE_STRIDE), dtype=torch.int64, device=self.device) if d_words is None else d_words
         if out.numel() < N * _lib.REFINE_STRIDE or out.element_size() != 8:
             raise ValueError(f"d_words wants {N} x {_lib.REFINE_STRIDE} 64-bit words")
         rx, ry, rt = (int(v) for v in radii)
         dx, dy, dth = (float(v) for v in steps)
-        check(self.L.slam2d_refine_poses(C.byref(self.lidar_c), C.byref(level.c), p_field, N, _ptr(d_in), _ptr(d_out), pose_stride,
-                                         _ptr(d_ranges), ranges_stride, None if motion is None else (C.c_double * 3)(*[float(v) for v in motion]),
-                                         rx, ry, rt, dx, dy, dth, int(outside_cost), _ptr(work), _ptr(out), _stream()), "slam2d_refine_poses")
+        check(getattr(self.L, name)(*head, C.byref(level.c), p_field, N, _ptr(d_in), _ptr(d_out), pose_stride, *source,
+                                    None if motion is None else _triple(motion), rx, ry, rt, dx, dy, dth, int(outside_cost), _ptr(work), _ptr(out),
+                                    _stream()), name)
         return out
 
-    @staticmethod
-    def refine_host(words, radii, steps, cost_scale):
-        """The words of ``refine_poses`` as a dict of host arrays [N]: ``cost`` (uint64, the winning candidate's), ``index`` (its
-        flat index: 0 is the moved seed), ``offsets`` [N, 3] (int: its signed steps in x, y and theta), ``start_cost`` (uint64,
-        the moved seed's own), ``score`` = -cost / cost_scale and ``moved`` (bool: another candidate than the seed won)."""
-        w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
-        w = np.ascontiguousarray(w).view(np.uint64).reshape(-1, _lib.REFINE_STRIDE)
-        nx, ny, nth = (2 * int(r) + 1 for r in radii)
-        index = (w[:, 0] & np.uint64((1 << 20) - 1)).astype(np.int64)
-        cost = w[:, 0] >> np.uint64(20)
-        jt, jy, jx = index // (ny * nx), index // nx % ny, index % nx
-        offsets = np.stack([refine_offsets(radii[0])[jx], refine_offsets(radii[1])[jy], refine_offsets(radii[2])[np.minimum(jt, nth - 1)]], axis=1)
-        return dict(cost=cost, index=index, offsets=offsets, start_cost=w[:, 1].copy(), score=-(cost.astype(np.float64) / cost_scale),
-                    moved=index != 0)
+    refine_host = staticmethod(refine_host)
 
     def search_points(self, level, p_field, lattice, d_points, M, outside_cost, point_stride=2):
         """``search_lattice`` for a set of points in the robot's frame instead of a scan (include/slam2d.h, slam2d_search_points):
         point k is ``d_points[k * point_stride + 0..1]`` -- x forward, y to the left, metres; a row with a NaN or an infinity is
         dropped.  The same ``[ny, nx]`` int64 words, cost << 16 | heading, where a valid point that ends outside the field pays
         ``outside_cost``.  Two launches on the current stream; the scratch is kept and grown; ``search_host`` decodes."""
-        if not 0 <= p_field < level.P:
-            raise ValueError(f"field slot {p_field} of a level of {level.P}")
-        lat = Lattice(*lattice)
         M, point_stride = int(M), int(point_stride)
-        n = int(self.L.slam2d_search_points_work(M, lat.nx, lat.ny, lat.nth))
-        if n < 0:
-            check(n, "slam2d_search_points_work")
         if point_stride < 2 or d_points.numel() < (M - 1) * point_stride + 2:
             raise ValueError(f"d_points {tuple(d_points.shape)}: want {M} points, {point_stride} doubles apart")
-        work = getattr(self, "_search_work", None)
-        if work is None or work.numel() < n:
-            work = self._search_work = torch.empty(n, dtype=torch.int64, device=self.device)
-        out = torch.empty((lat.ny, lat.nx), dtype=torch.int64, device=self.device)
-        check(self.L.slam2d_search_points(C.byref(level.c), p_field, lat.nx, lat.ny, lat.nth,
-                                          float(lat.x0), float(lat.dx), float(lat.y0), float(lat.dy), float(lat.th0), float(lat.dth),
-                                          _ptr(d_points), point_stride, M, int(outside_cost), _ptr(work), _ptr(out), _stream()),
-              "slam2d_search_points")
-        return out
+        return self._search("slam2d_search_points", (), M, level, p_field, lattice, (_ptr(d_points), point_stride, M), outside_cost)
 
     def refine_points(self, level, p_field, d_in, d_out, N, pose_stride, d_points, M, set_stride, radii, steps, outside_cost, motion=None,
                       d_words=None, point_stride=2):
@@ -1402,28 +1413,11 @@ class ParticleEngine:
         ``set_stride`` 0: the one set ``d_points`` (``M`` points, ``point_stride`` doubles apart) for every seed; >= M *
         point_stride: a set per seed, that many doubles apart.  The same ``[N, 2]`` int64 words and the same winning poses in
         ``d_out``.  Three launches on the current stream, no synchronisation; ``refine_host`` decodes."""
-        if not 0 <= p_field < level.P:
-            raise ValueError(f"field slot {p_field} of a level of {level.P}")
-        n = int(self.L.slam2d_refine_work(N))
-        if n < 0:
-            check(n, "slam2d_refine_work")
         M, point_stride, set_stride = int(M), int(point_stride), int(set_stride)
-        if d_in.numel() < (N - 1) * pose_stride + 3 or d_out.numel() < (N - 1) * pose_stride + 3:
-            raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {N} poses, {pose_stride} doubles apart")
         if M < 1 or point_stride < 2 or d_points.numel() < (N - 1) * set_stride + (M - 1) * point_stride + 2:
             raise ValueError(f"d_points {tuple(d_points.shape)}: want {M} points, {point_stride} doubles apart, sets {set_stride} apart")
-        work = getattr(self, "_refine_work", None)
-        if work is None or work.numel() < n:
-            work = self._refine_work = torch.empty(n, dtype=torch.int64, device=self.device)
-        out = torch.empty((N, _lib.REFINE_STRIDE), dtype=torch.int64, device=self.device) if d_words is None else d_words
-        if out.numel() < N * _lib.REFINE_STRIDE or out.element_size() != 8:
-            raise ValueError(f"d_words wants {N} x {_lib.REFINE_STRIDE} 64-bit words")
-        rx, ry, rt = (int(v) for v in radii)
-        dx, dy, dth = (float(v) for v in steps)
-        check(self.L.slam2d_refine_points(C.byref(level.c), p_field, N, _ptr(d_in), _ptr(d_out), pose_stride, _ptr(d_points), point_stride, M,
-                                          set_stride, None if motion is None else (C.c_double * 3)(*[float(v) for v in motion]),
-                                          rx, ry, rt, dx, dy, dth, int(outside_cost), _ptr(work), _ptr(out), _stream()), "slam2d_refine_points")
-        return out
+        return self._refine("slam2d_refine_points", (), level, p_field, d_in, d_out, N, pose_stride, (_ptr(d_points), point_stride, M, set_stride),
+                            radii, steps, outside_cost, motion, d_words)
 
     def mcl_step(self, level, p_field, d_in, d_out, N, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift, d_report,
                  d_ancestor=None):
@@ -1433,24 +1427,26 @@ class ParticleEngine:
         buffer of the same row length, 3 or more doubles per pose).  ``d_lut``, ``shift``: ``weight_table`` on the device;
         ``d_report``: 16 int64 words (``mcl_report_host`` decodes them); ``d_ancestor``: None or [N] int32.  Five launches on the
         current stream, no synchronisation; the scratch is kept and grown."""
-        if not 0 <= p_field < level.P:
-            raise ValueError(f"field slot {p_field} of a level of {level.P}")
+        self._mcl("slam2d_mcl_step", "_mcl_work", self.L.slam2d_mcl_work(N), "slam2d_mcl_work", level, p_field, N, "N", _lib.MCL_REPORT, (),
+                  d_in, d_out, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift, (), d_report, d_ancestor)
+
+    def _mcl(self, name, scratch, words, what, level, p_field, n, n_name, report_words, counts, d_in, d_out, motion, amp, seed, scan, d_ranges, outside_cost,
+             d_lut, shift, sizing, d_report, d_ancestor):
+        """The body of ``mcl_step`` and ``mcl_step_adaptive``, the library's ``name``, over ``n`` poses (``n_name`` in the messages)
+        and a report of ``report_words``: the two pose buffers, the report and the ancestors, the step's own scratch
+        (``scratch``, ``words``, ``what``: ``_scratch``'s arguments) and the packing of motion, amplitudes, seed and scan.  ``counts``: the adaptive step's count
+        words, after ``n``; ``sizing``: its bins and table, after the weights'."""
+        _check_slot(level, p_field)
         stride = d_in.shape[-1] if d_in.dim() > 1 else 3
-        if (d_out.shape[-1] if d_out.dim() > 1 else 3) != stride or d_in.numel() < N * stride or d_out.numel() < N * stride:
-            raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {N} poses of one row length")
-        if d_report.numel() < _lib.MCL_REPORT or (d_ancestor is not None and d_ancestor.numel() < N):
-            raise ValueError("d_report wants 16 words, d_ancestor N")
-        n = int(self.L.slam2d_mcl_work(N))
-        if n < 0:
-            check(n, "slam2d_mcl_work")
-        work = getattr(self, "_mcl_work", None)
-        if work is None or work.numel() < n:
-            work = self._mcl_work = torch.empty(n, dtype=torch.int64, device=self.device)
-        check(self.L.slam2d_mcl_step(C.byref(self.lidar_c), C.byref(level.c), p_field, N, _ptr(d_in), _ptr(d_out), stride,
-                                     (C.c_double * 3)(*[float(v) for v in motion]), (C.c_double * 3)(*[float(v) for v in amp]),
-                                     int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff, _ptr(d_ranges), int(outside_cost),
-                                     _ptr(d_lut), d_lut.numel(), int(shift), _ptr(d_ancestor), _ptr(work), _ptr(d_report), _stream()),
-              "slam2d_mcl_step")
+        if (d_out.shape[-1] if d_out.dim() > 1 else 3) != stride or d_in.numel() < n * stride or d_out.numel() < n * stride:
+            raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {n} poses of one row length")
+        if d_report.numel() < report_words or (d_ancestor is not None and d_ancestor.numel() < n):
+            raise ValueError(f"d_report wants {report_words} words, d_ancestor {n_name}")
+        work = self._scratch(scratch, words, what)
+        check(getattr(self.L, name)(C.byref(self.lidar_c), C.byref(level.c), p_field, n, *counts, _ptr(d_in), _ptr(d_out), stride,
+                                    _triple(motion), _triple(amp), int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff,
+                                    _ptr(d_ranges), int(outside_cost), _ptr(d_lut), d_lut.numel(), int(shift), *sizing,
+                                    _ptr(d_ancestor), _ptr(work), _ptr(d_report), _stream()), name)
 
     def mcl_step_adaptive(self, level, p_field, d_in, d_out, n_cap, d_count, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift,
                           bins, d_ntab, d_report, d_ancestor=None, d_count_out=None):
@@ -1460,29 +1456,12 @@ class ParticleEngine:
         ``d_ntab`` (``kld_table`` on the device), resamples to that many poses and leaves the count in ``d_count_out`` (default:
         ``d_count`` itself).  ``d_report``: 24 int64 words (``mcl_adapt_report_host``).  Seven launches on the current stream,
         no synchronisation; the scratch is kept and grown."""
-        if not 0 <= p_field < level.P:
-            raise ValueError(f"field slot {p_field} of a level of {level.P}")
-        stride = d_in.shape[-1] if d_in.dim() > 1 else 3
-        if (d_out.shape[-1] if d_out.dim() > 1 else 3) != stride or d_in.numel() < n_cap * stride or d_out.numel() < n_cap * stride:
-            raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {n_cap} poses of one row length")
-        if d_report.numel() < _lib.MCL_ADAPT_REPORT or (d_ancestor is not None and d_ancestor.numel() < n_cap):
-            raise ValueError("d_report wants 24 words, d_ancestor n_cap")
         d_count_out = d_count if d_count_out is None else d_count_out
         if any(t.numel() < 1 or t.element_size() != 4 for t in (d_count, d_count_out)):
             raise ValueError("d_count wants one 32-bit word")
-        n = int(self.L.slam2d_mcl_adapt_work(n_cap, C.byref(bins)))
-        if n < 0:
-            check(n, "slam2d_mcl_adapt_work")
-        work = getattr(self, "_mcl_adapt_work", None)
-        if work is None or work.numel() < n:
-            work = self._mcl_adapt_work = torch.empty(n, dtype=torch.int64, device=self.device)
-        check(self.L.slam2d_mcl_step_adaptive(C.byref(self.lidar_c), C.byref(level.c), p_field, n_cap, _ptr(d_count), _ptr(d_count_out),
-                                              _ptr(d_in), _ptr(d_out), stride,
-                                              (C.c_double * 3)(*[float(v) for v in motion]), (C.c_double * 3)(*[float(v) for v in amp]),
-                                              int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff, _ptr(d_ranges), int(outside_cost),
-                                              _ptr(d_lut), d_lut.numel(), int(shift), C.byref(bins), _ptr(d_ntab), d_ntab.numel(),
-                                              _ptr(d_ancestor), _ptr(work), _ptr(d_report), _stream()),
-              "slam2d_mcl_step_adaptive")
+        self._mcl("slam2d_mcl_step_adaptive", "_mcl_adapt_work", self.L.slam2d_mcl_adapt_work(n_cap, C.byref(bins)), "slam2d_mcl_adapt_work",
+                  level, p_field, n_cap, "n_cap", _lib.MCL_ADAPT_REPORT, (_ptr(d_count), _ptr(d_count_out)), d_in, d_out, motion, amp, seed, scan,
+                  d_ranges, outside_cost, d_lut, shift, (C.byref(bins), _ptr(d_ntab), d_ntab.numel()), d_report, d_ancestor)
 
     def grid_update(self, d_pose, stride, d_ranges, d_beam_shift=None):
         self._before_update()

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .engine import kld_table, mcl_adapt_report_host, mcl_report_host, pinned_stream, refine_host, weight_table
-from .matcher import check_stages, covering_window
+from .matcher import check_stages, covering_window, points_of, ranges_of
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 _MASK = np.uint64(0xffffffff)
@@ -57,15 +57,26 @@ def odometry_motion(prev, cur):
     return c * dx + s * dy, c * dy - s * dx, float(t1) - float(t0)
 
 
-def _ranges_of(reading_or_ranges, beams):
-    rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
-    rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
-    if rng.shape != (beams,):
-        raise ValueError(f"ranges of shape {rng.shape}: want ({beams},)")
-    return rng
+class _OnCover:
+    """What ``Localiser`` and ``Tracker`` start from: the covering field of a window, built ONCE in a level of the object's own."""
+
+    def _plan_cover(self, matcher, window, level, likelihood, outside_cost):
+        """The window, the level and the outside cost; nothing is built yet.  Returns the level."""
+        self.matcher = matcher
+        self.window = covering_window(None, window)
+        lv = self.level = matcher.covering_level(level, self.window[2], shared=False, likelihood=likelihood)
+        self.outside_cost = matcher.outside_cost_of(lv) if outside_cost is None else int(outside_cost)
+        return lv
+
+    def _build_cover(self):
+        """The level's field (``ScanMatcher._cover``) and its fault bits.  Returns the engine's device."""
+        with self.matcher._cover(self.level, *self.window[:2]) as (eng, _):
+            self.eng = eng
+            eng.take_flags()
+        return eng.device
 
 
-class Localiser:
+class Localiser(_OnCover):
     """Monte-Carlo localisation in ``matcher``'s map, taken as static.
 
     ``window = (cx, cy, half)``: the square the robot stays in; the constructor builds the field of ``matcher``'s ``level``
@@ -89,7 +100,6 @@ class Localiser:
 
     def __init__(self, matcher, window, particles=4096, level="fine", sigma=(0.05, 0.05, 0.02), temperature=1.0, seed=0,
                  outside_cost=None, adaptive=None, likelihood=None):
-        self.matcher = matcher
         self.N = int(particles)
         if not 1 <= self.N <= _lib.MCL_MAX_PARTICLES:
             raise ValueError(f"particles wants 1 .. {_lib.MCL_MAX_PARTICLES}, not {particles!r}")
@@ -99,24 +109,17 @@ class Localiser:
         self.amp = tuple(v / _IH_STD for v in self.sigma)
         self.seed = int(seed) & 0xffffffffffffffff
         self.scan = 0                                          # the number of the next scan: part of the generator's counter
-        cx, cy, half = self.window = covering_window(None, window)
-        og = matcher.og
-        lv = self.level = matcher.covering_level(level, half, shared=False, likelihood=likelihood)
-        self.outside_cost = matcher.outside_cost_of(lv) if outside_cost is None else int(outside_cost)
-        with pinned_stream():
-            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
-            eng = self.eng = og.engine()
-            matcher.build_cover(eng, lv, cx, cy)
-            eng.take_flags()
+        lv = self._plan_cover(matcher, window, level, likelihood, outside_cost)
+        dev = self._build_cover()
         lut, self.shift = weight_table(lv.cost_scale, temperature)          # (the distance build has put its table's scale there)
-        dev = eng.device
         self.d_lut = torch.from_numpy(lut.view(np.int32)).to(dev)
         self.d_pose = [torch.zeros((self.N, 3), dtype=torch.float64, device=dev) for _ in range(2)]     # ping-pong
         self.cur = 0
         self.d_ancestor = torch.empty(self.N, dtype=torch.int32, device=dev)
         self.d_report = torch.empty(_lib.MCL_REPORT, dtype=torch.int64, device=dev)
-        self.d_ranges = torch.empty(og.numSamplesPerRev, dtype=torch.float64, device=dev)
+        self.d_ranges = torch.empty(matcher.og.numSamplesPerRev, dtype=torch.float64, device=dev)
         self.adaptive = None
+        self._decode = mcl_report_host                          # of a report, and through its length of the step, chosen once
         if adaptive is not None:
             self._init_adaptive(dict(adaptive))
 
@@ -140,6 +143,7 @@ class Localiser:
         self.d_ntab = torch.from_numpy(tab.view(np.int32)).to(dev)
         self.d_count = torch.full((1,), self.N, dtype=torch.int32, device=dev)
         self.d_report = torch.empty(_lib.MCL_ADAPT_REPORT, dtype=torch.int64, device=dev)
+        self._decode = mcl_adapt_report_host
         self.adaptive = dict(n_min=n_min, bin_xy=bin_xy, bin_theta=bin_theta, epsilon=epsilon, z=z)
 
     @property
@@ -201,16 +205,13 @@ class Localiser:
 
     # ---- the filter ----
     def _enqueue(self, d_ranges, motion, d_report):
-        eng = self.eng
+        eng, d_in, d_out = self.eng, self.d_pose[self.cur], self.d_pose[1 - self.cur]
         if self.adaptive is not None:
-            eng.mcl_step_adaptive(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], self.N, self.d_count, motion, self.amp,
-                                  self.seed, self.scan, d_ranges, self.outside_cost, self.d_lut, self.shift, self.bins, self.d_ntab, d_report,
-                                  self.d_ancestor)
-            self.cur = 1 - self.cur
-            self.scan += 1
-            return
-        eng.mcl_step(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], self.N, motion, self.amp, self.seed, self.scan,
-                     d_ranges, self.outside_cost, self.d_lut, self.shift, d_report, self.d_ancestor)
+            eng.mcl_step_adaptive(self.level, 0, d_in, d_out, self.N, self.d_count, motion, self.amp, self.seed, self.scan, d_ranges,
+                                  self.outside_cost, self.d_lut, self.shift, self.bins, self.d_ntab, d_report, self.d_ancestor)
+        else:
+            eng.mcl_step(self.level, 0, d_in, d_out, self.N, motion, self.amp, self.seed, self.scan, d_ranges, self.outside_cost, self.d_lut,
+                         self.shift, d_report, self.d_ancestor)
         self.cur = 1 - self.cur
         self.scan += 1
 
@@ -218,9 +219,9 @@ class Localiser:
         """One scan: the set moved by ``motion`` = (dfwd, dside, dturn) in the robot's own previous frame, weighed against the scan
         and resampled.  One call, one download of 128 bytes: the report as ``engine.mcl_report_host`` decodes it --
         ``mean_pose`` is the estimate (192 bytes and ``engine.mcl_adapt_report_host`` with ``adaptive``)."""
-        self.d_ranges.copy_(torch.from_numpy(_ranges_of(reading_or_ranges, self.d_ranges.numel())))
+        self.d_ranges.copy_(torch.from_numpy(ranges_of(reading_or_ranges, self.d_ranges.numel())))
         self._enqueue(self.d_ranges, motion, self.d_report)
-        return mcl_report_host(self.d_report) if self.adaptive is None else mcl_adapt_report_host(self.d_report)
+        return self._decode(self.d_report)
 
     def run(self, readings):
         """A log: the motion of scan i is the step from raw odometry pose i - 1 to i in the frame of pose i - 1 (nothing for the
@@ -228,21 +229,20 @@ class Localiser:
         ``adaptive``, whose count goes from call to call on the device), and ONE download ends the call.  Returns the list of
         decoded reports."""
         beams = self.d_ranges.numel()
-        rng = np.stack([_ranges_of(r, beams) for r in readings])
+        rng = np.stack([ranges_of(r, beams) for r in readings])
         with pinned_stream():
             d_rng = torch.from_numpy(rng).to(self.eng.device)
-            words = _lib.MCL_REPORT if self.adaptive is None else _lib.MCL_ADAPT_REPORT
-            d_rep = torch.empty((len(readings), words), dtype=torch.int64, device=self.eng.device)
+            d_rep = torch.empty((len(readings), self.d_report.numel()), dtype=torch.int64, device=self.eng.device)
             for i in range(len(readings)):
                 self._enqueue(d_rng[i], odometry_motion(readings[i - 1], readings[i]) if i else (0.0, 0.0, 0.0), d_rep[i])
             host = d_rep.cpu().numpy()
-        return [mcl_report_host(row) if self.adaptive is None else mcl_adapt_report_host(row) for row in host]
+        return [self._decode(row) for row in host]
 
 
 TrackReport = collections.namedtuple("TrackReport", "pose cost start_cost offsets")
 
 
-class Tracker:
+class Tracker(_OnCover):
     """Position tracking in ``matcher``'s map, taken as static: ONE pose follows the robot, scan by scan -- the cheapest
     localisation, for a robot whose start is known (``ScanMatcher.searchPoses`` finds one).
 
@@ -254,21 +254,12 @@ class Tracker:
     stage.  Integer costs and rounded operations: a run is the same bits every time."""
 
     def __init__(self, matcher, window, level="fine", stages=None, likelihood=None, outside_cost=None):
-        self.matcher = matcher
-        cx, cy, half = self.window = covering_window(None, window)
-        og = matcher.og
-        lv = self.level = matcher.covering_level(level, half, shared=False, likelihood=likelihood)
+        lv = self._plan_cover(matcher, window, level, likelihood, outside_cost)
         self.stages = check_stages(stages, lv.step)
-        self.outside_cost = matcher.outside_cost_of(lv) if outside_cost is None else int(outside_cost)
-        with pinned_stream():
-            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
-            eng = self.eng = og.engine()
-            matcher.build_cover(eng, lv, cx, cy)
-            eng.take_flags()
-        dev = eng.device
+        dev = self._build_cover()
         self.d_pose = [torch.zeros(3, dtype=torch.float64, device=dev) for _ in range(2)]               # ping-pong
         self.cur = 0
-        self.d_ranges = torch.empty(og.numSamplesPerRev, dtype=torch.float64, device=dev)
+        self.d_ranges = torch.empty(matcher.og.numSamplesPerRev, dtype=torch.float64, device=dev)
         # what one step downloads: the pose, then the stages' words (as doubles' bits)
         self.d_report = torch.empty(3 + _lib.REFINE_STRIDE * len(self.stages), dtype=torch.float64, device=dev)
 
@@ -281,62 +272,54 @@ class Tracker:
         """The current pose, downloaded: (x, y, theta)."""
         return tuple(float(v) for v in self.d_pose[self.cur].cpu().numpy())
 
-    def _enqueue(self, d_ranges, motion, d_pose_out, d_words):
-        """The stages of one scan; the last one's pose also goes to ``d_pose_out`` [3], the words to ``d_words`` [stages, 2] (int64)."""
+    def _enqueue(self, refine, source, motion, d_report):
+        """The stages of one scan or one point set: ``refine`` is the engine's ``refine_poses`` or ``refine_points``, ``source`` its
+        arguments between the pose stride and the radii.  The last stage's pose also goes to the head of ``d_report`` (a row like
+        ``self.d_report``), the stages' words behind it."""
+        d_words = d_report[3:].view(torch.int64).view(len(self.stages), _lib.REFINE_STRIDE)
         for i, (radii, steps) in enumerate(self.stages):
-            self.eng.refine_poses(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], 1, 3, d_ranges, 0, radii, steps,
-                                  self.outside_cost, motion=motion if i == 0 else None, d_words=d_words[i])
+            refine(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], 1, 3, *source, radii, steps, self.outside_cost,
+                   motion=motion if i == 0 else None, d_words=d_words[i])
             self.cur = 1 - self.cur
-        d_pose_out.copy_(self.d_pose[self.cur])
+        d_report[:3].copy_(self.d_pose[self.cur])
 
-    def _report(self, pose, words):
+    def _report(self, row):
+        """A downloaded row of ``_enqueue`` as a ``TrackReport``."""
+        words = row[3:].view(np.uint64).reshape(len(self.stages), _lib.REFINE_STRIDE)
         dec = [refine_host(words[i], radii, steps, self.level.cost_scale) for i, (radii, steps) in enumerate(self.stages)]
-        return TrackReport(tuple(float(v) for v in pose), int(dec[-1]["cost"][0]), int(dec[0]["start_cost"][0]),
+        return TrackReport(tuple(float(v) for v in row[:3]), int(dec[-1]["cost"][0]), int(dec[0]["start_cost"][0]),
                            np.stack([d["offsets"][0] for d in dec]))
 
     def step(self, reading_or_ranges, motion):
         """One scan: the pose moved by ``motion`` = (dfwd, dside, dturn) in the robot's own previous frame (None: not moved), then
         refined against the scan.  One small download; returns ``TrackReport(pose, cost, start_cost, offsets)``: the new pose,
         its cost, the cost of the moved pose before the search and the stages' signed steps [stages, 3]."""
-        self.d_ranges.copy_(torch.from_numpy(_ranges_of(reading_or_ranges, self.d_ranges.numel())))
+        self.d_ranges.copy_(torch.from_numpy(ranges_of(reading_or_ranges, self.d_ranges.numel())))
         with pinned_stream():
-            self._enqueue(self.d_ranges, motion, self.d_report[:3], self.d_report[3:].view(torch.int64).view(len(self.stages), _lib.REFINE_STRIDE))
-            host = self.d_report.cpu().numpy()
-        return self._report(host[:3], host[3:].view(np.uint64).reshape(len(self.stages), _lib.REFINE_STRIDE))
+            self._enqueue(self.eng.refine_poses, (self.d_ranges, 0), motion, self.d_report)
+            return self._report(self.d_report.cpu().numpy())
 
     def step_points(self, points, motion):
         """``step`` for a set of points in the robot's frame instead of a scan (slam2d_refine_points, include/slam2d.h):
         ``points`` is ``[M, 2]`` -- x forward, y to the left, metres; rows with a NaN or an infinity are dropped --, M <=
         ``_lib.MAX_POINTS``, as the ``points`` module prepares them.  The field is the one the constructor built: a point that
         ends outside it pays ``outside_cost``.  The same stages, the same download, the same ``TrackReport``."""
-        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
-        if pts.ndim != 2 or pts.shape[1] != 2 or not 1 <= len(pts) <= _lib.MAX_POINTS:
-            raise ValueError(f"points of shape {pts.shape}: want (M, 2), 1 <= M <= {_lib.MAX_POINTS}")
-        T = len(self.stages)
+        pts = points_of(points)
         with pinned_stream():
-            d_pts = torch.from_numpy(pts).to(self.eng.device)
-            d_words = self.d_report[3:].view(torch.int64).view(T, _lib.REFINE_STRIDE)
-            for i, (radii, steps) in enumerate(self.stages):
-                self.eng.refine_points(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], 1, 3, d_pts, len(pts), 0, radii, steps,
-                                       self.outside_cost, motion=motion if i == 0 else None, d_words=d_words[i])
-                self.cur = 1 - self.cur
-            self.d_report[:3].copy_(self.d_pose[self.cur])
-            host = self.d_report.cpu().numpy()
-        return self._report(host[:3], host[3:].view(np.uint64).reshape(T, _lib.REFINE_STRIDE))
+            self._enqueue(self.eng.refine_points, (torch.from_numpy(pts).to(self.eng.device), len(pts), 0), motion, self.d_report)
+            return self._report(self.d_report.cpu().numpy())
 
     def run(self, readings):
         """A log, as ``Localiser.run`` takes it: the motion of scan i is the step from raw odometry pose i - 1 to i in the frame of
         pose i - 1 (nothing for the first scan).  Every scan is enqueued without a synchronisation; ONE download of the [S, 3]
         poses and the [S, stages, 2] words ends the call.  Returns the list of ``TrackReport``s."""
         beams = self.d_ranges.numel()
-        rng = np.stack([_ranges_of(r, beams) for r in readings])
-        S, T = len(readings), len(self.stages)
+        rng = np.stack([ranges_of(r, beams) for r in readings])
         with pinned_stream():
             dev = self.eng.device
             d_rng = torch.from_numpy(rng).to(dev)
-            d_rep = torch.empty((S, 3 + _lib.REFINE_STRIDE * T), dtype=torch.float64, device=dev)
-            for i in range(S):
-                self._enqueue(d_rng[i], odometry_motion(readings[i - 1], readings[i]) if i else None, d_rep[i, :3],
-                              d_rep[i, 3:].view(torch.int64).view(T, _lib.REFINE_STRIDE))
+            d_rep = torch.empty((len(readings), self.d_report.numel()), dtype=torch.float64, device=dev)
+            for i in range(len(readings)):
+                self._enqueue(self.eng.refine_poses, (d_rng[i], 0), odometry_motion(readings[i - 1], readings[i]) if i else None, d_rep[i])
             host = d_rep.cpu().numpy()
-        return [self._report(row[:3], row[3:].view(np.uint64).reshape(T, _lib.REFINE_STRIDE)) for row in host]
+        return [self._report(row) for row in host]

@@ -7,6 +7,7 @@ before its next statement).  The batched, all-particles path is
 ``filter.ParticleFilter``.
 """
 import collections
+import contextlib
 import copy
 import math
 
@@ -86,6 +87,30 @@ def _shared_level(og, key_extra, **kw):
     if key not in _level_cache:
         _level_cache[key] = SearchLevel(og.lidar, 1, og.device, bnb=False, **kw)     # whole cubes: brute-force sweep
     return _level_cache[key]
+
+
+# ---- what the localisation calls take: a scan, or a set of points ----
+def ranges_of(reading_or_ranges, beams, N=None):
+    """A reading dict or its ranges as a contiguous float64 array: ``[beams]``, or -- with ``N`` -- also ``[N, beams]``, a scan per
+    pose; ValueError otherwise."""
+    rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
+    rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
+    if N is None and rng.shape != (beams,):
+        raise ValueError(f"ranges of shape {rng.shape}: want ({beams},)")
+    if N is not None and rng.shape not in ((beams,), (N, beams)):
+        raise ValueError(f"ranges of shape {rng.shape}: want ({beams},) or ({N}, {beams})")
+    return rng
+
+
+def points_of(points, N=None):
+    """A point set as a contiguous float64 array: ``[M, 2]``, or -- with ``N`` -- also ``[N, M, 2]``, a set per pose, 1 <= M <=
+    ``_lib.MAX_POINTS``; ValueError otherwise."""
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+    if N is None and (pts.ndim != 2 or pts.shape[1] != 2 or not 1 <= len(pts) <= _lib.MAX_POINTS):
+        raise ValueError(f"points of shape {pts.shape}: want (M, 2), 1 <= M <= {_lib.MAX_POINTS}")
+    if N is not None and (pts.ndim not in (2, 3) or pts.shape[-1] != 2 or not 1 <= pts.shape[-2] <= _lib.MAX_POINTS or (pts.ndim == 3 and len(pts) != N)):
+        raise ValueError(f"points of shape {pts.shape}: want (M, 2) or ({N}, M, 2), 1 <= M <= {_lib.MAX_POINTS}")
+    return pts
 
 
 # ---- the covering level of ScanMatcher.scorePoses, planned on the host ----
@@ -426,6 +451,31 @@ class ScanMatcher:
         table = getattr(lv, "distance_table", None)
         return int(encode_cost(lv.floor_value, lv.cost_scale)) if table is None else int(table[0][-1])
 
+    @contextlib.contextmanager
+    def _cover(self, lv, cx, cy, dist2=False):
+        """The prologue of every call on a covering level, with the level to itself and the stream pinned: the map grown to hold
+        the level's frame around (cx, cy), the grid's engine, the field built there.  Yields (engine, what ``build_cover``
+        returned)."""
+        with _Exclusive(lv), pinned_stream():
+            self.og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
+            eng = self.og.engine()
+            yield eng, self.build_cover(eng, lv, cx, cy, dist2=dist2)
+
+    def _download(self, eng, name, *tensors):
+        """The epilogue of the public call ``name``: its float64 or int64 result ``tensors`` and the build's fault word in ONE
+        download -- as the 64-bit words they are, so rows and images arrive bit for bit --, the word cleared on the device if
+        any bit is set, ``Slam2dError`` on a fatal one, else ``last_flags``.  Returns the tensors as host arrays."""
+        words = [t.reshape(-1) if t.dtype == torch.int64 else t.reshape(-1).view(torch.int64) for t in tensors]
+        host = torch.cat(words + [eng.flags[:1].to(torch.int64)]).cpu().numpy()
+        bits = int(host[-1]) & 0xffffffff
+        if bits:
+            eng.flags.zero_()
+            if bits & _lib.FATAL_FLAGS:
+                raise _lib.Slam2dError(f"{name}: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
+        self.last_flags = bits
+        ends = np.cumsum([t.numel() for t in tensors])
+        return [host[e - t.numel():e].view(np.float64 if t.dtype == torch.float64 else np.int64).reshape(tuple(t.shape)) for t, e in zip(tensors, ends)]
+
     def clearance(self, window, level="fine", max_dist=None):
         """How far every cell of the covering frame of ``window = (cx, cy, half)`` is from a wall: ``dict(dist, xs, ys)`` with
         ``dist`` [fh, fw] in metres -- sqrt(k) * step, k the squared distance in cells to the nearest occupied field cell of
@@ -434,11 +484,7 @@ class ScanMatcher:
         without a wall.  Cells outside the frame are unknown, not walls."""
         cx, cy, half = covering_window(None, window)
         lv = self._covering_level(level, half, True, lambda step: clearance_table_of(max_dist, step))
-        with _Exclusive(lv), pinned_stream():
-            og = self.og
-            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
-            eng = og.engine()
-            d2 = self.build_cover(eng, lv, cx, cy, dist2=True)
+        with self._cover(lv, cx, cy, dist2=True) as (eng, d2):
             bits = int(eng.take_flags()[0])
             self.last_flags = bits
             fr = lv.frames()[0]
@@ -460,31 +506,17 @@ class ScanMatcher:
         ``likelihood``: score against the likelihood field of ``covering_level`` instead of the blurred one.
         ValueError naming ``window`` when the frame is beyond what the field build accepts."""
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
-        rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
-        rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
         N, B = len(poses), self.og.numSamplesPerRev
         if N == 0:
             raise ValueError("no poses")
-        if rng.shape not in ((B,), (N, B)):
-            raise ValueError(f"ranges of shape {rng.shape}: want ({B},) or ({N}, {B})")
+        rng = ranges_of(reading_or_ranges, B, N)
         cx, cy, half = covering_window(poses, window)
         lv = self.covering_level(level, half, likelihood=likelihood)
-        with _Exclusive(lv), pinned_stream():
-            og = self.og
-            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
-            eng = og.engine()
-            self.build_cover(eng, lv, cx, cy)
+        with self._cover(lv, cx, cy) as (eng, _):
             rows = eng.score_poses(lv, 0, eng.to_device(poses), 3, N, eng.to_device(rng), 0 if rng.ndim == 1 else B)
-            # one download: the rows and the build's fault word
-            host = torch.cat([rows.reshape(-1), eng.flags[:1].to(torch.float64)]).cpu().numpy()
-            bits = int(host[-1])
-            if bits:
-                eng.flags.zero_()
-                if bits & _lib.FATAL_FLAGS:
-                    raise _lib.Slam2dError(f"scorePoses: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
-            self.last_flags = bits
+            host, = self._download(eng, "scorePoses", rows)
             self.last_cover = dict(level=lv, window=(cx, cy, half))
-            return eng.score_host(host[:-1])
+            return eng.score_host(host)
 
     def searchPoses(self, reading_or_ranges, window, step=None, headings=120, level="fine", top=5, separation=None, outside_cost=None,
                     likelihood=None):
@@ -499,32 +531,24 @@ class ScanMatcher:
         ``peaks``: up to ``top`` ``Peak(x, y, theta, score, cost)``, lowest cost first, no two within ``separation`` metres
         (default: ten lattice steps) of each other on either axis (``lattice_peaks``).  ``self.last_cover`` keeps the level,
         its window and the ``Lattice``."""
-        rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
-        rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
-        if rng.shape != (self.og.numSamplesPerRev,):
-            raise ValueError(f"ranges of shape {rng.shape}: want ({self.og.numSamplesPerRev},)")
-        cx, cy, half = covering_window(None, window)
-        lv = self.covering_level(level, half, likelihood=likelihood)
-        lat = window_lattice((cx, cy, half), lv.step if step is None else step, headings)
+        rng = ranges_of(reading_or_ranges, self.og.numSamplesPerRev)
+        window = covering_window(None, window)
+        lv = self.covering_level(level, window[2], likelihood=likelihood)
+        return self._search("searchPoses", lv, window, step, headings, top, separation, outside_cost,
+                            lambda eng, lat, cost: eng.search_lattice(lv, 0, lat, eng.to_device(rng), cost))
+
+    def _search(self, name, lv, window, step, headings, top, separation, outside_cost, launch):
+        """The body of ``searchPoses`` and ``searchPoints`` in the covering level ``lv`` of ``window``: the lattice, the field, the
+        search ``launch(eng, lattice, outside_cost)``, one download, the decoded image and its peaks."""
+        cx, cy, half = window
+        lat = window_lattice(window, lv.step if step is None else step, headings)
         sep = 10 if separation is None else int(round(float(separation) / lat.dx))
         if outside_cost is None:
             outside_cost = self.outside_cost_of(lv)
-        with _Exclusive(lv), pinned_stream():
-            og = self.og
-            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
-            eng = og.engine()
-            self.build_cover(eng, lv, cx, cy)
-            words = eng.search_lattice(lv, 0, lat, eng.to_device(rng), outside_cost)
-            # one download: the image and the build's fault word
-            host = torch.cat([words.reshape(-1), eng.flags[:1].to(torch.int64)]).cpu().numpy()
-            bits = int(host[-1]) & 0xffffffff
-            if bits:
-                eng.flags.zero_()
-                if bits & _lib.FATAL_FLAGS:
-                    raise _lib.Slam2dError(f"searchPoses: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
-            self.last_flags = bits
+        with self._cover(lv, cx, cy) as (eng, _):
+            host, = self._download(eng, name, launch(eng, lat, outside_cost))
             self.last_cover = dict(level=lv, window=(cx, cy, half), lattice=lat)
-            res = eng.search_host(host[:-1], lat, lv.cost_scale)
+            res = eng.search_host(host, lat, lv.cost_scale)
         res["peaks"] = [Peak(float(res["xs"][ix]), float(res["ys"][iy]), float(res["thetas"][it]), float(res["score"][iy, ix]),
                              int(res["cost"][iy, ix])) for iy, ix, it in lattice_peaks(res["cost"], res["heading"], top, sep)]
         return res
@@ -540,42 +564,36 @@ class ScanMatcher:
         the last stage's winner), ``score`` = -cost / cost_scale, ``start_cost`` (the seed's own) and ``offsets`` [N, stages, 3]
         (each stage's signed steps in x, y, theta); ``self.last_cover`` keeps the level and its window."""
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
-        rng = reading_or_ranges["range"] if isinstance(reading_or_ranges, dict) else reading_or_ranges
-        rng = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
         N, B = len(poses), self.og.numSamplesPerRev
         if N == 0:
             raise ValueError("no poses")
-        if rng.shape not in ((B,), (N, B)):
-            raise ValueError(f"ranges of shape {rng.shape}: want ({B},) or ({N}, {B})")
-        cx, cy, half = covering_window(poses, window)
-        lv = self.covering_level(level, half, likelihood=likelihood)
+        rng = ranges_of(reading_or_ranges, B, N)
+        window = covering_window(poses, window)
+        lv = self.covering_level(level, window[2], likelihood=likelihood)
+        return self._refine("refinePoses", lv, window, poses, rng, stages, outside_cost,
+                            lambda eng, a, b, d_rng, radii, steps, cost, words:
+                            eng.refine_poses(lv, 0, a, b, N, 3, d_rng, 0 if rng.ndim == 1 else B, radii, steps, cost, d_words=words))
+
+    def _refine(self, name, lv, window, poses, source, stages, outside_cost, launch):
+        """The body of ``refinePoses`` and ``refinePoints`` in the covering level ``lv`` of ``window``: the field, the stages in
+        turn -- ``launch(eng, d_in, d_out, d_source, radii, steps, outside_cost, d_words)``, ``source`` the scans or the point sets
+        --, one download, the decoded words."""
+        cx, cy, half = window
+        N = len(poses)
         stages = check_stages(stages, lv.step)
         if outside_cost is None:
             outside_cost = self.outside_cost_of(lv)
-        with _Exclusive(lv), pinned_stream():
-            og = self.og
-            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
-            eng = og.engine()
-            self.build_cover(eng, lv, cx, cy)
+        with self._cover(lv, cx, cy) as (eng, _):
             d_pose = [eng.to_device(poses), torch.empty((N, 3), dtype=torch.float64, device=eng.device)]
-            d_rng = eng.to_device(rng)
+            d_source = eng.to_device(source)
             words = torch.empty((len(stages), N, _lib.REFINE_STRIDE), dtype=torch.int64, device=eng.device)
             for i, (radii, steps) in enumerate(stages):
-                eng.refine_poses(lv, 0, d_pose[i & 1], d_pose[1 - (i & 1)], N, 3, d_rng, 0 if rng.ndim == 1 else B, radii, steps, outside_cost,
-                                 d_words=words[i])
+                launch(eng, d_pose[i & 1], d_pose[1 - (i & 1)], d_source, radii, steps, outside_cost, words[i])
             # one download: the poses, the stages' words and the build's fault word
-            host = torch.cat([d_pose[len(stages) & 1].reshape(-1), words.reshape(-1).view(torch.float64),
-                              eng.flags[:1].to(torch.float64)]).cpu().numpy()
-            bits = int(host[-1])
-            if bits:
-                eng.flags.zero_()
-                if bits & _lib.FATAL_FLAGS:
-                    raise _lib.Slam2dError(f"refinePoses: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
-            self.last_flags = bits
+            best, w = self._download(eng, name, d_pose[len(stages) & 1], words)
             self.last_cover = dict(level=lv, window=(cx, cy, half), stages=stages)
-        w = host[3 * N:-1].view(np.uint64).reshape(len(stages), N, _lib.REFINE_STRIDE)
         dec = [ParticleEngine.refine_host(w[i], radii, steps, lv.cost_scale) for i, (radii, steps) in enumerate(stages)]
-        return dict(poses=host[:3 * N].reshape(N, 3).copy(), cost=dec[-1]["cost"], score=dec[-1]["score"], start_cost=dec[0]["start_cost"],
+        return dict(poses=best.copy(), cost=dec[-1]["cost"], score=dec[-1]["score"], start_cost=dec[0]["start_cost"],
                     offsets=np.stack([d["offsets"] for d in dec], axis=1))
 
     def points_level(self, level, half, points, likelihood=None, shared=True):
@@ -598,34 +616,11 @@ class ScanMatcher:
         ``_lib.MAX_POINTS``: several scans joined by odometry (``points.merge_scans``), two sensors, a sensor off the robot's
         origin, a driver's own beam angles (``points.polar_points``).  The same lattice, cost, peaks and return value; the
         field is ``points_level``'s.  ``self.last_cover`` keeps the level, its window and the ``Lattice``."""
-        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
-        if pts.ndim != 2 or pts.shape[1] != 2 or not 1 <= len(pts) <= _lib.MAX_POINTS:
-            raise ValueError(f"points of shape {pts.shape}: want (M, 2), 1 <= M <= {_lib.MAX_POINTS}")
-        cx, cy, half = covering_window(None, window)
-        lv = self.points_level(level, half, pts, likelihood)
-        lat = window_lattice((cx, cy, half), lv.step if step is None else step, headings)
-        sep = 10 if separation is None else int(round(float(separation) / lat.dx))
-        if outside_cost is None:
-            outside_cost = self.outside_cost_of(lv)
-        with _Exclusive(lv), pinned_stream():
-            og = self.og
-            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
-            eng = og.engine()
-            self.build_cover(eng, lv, cx, cy)
-            words = eng.search_points(lv, 0, lat, eng.to_device(pts), len(pts), outside_cost)
-            # one download: the image and the build's fault word
-            host = torch.cat([words.reshape(-1), eng.flags[:1].to(torch.int64)]).cpu().numpy()
-            bits = int(host[-1]) & 0xffffffff
-            if bits:
-                eng.flags.zero_()
-                if bits & _lib.FATAL_FLAGS:
-                    raise _lib.Slam2dError(f"searchPoints: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
-            self.last_flags = bits
-            self.last_cover = dict(level=lv, window=(cx, cy, half), lattice=lat)
-            res = eng.search_host(host[:-1], lat, lv.cost_scale)
-        res["peaks"] = [Peak(float(res["xs"][ix]), float(res["ys"][iy]), float(res["thetas"][it]), float(res["score"][iy, ix]),
-                             int(res["cost"][iy, ix])) for iy, ix, it in lattice_peaks(res["cost"], res["heading"], top, sep)]
-        return res
+        pts = points_of(points)
+        window = covering_window(None, window)
+        lv = self.points_level(level, window[2], pts, likelihood)
+        return self._search("searchPoints", lv, window, step, headings, top, separation, outside_cost,
+                            lambda eng, lat, cost: eng.search_points(lv, 0, lat, eng.to_device(pts), len(pts), cost))
 
     def refinePoints(self, poses, points, stages=None, level="fine", window=None, likelihood=None, outside_cost=None):
         """``refinePoses`` for a set of points in the robot's frame instead of a scan (include/slam2d.h, slam2d_refine_points):
@@ -633,43 +628,16 @@ class ScanMatcher:
         dropped, so sets of different sizes are padded with NaN rows).  The same stages, frame planning and return value; the
         field is ``points_level``'s."""
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
-        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
         N = len(poses)
         if N == 0:
             raise ValueError("no poses")
-        if pts.ndim not in (2, 3) or pts.shape[-1] != 2 or not 1 <= pts.shape[-2] <= _lib.MAX_POINTS or (pts.ndim == 3 and len(pts) != N):
-            raise ValueError(f"points of shape {pts.shape}: want (M, 2) or ({N}, M, 2), 1 <= M <= {_lib.MAX_POINTS}")
+        pts = points_of(points, N)
         M = pts.shape[-2]
-        cx, cy, half = covering_window(poses, window)
-        lv = self.points_level(level, half, pts, likelihood)
-        stages = check_stages(stages, lv.step)
-        if outside_cost is None:
-            outside_cost = self.outside_cost_of(lv)
-        with _Exclusive(lv), pinned_stream():
-            og = self.og
-            og.checkAndExapndOG([cx - lv.reach, cx + lv.reach], [cy - lv.reach, cy + lv.reach])      # :27
-            eng = og.engine()
-            self.build_cover(eng, lv, cx, cy)
-            d_pose = [eng.to_device(poses), torch.empty((N, 3), dtype=torch.float64, device=eng.device)]
-            d_pts = eng.to_device(pts)
-            words = torch.empty((len(stages), N, _lib.REFINE_STRIDE), dtype=torch.int64, device=eng.device)
-            for i, (radii, steps) in enumerate(stages):
-                eng.refine_points(lv, 0, d_pose[i & 1], d_pose[1 - (i & 1)], N, 3, d_pts, M, 0 if pts.ndim == 2 else 2 * M, radii, steps,
-                                  outside_cost, d_words=words[i])
-            # one download: the poses, the stages' words and the build's fault word
-            host = torch.cat([d_pose[len(stages) & 1].reshape(-1), words.reshape(-1).view(torch.float64),
-                              eng.flags[:1].to(torch.float64)]).cpu().numpy()
-            bits = int(host[-1])
-            if bits:
-                eng.flags.zero_()
-                if bits & _lib.FATAL_FLAGS:
-                    raise _lib.Slam2dError(f"refinePoints: {_lib.describe_flags(bits & _lib.FATAL_FLAGS)}")
-            self.last_flags = bits
-            self.last_cover = dict(level=lv, window=(cx, cy, half), stages=stages)
-        w = host[3 * N:-1].view(np.uint64).reshape(len(stages), N, _lib.REFINE_STRIDE)
-        dec = [ParticleEngine.refine_host(w[i], radii, steps, lv.cost_scale) for i, (radii, steps) in enumerate(stages)]
-        return dict(poses=host[:3 * N].reshape(N, 3).copy(), cost=dec[-1]["cost"], score=dec[-1]["score"], start_cost=dec[0]["start_cost"],
-                    offsets=np.stack([d["offsets"] for d in dec], axis=1))
+        window = covering_window(poses, window)
+        lv = self.points_level(level, window[2], pts, likelihood)
+        return self._refine("refinePoints", lv, window, poses, pts, stages, outside_cost,
+                            lambda eng, a, b, d_pts, radii, steps, cost, words:
+                            eng.refine_points(lv, 0, a, b, N, 3, d_pts, M, 0 if pts.ndim == 2 else 2 * M, radii, steps, cost, d_words=words))
 
     def searchToMatch(self, probSP, estimatedX, estimatedY, estimatedTheta, rMeasure, xRangeList, yRangeList,
                       searchRadius, searchHalfRad, unitLength, estMovingDist, estMovingTheta, fineSearch=False,
