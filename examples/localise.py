@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Monte-Carlo localisation in a finished map with Localiser: follow the robot scan by scan, the hypotheses never leaving the device.
 
-    python examples/localise.py [--scans 40] [--particles 4096] [--temperature 64] [--level fine] [--adaptive] [--likelihood [SIGMA]] [--track]
+    python examples/localise.py [--scans 40] [--particles 4096] [--temperature 64] [--level fine] [--adaptive] [--likelihood [SIGMA]] [--track] [--merge K]
 
 Maps a seeded walk through a synthetic world at its true poses (map_from_poses), then forgets the poses: the first scan is
 searched for in the whole window (ScanMatcher.searchPoses), the particle set is seeded around the search's peaks
@@ -21,6 +21,10 @@ hypothesis half a metre off then still pays less than one across the building.
 
 --track follows the same log once more with a Tracker: ONE pose on the device, from the search's best peak, moved by the odometry
 increment and refined by a local search per scan (slam2d_refine_poses); its error is printed beside the filter's.
+
+--merge K follows the same log once more with a second filter of the same seed that is given POINTS instead of scans: per step
+the last K scans joined through their odometry (points.merge_scans) -- Localiser.run_points, slam2d_mcl_step_points -- and
+prints the same table beside the scan run's.
 """
 import argparse
 import importlib
@@ -68,36 +72,56 @@ def main():
     ap.add_argument("--likelihood", type=float, nargs="?", const=0.2, default=None, metavar="SIGMA",
                     help="weigh against the likelihood field of this sigma in metres (default 0.2) instead of the blurred field")
     ap.add_argument("--track", action="store_true", help="also follow the log with a Tracker -- one pose -- from the search's best peak")
+    ap.add_argument("--merge", type=int, default=0, metavar="K",
+                    help="also follow the log with the last K scans of every step merged into one point set (Localiser.run_points)")
     args = ap.parse_args()
     if args.track and args.adaptive:
         ap.error("--track starts from the search's best peak: not with --adaptive")
+    if args.merge < 0:
+        ap.error("--merge wants a number of scans, 1 or more")
     likelihood = None if args.likelihood is None else dict(sigma=args.likelihood)
     pkg = importlib.import_module("slam-2d-lidar-scan_amd")
     true, log, grid, window = synthetic(args.scans)
     og = pkg.map_from_poses(true, **grid)
     sm = pkg.ScanMatcher(og, *SM_PARAMS)
-    if args.adaptive:
-        loc = pkg.Localiser(sm, window, particles=args.particles, level=args.level, sigma=(0.03, 0.03, 0.02), temperature=args.temperature, seed=1,
-                            adaptive={}, likelihood=likelihood)
-        loc.seed_uniform()
-    else:
+    if not args.adaptive:
         found = sm.searchPoses(log[0], window, headings=120, level=args.level, top=4, likelihood=likelihood)
         for q in found["peaks"]:
             print(f"search peak ({q.x:7.2f}, {q.y:7.2f}, {q.theta:6.3f}) score {q.score:9.2f}")
+
+    def seeded():
+        """A filter of seed 1 on the window, lost (--adaptive) or around the search's peaks: the same set every time."""
         loc = pkg.Localiser(sm, window, particles=args.particles, level=args.level, sigma=(0.03, 0.03, 0.02), temperature=args.temperature, seed=1,
-                            likelihood=likelihood)
-        loc.seed_from_peaks(found["peaks"], (0.1, 0.1, 0.05))
+                            adaptive={} if args.adaptive else None, likelihood=likelihood)
+        if args.adaptive:
+            loc.seed_uniform()
+        else:
+            loc.seed_from_peaks(found["peaks"], (0.1, 0.1, 0.05))
+        return loc
+
+    def table(reports, dt, what):
+        for r, rep in zip(true, reports):
+            x, y, th = rep["mean_pose"]
+            dth = (th - r["theta"] + math.pi) % (2 * math.pi) - math.pi
+            print(f"true ({r['x']:7.2f}, {r['y']:7.2f}, {r['theta']:6.3f})  mean ({x:7.2f}, {y:7.2f}, {th:6.3f})  off by "
+                  f"{math.hypot(x - r['x'], y - r['y']):.3f} m, {abs(dth):.3f} rad  {rep['distinct']:5d} distinct ancestors of "
+                  f"{rep.get('n_out', args.particles)}, {rep['positive']:5d} weights above zero"
+                  + (f"  count {rep['n_in']:7d} -> {rep['n_out']:7d} ({rep['bins']} bins)" if args.adaptive else ""))
+        print(f"{len(log)} {what}, {args.particles} particles: {1e3 * dt / len(log):.3f} ms per step, upload and the one download included")
+
     t0 = time.perf_counter()
-    reports = loc.run(log)
-    dt = time.perf_counter() - t0
-    for r, rep in zip(true, reports):
-        x, y, th = rep["mean_pose"]
-        dth = (th - r["theta"] + math.pi) % (2 * math.pi) - math.pi
-        print(f"true ({r['x']:7.2f}, {r['y']:7.2f}, {r['theta']:6.3f})  mean ({x:7.2f}, {y:7.2f}, {th:6.3f})  off by "
-              f"{math.hypot(x - r['x'], y - r['y']):.3f} m, {abs(dth):.3f} rad  {rep['distinct']:5d} distinct ancestors of {rep.get('n_out', args.particles)}, "
-              f"{rep['positive']:5d} weights above zero"
-              + (f"  count {rep['n_in']:7d} -> {rep['n_out']:7d} ({rep['bins']} bins)" if args.adaptive else ""))
-    print(f"{len(log)} scans, {args.particles} particles: {1e3 * dt / len(log):.3f} ms per scan, upload and the one download included")
+    reports = seeded().run(log)
+    table(reports, time.perf_counter() - t0, "scans")
+    if args.merge:
+        # the same log as points: per step the last K scans joined through the odometry, in the frame of the last one
+        points = importlib.import_module("slam-2d-lidar-scan_amd.points")
+        localise = importlib.import_module("slam-2d-lidar-scan_amd.localise")
+        sets = [points.merge_scans(log[max(0, i + 1 - args.merge):i + 1], fov=grid["lidarFOV"], max_range=grid["lidarMaxRange"])[0]
+                for i in range(len(log))]
+        motions = [localise.odometry_motion(log[i - 1], log[i]) if i else (0.0, 0.0, 0.0) for i in range(len(log))]
+        t0 = time.perf_counter()
+        merged = seeded().run_points(sets, motions)
+        table(merged, time.perf_counter() - t0, f"sets of up to {max(len(q) for q in sets)} points ({args.merge} scans each)")
     if args.track:
         # position tracking with ONE pose (Tracker, slam2d_refine_poses): from the search's best peak, refined on the first scan
         tr = pkg.Tracker(sm, window, level=args.level, likelihood=likelihood)

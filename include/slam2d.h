@@ -642,7 +642,8 @@ int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int3
  * SLAM2D_REFINE_MAX_CANDIDATES or more than SLAM2D_REFINE_MAX_BLOCKS blocks -- N * ceil(nth / hc), hc = min(max(1, 2048 / M),
  * ceil(nth / ceil(1024 / N))) -- (refine); fmax * fpitch >= 2^29.  slam2d_search_points_work makes no HIP call; < 0 means
  * SLAM2D_E_* (the M, nx, ny, nth cases above).
- * The set-of-cells score of slam2d_score_poses and slam2d_mcl_step have no point form. */
+ * slam2d_score_points, slam2d_mcl_step_points and slam2d_mcl_step_adaptive_points (below slam2d_mcl_step_adaptive) are the point
+ * forms of slam2d_score_poses and of the two MCL steps, on this cost. */
 #define SLAM2D_MAX_POINTS SLAM2D_MAX_BEAMS        /* 2048: cost stays below 2^44, one heading fits REFINE_TABLE */
 int64_t slam2d_search_points_work(int32_t M, int32_t nx, int32_t ny, int32_t nth);   /* 2 * nth * M words */
 int slam2d_search_points(const Slam2dLevel* level, int32_t p_field,
@@ -768,6 +769,59 @@ int slam2d_mcl_step_adaptive(const Slam2dLidar* lidar, const Slam2dLevel* level,
                              const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
                              const Slam2dMclBins* bins, const uint32_t* d_ntab, int32_t ntab_n,
                              int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream);
+
+/* The point forms of slam2d_score_poses, slam2d_mcl_step and slam2d_mcl_step_adaptive: the same calls for a SET OF POINTS in the
+ * robot's frame (the comment above SLAM2D_MAX_POINTS: point k at d_points[k * point_stride + 0..1], steps 1-4 of its cost) instead
+ * of one scan of one sensor, so that a caller who found a place with slam2d_search_points can grade pose sets and follow the robot
+ * with the particle filter on the same input (added symbols: no struct and no existing signature changed, the ABI number stays).
+ * PRECONDITION: that of slam2d_score_poses (a FULL build -- slam2d_field_build or slam2d_field_build_distance -- has run for slot
+ * p_field of `level`, ordered in front of the call); the same members of `level` are read.  No Slam2dLidar is taken.  Integer
+ * operations and ONE rounded IEEE operation at a time, as in the scan forms: the same inputs give the same bits on every call.
+ * slam2d_score_points is slam2d_score_poses with that endpoint: for pose n = (x, y, th) at d_pose[n * pose_stride + 0..2] and its
+ * set at d_points + n * set_stride (set_stride 0: the one set for every pose; >= M * point_stride doubles: a set per pose), steps
+ * 1-3 of the point cost give valid, the INSIDE points, their cells and sum_b; U = the SET of cells of the inside points, sum_u its
+ * sum; d_out[n * SLAM2D_SCORE_STRIDE + 0..7] as slam2d_score_poses lists them, with the number of VALID points in slot 4.  ONE
+ * launch, a wave per pose with a hash set of score_hash_size(M) keys of its own, no global atomic; a pose costs one cos / sin.
+ * slam2d_mcl_step_points is slam2d_mcl_step with steps a (NOISE), b (MOVE), d (RESAMPLE) and e (REPORT) as written there and
+ *   c. WEIGH.  For the moved pose (x', y', th') and the ONE set d_points, steps 1-4 of the point cost, with c = cos(th'), s =
+ *      sin(th'):  cost_n = sum_b + (uint64)(valid - inside) * outside_cost;  cmin, best and w_n as in slam2d_mcl_step.
+ *   Report word 5 is `valid`.  A set without a valid point costs 0 at every pose: every weight is d_lut[0], best = 0, and the
+ *   resampling is the one of equal weights.
+ * d_work: slam2d_mcl_points_work(N) = slam2d_mcl_work(N) + 2 * N 8-byte words: behind the scan form's arrays the move launch
+ * leaves cos(th'), sin(th') of every MOVED heading, so the scoring launch -- a wave per particle, the points interleaved over
+ * its lanes -- reads four doubles per particle and evaluates no transcendental (a set's trip of 64 points is cheaper than the
+ * pair); the sixteen waves of a block join their packed minima in LDS in front of the block's one integer atomicMin.  Five
+ * launches, of which the weigh and resample launches are slam2d_mcl_step's own kernels.
+ * slam2d_mcl_step_adaptive_points is slam2d_mcl_step_adaptive with the same WEIGH step and word 5; its EQUIVALENCE clause holds
+ * against slam2d_mcl_step_points.  d_work: slam2d_mcl_adapt_points_work(n_cap, bins) = slam2d_mcl_adapt_work(n_cap, bins) +
+ * 2 * n_cap words.  Seven launches; the weigh, reference, count and resample launches are slam2d_mcl_step_adaptive's own.
+ * All three allocate nothing, raise no fault bit and do not synchronise; the caller need not initialise d_out, d_work, d_report,
+ * d_pose_out or d_ancestor.  SLAM2D_E_BADARG, before any HIP call: the level cases of slam2d_score_poses; M < 1 or >
+ * SLAM2D_MAX_POINTS, point_stride < 2, a NULL d_points; (score) a NULL d_pose or d_out, N <= 0, pose_stride < 3, set_stride
+ * neither 0 nor >= M * point_stride; (steps) every particle, table and motion case of slam2d_mcl_step and, for the adaptive one,
+ * every count, table and bins case of slam2d_mcl_step_adaptive.  SLAM2D_E_TOOLARGE: as in the scan forms (the poses of one
+ * launch, N or n_cap > SLAM2D_MCL_MAX_PARTICLES, the bins, fmax * fpitch >= 2^29).  The two *_work functions make no HIP call;
+ * < 0 means SLAM2D_E_*, as slam2d_mcl_work and slam2d_mcl_adapt_work answer. */
+int slam2d_score_points(const Slam2dLevel* level, int32_t p_field, int32_t N,
+                        const double* d_pose, int32_t pose_stride,
+                        const double* d_points, int32_t point_stride, int32_t M, int32_t set_stride,
+                        double* d_out, void* stream);
+int64_t slam2d_mcl_points_work(int32_t N);                      /* slam2d_mcl_work(N) + 2 * N */
+int slam2d_mcl_step_points(const Slam2dLevel* level, int32_t p_field, int32_t N,
+                           const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                           const double motion[3], const double amp[3], uint64_t seed, uint64_t scan,
+                           const double* d_points, int32_t point_stride, int32_t M,
+                           uint32_t outside_cost, const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
+                           int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream);
+int64_t slam2d_mcl_adapt_points_work(int32_t n_cap, const Slam2dMclBins* bins);   /* slam2d_mcl_adapt_work(n_cap, bins) + 2 * n_cap */
+int slam2d_mcl_step_adaptive_points(const Slam2dLevel* level, int32_t p_field, int32_t n_cap,
+                                    const uint32_t* d_n_in, uint32_t* d_n_out,
+                                    const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                                    const double motion[3], const double amp[3], uint64_t seed, uint64_t scan,
+                                    const double* d_points, int32_t point_stride, int32_t M,
+                                    uint32_t outside_cost, const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
+                                    const Slam2dMclBins* bins, const uint32_t* d_ntab, int32_t ntab_n,
+                                    int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream);
 
 /* Exact wall distances as a search field: another way to fill the slots of a level, for the calls that read a full field
  * (slam2d_score_poses, slam2d_search_lattice, slam2d_mcl_step, slam2d_mcl_step_adaptive) -- the likelihood field of Monte-Carlo

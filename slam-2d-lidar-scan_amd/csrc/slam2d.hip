@@ -4848,6 +4848,63 @@ __global__ __launch_bounds__(256) void k_refine_points(Slam2dLevel lv, int p_fie
     refine_candidates(rb, lat, E, valid, lv, sf, outside_cost, out);
 }
 
+// slam2d_score_points: k_score_poses' wave per pose and its hash set of cell keys (hsize = score_hash_size(M)), with R(theta) q
+// of the pose's set for an endpoint -- points interleaved over the lanes (point = 64 i + lane), one cos / sin per pose, which
+// every lane of the wave evaluates alike.  Slot 4 is the number of VALID points.  Reads frames[p_field], the slot's field and the
+// inputs; writes out; no global atomic, no fault bit.
+__global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_points(Slam2dLevel lv, int p_field, int N, int hsize, const double* __restrict__ pose,
+                                                                   int pstride, const double* __restrict__ points, int ptstride, int M, int sstride,
+                                                                   double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) int score_lds[];              // [blockDim.x / 64][hsize] keys
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = blockIdx.x * (blockDim.x >> 6) + wv;
+    int* hkey = score_lds + wv * hsize;
+    const int hmask = hsize - 1;
+    for (int i = lane; i < hsize; i += 64) hkey[i] = INT_MAX;                    // (no key: cx < 2^15 leaves the low half below 0xffff)
+    __syncthreads();
+    if (n >= N) return;                                                          // (wave-uniform)
+    const SlotField sf = slot_field(lv, p_field);
+    const double x = pose[(size_t)n * pstride], y = pose[(size_t)n * pstride + 1], th = pose[(size_t)n * pstride + 2];
+    const double c = cos(th), s = sin(th);
+    const double* __restrict__ pts = points + (size_t)n * sstride;
+    unsigned long long sum_u = 0ull, sum_b = 0ull;                               // (this lane's share)
+    int n_u = 0, n_in = 0, n_val = 0;                                            // (the wave's counts: ballots)
+    for (int k0 = 0; k0 < M; k0 += 64) {                                         // (wave-uniform trip count)
+        const int k = k0 + lane;
+        const bool valid = k < M && point_valid(pts, ptstride, k);
+        bool inside = false;
+        int key = INT_MAX;
+        uint32_t cost = 0u;
+        if (valid) {
+            const double2 e = point_offset(c, s, pts[(size_t)k * ptstride], pts[(size_t)k * ptstride + 1]);
+            int cx, cy;
+            if (score_cell(x + e.x, y + e.y, sf.fr.xlo, sf.fr.ylo, lv.step, sf.fs.fw, sf.fs.fh, cx, cy)) {
+                inside = true;
+                key = (cy << 16) | cx;
+                cost = sf.field[(size_t)cy * lv.fpitch + cx];
+            }
+        }
+        bool owns = false;
+        if (inside) {
+            int slot;
+            owns = cell_set_insert(hkey, hmask, key, slot);
+            sum_b += cost;
+            if (owns) sum_u += cost;
+        }
+        n_val += __popcll(__ballot(valid));
+        n_in += __popcll(__ballot(inside));
+        n_u += __popcll(__ballot(owns));
+    }
+    sum_u = wave64_sum_u64(sum_u);
+    sum_b = wave64_sum_u64(sum_b);
+    if (lane == 0) {
+        const double inv = 1.0 / lv.cost_scale;
+        double* o = out + (size_t)n * SLAM2D_SCORE_STRIDE;
+        o[0] = -((double)sum_u * inv); o[1] = (double)n_u; o[2] = -((double)sum_b * inv); o[3] = (double)n_in;
+        o[4] = (double)n_val; o[5] = (double)sum_u; o[6] = (double)sum_b; o[7] = 0.0;
+    }
+}
+
 // ---- Monte-Carlo localisation in a known map (slam2d_mcl_step): move, weigh, resample, all in integers and rounded operations ----
 #define MCL_WAVES 4                  // particles (waves) per block of the scoring launch
 #define MCL_UNROLL 2                 // trips of 64 beams its beam loop takes at a time: their gathers are in flight together
@@ -4913,8 +4970,8 @@ __device__ __forceinline__ void mcl_reset_joined(const MclWork& wk, unsigned lon
     report[3] = 0ull; report[6] = 0ull;
     for (int i = 10; i < 15; ++i) report[i] = 0ull;
 }
-// Particle n's three draws and its move, in the header's operations and order
-__device__ __forceinline__ void mcl_move_particle(const int n, const double* __restrict__ pose, const int pstride, const double dfwd, const double dside,
+// Particle n's three draws and its move, in the header's operations and order; returns the moved heading
+__device__ __forceinline__ double mcl_move_particle(const int n, const double* __restrict__ pose, const int pstride, const double dfwd, const double dside,
                                                   const double dturn, const double amp0, const double amp1, const double amp2, const uint64_t seed,
                                                   const uint64_t scan, const MclWork& wk) {
     const double x0 = pose[(size_t)n * pstride], y0 = pose[(size_t)n * pstride + 1], th0 = pose[(size_t)n * pstride + 2];
@@ -4923,7 +4980,7 @@ __device__ __forceinline__ void mcl_move_particle(const int n, const double* __r
     double* m = wk.moved + (size_t)n * 3;
     m[0] = (x0 + c * fx) - s * fy;
     m[1] = (y0 + s * fx) + c * fy;
-    m[2] = (th0 + dturn) + amp2 * mcl_noise((uint32_t)n, 2u, seed, scan);
+    return m[2] = (th0 + dturn) + amp2 * mcl_noise((uint32_t)n, 2u, seed, scan);
 }
 
 // First launch, one thread per particle: mcl_move_particle; thread 0 also resets the joined words.  (Moving the pose inside the
@@ -5047,9 +5104,11 @@ __global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcl_weigh(int N, const u
 }
 
 // One block of MCL_SCAN_BLOCK threads: the scan blocks' sums become their exclusive prefix sums; W, the resampler's word and u0,
-// and the report's words 0-15 that need no particle loop
-__device__ __forceinline__ void mcl_sums_block(const Slam2dLidar& lid, const int N, const uint64_t seed, const uint64_t scan,
-                                               const double* __restrict__ ranges, const MclWork& wk, unsigned long long* __restrict__ report) {
+// and the report's words 0-15 that need no particle loop.  counted(t): thread t's share of word 5 -- the beams in range
+// (mcl_beams_in_range) or the valid points (mclp_points_valid) among items t, t + MCL_SCAN_BLOCK, ...
+template <class Counted>
+__device__ __forceinline__ void mcl_sums_block(const int N, const uint64_t seed, const uint64_t scan, const Counted counted, const MclWork& wk,
+                                               unsigned long long* __restrict__ report) {
     __shared__ unsigned long long lds[16];
     __shared__ unsigned n_rng;
     const int t = threadIdx.x, nb = (N + MCL_SCAN_BLOCK - 1) / MCL_SCAN_BLOCK;
@@ -5058,8 +5117,7 @@ __device__ __forceinline__ void mcl_sums_block(const Slam2dLidar& lid, const int
     unsigned long long W;
     const unsigned long long incl = block_scan_u64(v, lds, W);
     if (t < nb) wk.bsum[t] = incl - v;
-    unsigned cnt = 0u;
-    for (int b = t; b < lid.beams; b += MCL_SCAN_BLOCK) cnt += ranges[b] < lid.max_range;
+    const unsigned cnt = counted(t);
     if (cnt) atomicAdd(&n_rng, cnt);
     __syncthreads();
     if (t == 0) {
@@ -5075,10 +5133,19 @@ __device__ __forceinline__ void mcl_sums_block(const Slam2dLidar& lid, const int
     }
 }
 
+// thread t's count of the scan's beams IN RANGE, for mcl_sums_block
+__device__ __forceinline__ auto mcl_beams_in_range(const Slam2dLidar& lid, const double* __restrict__ ranges) {
+    return [&lid, ranges](const int t) {
+        unsigned cnt = 0u;
+        for (int b = t; b < lid.beams; b += MCL_SCAN_BLOCK) cnt += ranges[b] < lid.max_range;
+        return cnt;
+    };
+}
+
 // Sums: mcl_sums_block, one block
 __global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcl_sums(Slam2dLidar lid, int N, uint64_t seed, uint64_t scan, const double* __restrict__ ranges,
                                                              MclWork wk, unsigned long long* __restrict__ report) {
-    mcl_sums_block(lid, N, seed, scan, ranges, wk, report);
+    mcl_sums_block(N, seed, scan, mcl_beams_in_range(lid, ranges), wk, report);
 }
 
 // The resampler's pieces.  Offspring k of n_off has the ticket t_k = floor((k W + u0) / n_off) < W (below 2^64: W <= N * 0xffffff,
@@ -5211,15 +5278,20 @@ __global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcla_weigh(const uint32_
     mcl_weigh_block(N, lut, lut_n, lut_shift, wk, report);
 }
 
-// mcl_sums_block; word 16 = N is what the last launch reads, as it may overwrite *n_in
-__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcla_sums(Slam2dLidar lid, const uint32_t* __restrict__ n_in, int n_cap, uint64_t seed, uint64_t scan,
-                                                              const double* __restrict__ ranges, MclWork wk, unsigned long long* __restrict__ report) {
-    const int N = mcla_live(n_in, n_cap);
-    mcl_sums_block(lid, N, seed, scan, ranges, wk, report);
+// word 16 = N is what the last launch reads, as it may overwrite *n_in; the padding words
+__device__ __forceinline__ void mcla_report_live(const int N, unsigned long long* __restrict__ report) {
     if (threadIdx.x == 0) {
         report[16] = (unsigned long long)N;
         for (int i = 20; i < 24; ++i) report[i] = 0ull;
     }
+}
+
+// mcl_sums_block, then mcla_report_live
+__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcla_sums(Slam2dLidar lid, const uint32_t* __restrict__ n_in, int n_cap, uint64_t seed, uint64_t scan,
+                                                              const double* __restrict__ ranges, MclWork wk, unsigned long long* __restrict__ report) {
+    const int N = mcla_live(n_in, n_cap);
+    mcl_sums_block(N, seed, scan, mcl_beams_in_range(lid, ranges), wk, report);
+    mcla_report_live(N, report);
 }
 
 // The pose bin of the header's step e; n_bins for a pose that is not binnable.  No quotient that fails the guard is converted.
@@ -5323,6 +5395,162 @@ __global__ __launch_bounds__(256) void k_mcla_resample(int n_cap, const uint32_t
         mcl_emit_offspring(j, a, first, wk, out, pstride, ancestor, part);
     }
     mcl_join_sums(part, acc, report);
+}
+
+// ---- the two steps for a set of points in the robot's frame (slam2d_mcl_step_points, slam2d_mcl_step_adaptive_points) ----
+// WEIGH with the point cost of include/slam2d.h (above SLAM2D_MAX_POINTS): an endpoint is (x', y') + R(th') q.  A point's trip
+// is six multiply-adds and two divisions, so one cos / sin per wave would cost more than the set's trips: the move launch, a
+// thread per particle, evaluates cos(th'), sin(th') of the MOVED heading and leaves them in cs[n][2], 2 n words of d_work behind
+// the scan form's, and the scoring wave evaluates no transcendental.  Only the move, score and sums launches differ from the
+// scan forms': the weigh, reference, count and resample launches are theirs.
+
+#define MCLP_WAVES 16                // particles (waves) per block of the point forms' scoring launches: one join per block
+
+// mcl_move_particle, then the moved heading's cos / sin into cs
+__device__ __forceinline__ void mclp_move_particle(const int n, const double* __restrict__ pose, const int pstride, const double dfwd, const double dside,
+                                                   const double dturn, const double amp0, const double amp1, const double amp2, const uint64_t seed,
+                                                   const uint64_t scan, const MclWork& wk, double* __restrict__ cs) {
+    const double th = mcl_move_particle(n, pose, pstride, dfwd, dside, dturn, amp0, amp1, amp2, seed, scan, wk);
+    cs[(size_t)n * 2] = cos(th);
+    cs[(size_t)n * 2 + 1] = sin(th);
+}
+
+// k_mcl_move with mclp_move_particle
+__global__ __launch_bounds__(256) void k_mclp_move(int N, const double* __restrict__ pose, int pstride, double dfwd, double dside, double dturn,
+                                                   double amp0, double amp1, double amp2, uint64_t seed, uint64_t scan, MclWork wk,
+                                                   double* __restrict__ cs, unsigned long long* __restrict__ report) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0) mcl_reset_joined(wk, report);
+    if (n >= N) return;
+    mclp_move_particle(n, pose, pstride, dfwd, dside, dturn, amp0, amp1, amp2, seed, scan, wk, cs);
+}
+
+// mcl_beams for points: U trips of 64 points of one particle, from point k0.  A point that is not inside -- invalid, beyond the
+// last point, outside the field, a quotient that fails the guard -- loads cell 0 of the image and adds nothing: no branch, so
+// the U gathers are in flight together.  (An invalid point's offset is not finite, so its quotient fails the guard by itself.)
+template <int U>
+__device__ __forceinline__ void mclp_points(const int k0, const int lane, const int M, const double* __restrict__ pts, const int ptstride, const double c,
+                                            const double s, const double x, const double y, const Slam2dFrame& fr, const double step,
+                                            const FieldSize fs, const int fpitch, const uint32_t* __restrict__ field,
+                                            unsigned long long& sum_b, int& n_in, int& n_val) {
+    int idx[U];
+    bool inside[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int k = k0 + 64 * u + lane;
+        const double qx = k < M ? pts[(size_t)k * ptstride] : NAN, qy = k < M ? pts[(size_t)k * ptstride + 1] : NAN;
+        const bool valid = __builtin_isfinite(qx) && __builtin_isfinite(qy);     // (step 1)
+        const double2 e = point_offset(c, s, qx, qy);
+        int cx, cy;
+        inside[u] = score_cell(x + e.x, y + e.y, fr.xlo, fr.ylo, step, fs.fw, fs.fh, cx, cy) && valid;
+        idx[u] = inside[u] ? cy * fpitch + cx : 0;                               // (fmax * fpitch < 2^29)
+        n_val += __popcll(__ballot(valid));
+        n_in += __popcll(__ballot(inside[u]));
+    }
+    uint32_t cost[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) cost[u] = field[idx[u]];
+#pragma unroll
+    for (int u = 0; u < U; ++u) sum_b += inside[u] ? cost[u] : 0u;
+}
+
+// Particle n on this wave, as mcl_score_particle: the points interleaved over the lanes, read contiguously; the moved position and
+// the heading's cos / sin from the move launch -- four doubles per particle.  Writes the particle's cost and returns cost << 20 | n
+// (the same on every lane) for mclp_join_block.
+__device__ __forceinline__ unsigned long long mclp_score_particle(const int n, const int lane, const Slam2dLevel& lv, const Slam2dFrame& fr, const FieldSize fs,
+                                                    const uint32_t* __restrict__ field, const double* __restrict__ pts, const int ptstride, const int M,
+                                                    const unsigned outside_cost, const MclWork& wk, const double* __restrict__ cs) {
+    const double x = wk.moved[(size_t)n * 3], y = wk.moved[(size_t)n * 3 + 1], c = cs[(size_t)n * 2], s = cs[(size_t)n * 2 + 1];
+    const int trips = (M + 63) >> 6;
+    unsigned long long sum_b = 0ull;                                             // (this lane's share)
+    int n_in = 0, n_val = 0;                                                     // (the wave's counts: ballots)
+    int t = 0;
+    for (; t + MCL_UNROLL <= trips; t += MCL_UNROLL)                             // (wave-uniform trip counts)
+        mclp_points<MCL_UNROLL>(64 * t, lane, M, pts, ptstride, c, s, x, y, fr, lv.step, fs, lv.fpitch, field, sum_b, n_in, n_val);
+    for (; t < trips; ++t) mclp_points<1>(64 * t, lane, M, pts, ptstride, c, s, x, y, fr, lv.step, fs, lv.fpitch, field, sum_b, n_in, n_val);
+    sum_b = wave64_sum_u64(sum_b);
+    const unsigned long long cost = sum_b + (unsigned long long)(n_val - n_in) * outside_cost;          // (below 2^44 at 2048 points)
+    if (lane == 0) wk.cost[n] = cost;
+    return (cost << 20) | (unsigned long long)n;
+}
+
+// The waves' minima of cost << 20 | n (all ones: none) joined per block in LDS, then with mcl_score_particle's conditional 64-bit
+// atomicMin, one per block.  A wave of the point form is a few microseconds short: with a join per wave the waves of a small set
+// all read the word before any atomic has landed and every one of them sends its own to the one address
+// (profiles/r24_mcl_points.md).  Every thread of the block calls it.
+__device__ __forceinline__ void mclp_join_block(const unsigned long long best, const int wv, const int lane, const MclWork& wk) {
+    __shared__ unsigned long long wbest[MCLP_WAVES];
+    if (lane == 0) wbest[wv] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long v = wbest[0];
+        for (int i = 1; i < MCLP_WAVES; ++i) v = min(v, wbest[i]);
+        if (v < __hip_atomic_load(wk.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(wk.key, v);
+    }
+}
+
+// Score: one wave per particle (mclp_score_particle), MCLP_WAVES of them per block (mclp_join_block).  Reads frames[p_field], the
+// slot's field, the moved poses, cs and the points; writes the costs; no fault bit.
+__global__ __launch_bounds__(64 * MCLP_WAVES) void k_mclp_score(Slam2dLevel lv, int p_field, int N, const double* __restrict__ pts, int ptstride, int M,
+                                                                unsigned outside_cost, MclWork wk, const double* __restrict__ cs) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = blockIdx.x * MCLP_WAVES + wv;
+    const SlotField sf = slot_field(lv, p_field);
+    unsigned long long best = ~0ull;
+    if (n < N) best = mclp_score_particle(n, lane, lv, sf.fr, sf.fs, sf.field, pts, ptstride, M, outside_cost, wk, cs);    // (wave-uniform)
+    mclp_join_block(best, wv, lane, wk);
+}
+
+// thread t's count of the set's VALID points, for mcl_sums_block
+__device__ __forceinline__ auto mclp_points_valid(const double* __restrict__ pts, const int ptstride, const int M) {
+    return [pts, ptstride, M](const int t) {
+        unsigned cnt = 0u;
+        for (int k = t; k < M; k += MCL_SCAN_BLOCK) cnt += point_valid(pts, ptstride, k);
+        return cnt;
+    };
+}
+
+// Sums: mcl_sums_block with the valid points in word 5, one block
+__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mclp_sums(int N, uint64_t seed, uint64_t scan, const double* __restrict__ pts, int ptstride, int M,
+                                                              MclWork wk, unsigned long long* __restrict__ report) {
+    mcl_sums_block(N, seed, scan, mclp_points_valid(pts, ptstride, M), wk, report);
+}
+
+// k_mcla_move with mclp_move_particle
+__global__ __launch_bounds__(256) void k_mclap_move(const uint32_t* __restrict__ n_in, int n_cap, const double* __restrict__ pose, int pstride,
+                                                    double dfwd, double dside, double dturn, double amp0, double amp1, double amp2,
+                                                    uint64_t seed, uint64_t scan, MclWork wk, double* __restrict__ cs,
+                                                    unsigned long long* __restrict__ bitmap, int words, unsigned long long* __restrict__ tail,
+                                                    unsigned long long* __restrict__ report) {
+    const int N = mcla_live(n_in, n_cap), t0 = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    if (t0 == 0) {
+        mcl_reset_joined(wk, report);
+        tail[0] = 0ull; tail[1] = 0ull;
+    }
+    for (int i = t0; i < words; i += stride) bitmap[i] = 0ull;
+    for (int n = t0; n < N; n += stride) mclp_move_particle(n, pose, pstride, dfwd, dside, dturn, amp0, amp1, amp2, seed, scan, wk, cs);
+}
+
+// mclp_score_particle: a wave takes particles wave, wave + the grid's waves, ... below N and keeps their minimum for mclp_join_block
+__global__ __launch_bounds__(64 * MCLP_WAVES) void k_mclap_score(Slam2dLevel lv, int p_field, const uint32_t* __restrict__ n_in, int n_cap,
+                                                                const double* __restrict__ pts, int ptstride, int M, unsigned outside_cost,
+                                                                MclWork wk, const double* __restrict__ cs) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int N = mcla_live(n_in, n_cap);
+    const SlotField sf = slot_field(lv, p_field);
+    unsigned long long best = ~0ull;
+    for (int n = blockIdx.x * MCLP_WAVES + wv; n < N; n += gridDim.x * MCLP_WAVES)  // (wave-uniform)
+        best = min(best, mclp_score_particle(n, lane, lv, sf.fr, sf.fs, sf.field, pts, ptstride, M, outside_cost, wk, cs));
+    mclp_join_block(best, wv, lane, wk);
+}
+
+// k_mclp_sums over the live count, then mcla_report_live
+__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mclap_sums(const uint32_t* __restrict__ n_in, int n_cap, uint64_t seed, uint64_t scan,
+                                                               const double* __restrict__ pts, int ptstride, int M, MclWork wk,
+                                                               unsigned long long* __restrict__ report) {
+    const int N = mcla_live(n_in, n_cap);
+    mcl_sums_block(N, seed, scan, mclp_points_valid(pts, ptstride, M), wk, report);
+    mcla_report_live(N, report);
 }
 
 // Sharded normaliser, merge half: every rank folds the gathered [world][3] partials in rank order
@@ -6182,6 +6410,23 @@ int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32
     return launch_status();
 }
 
+int slam2d_score_points(const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose, int32_t pose_stride, const double* d_points,
+                        int32_t point_stride, int32_t M, int32_t set_stride, double* d_out, void* stream) {
+    const int rc = check_level_field(level, p_field);
+    if (rc == SLAM2D_E_BADARG) return rc;
+    if (!d_pose || !d_points || !d_out || N <= 0 || pose_stride < 3) return SLAM2D_E_BADARG;
+    if (M < 1 || M > SLAM2D_MAX_POINTS || point_stride < 2) return SLAM2D_E_BADARG;
+    if (set_stride != 0 && (long long)set_stride < (long long)M * point_stride) return SLAM2D_E_BADARG;
+    if (rc) return rc;
+    const int hsize = score_hash_size(M);
+    const int waves = hsize > 2048 ? SCORE_WAVES / 2 : SCORE_WAVES;               // <= 32 KB of hash sets per block
+    const long long blocks = ((long long)N + waves - 1) / waves;
+    if (blocks * (64 * waves) > 0xffffffffll) return SLAM2D_E_TOOLARGE;           // (a launch holds fewer than 2^32 threads)
+    k_score_points<<<(unsigned)blocks, 64 * waves, (size_t)waves * hsize * sizeof(int), (hipStream_t)stream>>>(
+        *level, p_field, N, hsize, d_pose, pose_stride, d_points, point_stride, M, set_stride, d_out);
+    return launch_status();
+}
+
 // the checks slam2d_search_lattice and its work size share; *words: the 8-byte words of d_work (the endpoint table)
 static int check_search_lattice(const Slam2dLidar* lidar, int nx, int ny, int nth, long long* words) {
     if (!lidar || nx < 1 || ny < 1 || nth < 1 || nth > 65536) return SLAM2D_E_BADARG;
@@ -6344,19 +6589,35 @@ int64_t slam2d_mcl_work(int32_t N) {
     return mcl_work_words(N);
 }
 
-// What slam2d_mcl_step and slam2d_mcl_step_adaptive check alike, for n particles (or that capacity).  SLAM2D_E_BADARG comes
-// before SLAM2D_E_TOOLARGE -- n first, then the field's --, which a caller returns after its own argument checks.
-static int check_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int p_field, int n, const double* d_pose_in, const double* d_pose_out,
-                          int pose_stride, const double* motion, const double* amp, const double* d_ranges, const uint32_t* d_lut, int lut_n,
-                          int lut_shift, const uint64_t* d_work, const uint64_t* d_report) {
-    const int frc = check_scored_field(lidar, level, p_field);
+// What the four MCL steps check alike, for n particles (or that capacity), behind their field check's answer frc; d_source: the
+// scan or the point set.  SLAM2D_E_BADARG comes before SLAM2D_E_TOOLARGE -- n first, then the field's --, which a caller returns
+// after its own argument checks.
+static int check_mcl_particles(int frc, int n, const double* d_pose_in, const double* d_pose_out, int pose_stride, const double* motion,
+                               const double* amp, const double* d_source, const uint32_t* d_lut, int lut_n, int lut_shift, const uint64_t* d_work,
+                               const uint64_t* d_report) {
     if (frc == SLAM2D_E_BADARG) return frc;
-    if (!d_pose_in || !d_pose_out || !motion || !amp || !d_ranges || !d_lut || !d_work || !d_report) return SLAM2D_E_BADARG;
+    if (!d_pose_in || !d_pose_out || !motion || !amp || !d_source || !d_lut || !d_work || !d_report) return SLAM2D_E_BADARG;
     if (d_pose_in == d_pose_out || n < 1 || pose_stride < 3 || lut_n < 1 || lut_n > 65536 || lut_shift < 0 || lut_shift > 43)
         return SLAM2D_E_BADARG;
     for (int i = 0; i < 3; ++i)
         if (!__builtin_isfinite(motion[i]) || !__builtin_isfinite(amp[i])) return SLAM2D_E_BADARG;
     return n > SLAM2D_MCL_MAX_PARTICLES ? SLAM2D_E_TOOLARGE : frc;
+}
+// The scan forms': the lidar's and the level's checks in front
+static int check_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int p_field, int n, const double* d_pose_in, const double* d_pose_out,
+                          int pose_stride, const double* motion, const double* amp, const double* d_ranges, const uint32_t* d_lut, int lut_n,
+                          int lut_shift, const uint64_t* d_work, const uint64_t* d_report) {
+    return check_mcl_particles(check_scored_field(lidar, level, p_field), n, d_pose_in, d_pose_out, pose_stride, motion, amp, d_ranges, d_lut, lut_n,
+                               lut_shift, d_work, d_report);
+}
+// The point forms': the level's checks in front, the set's own (slam2d_refine_points') behind
+static int check_mcl_step_points(const Slam2dLevel* level, int p_field, int n, const double* d_pose_in, const double* d_pose_out, int pose_stride,
+                                 const double* motion, const double* amp, const double* d_points, int point_stride, int M, const uint32_t* d_lut,
+                                 int lut_n, int lut_shift, const uint64_t* d_work, const uint64_t* d_report) {
+    const int rc = check_mcl_particles(check_level_field(level, p_field), n, d_pose_in, d_pose_out, pose_stride, motion, amp, d_points, d_lut, lut_n,
+                                       lut_shift, d_work, d_report);
+    if (rc == SLAM2D_E_BADARG || M < 1 || M > SLAM2D_MAX_POINTS || point_stride < 2) return SLAM2D_E_BADARG;
+    return rc;
 }
 
 int slam2d_mcl_step(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose_in,
@@ -6396,36 +6657,102 @@ int64_t slam2d_mcl_adapt_work(int32_t n_cap, const Slam2dMclBins* bins) {
     return mcl_work_words(n_cap) + mcla_bitmap_words(n_bins) + MCLA_TAIL;
 }
 
+// What the two adaptive steps check behind their plain step's answer rc; *n_bins: nx * ny * nth
+static int check_mcl_adaptive(int rc, const uint32_t* d_n_in, const uint32_t* d_n_out, const uint32_t* d_ntab, int ntab_n, const Slam2dMclBins* bins,
+                              long long* n_bins) {
+    if (rc == SLAM2D_E_BADARG) return rc;
+    if (!d_n_in || !d_n_out || !d_ntab || ntab_n < 1 || ntab_n > 65536) return SLAM2D_E_BADARG;
+    const int brc = check_mcl_bins(bins, n_bins);
+    if (brc == SLAM2D_E_BADARG) return brc;
+    return rc ? rc : brc;
+}
+// d_work of an adaptive step and the grids of its launches over the capacity: slam2d_mcl_step's arrays, the bitmap, the tail
+struct MclaWork { MclWork wk; unsigned long long *bitmap, *tail; int words, per_particle, move_blocks, score_blocks; };
+static MclaWork mcla_work_of(uint64_t* d_work, int n_cap, long long n_bins) {
+    const int words = (int)mcla_bitmap_words(n_bins);                             // (at most 2^20 + 1)
+    unsigned long long* bitmap = (unsigned long long*)d_work + mcl_work_words(n_cap);
+    return MclaWork{mcl_work_of(d_work, n_cap), bitmap, bitmap + words, words, min(cdiv(n_cap, 256), MCLA_BLOCKS),
+                    min(max(cdiv(n_cap, 256), cdiv(words, 256)), MCLA_BLOCKS), min(cdiv(n_cap, MCL_WAVES), MCLA_SCORE_BLOCKS)};
+}
+// The last three launches of an adaptive step: the reference ancestors and their bins, the bitmap's count, the resampling
+static int launch_mcla_resampling(const MclaWork& a, int n_cap, const uint32_t* d_n_in, uint32_t* d_n_out, const Slam2dMclBins& bins,
+                                  const uint32_t* d_ntab, int ntab_n, double* d_pose_out, int pose_stride, int32_t* d_ancestor,
+                                  unsigned long long* report, hipStream_t s) {
+    k_mcla_refs<<<min(a.per_particle, MCLA_REF_BLOCKS), 256, 0, s>>>(d_n_in, n_cap, a.wk, bins, a.bitmap, a.tail, report);
+    k_mcla_count<<<min(cdiv(a.words, 256), MCLA_BLOCKS), 256, 0, s>>>(a.bitmap, a.words, a.tail);
+    k_mcla_resample<<<a.per_particle, 256, 0, s>>>(n_cap, d_ntab, ntab_n, a.wk, a.tail, d_pose_out, pose_stride, d_ancestor, d_n_out, report);
+    return launch_status();
+}
+
 int slam2d_mcl_step_adaptive(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, int32_t n_cap, const uint32_t* d_n_in,
                              uint32_t* d_n_out, const double* d_pose_in, double* d_pose_out, int32_t pose_stride, const double motion[3],
                              const double amp[3], uint64_t seed, uint64_t scan, const double* d_ranges, uint32_t outside_cost,
                              const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift, const Slam2dMclBins* bins, const uint32_t* d_ntab,
                              int32_t ntab_n, int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream) {
-    const int rc = check_mcl_step(lidar, level, p_field, n_cap, d_pose_in, d_pose_out, pose_stride, motion, amp, d_ranges, d_lut, lut_n, lut_shift,
-                                  d_work, d_report);
-    if (rc == SLAM2D_E_BADARG) return rc;
-    if (!d_n_in || !d_n_out || !d_ntab || ntab_n < 1 || ntab_n > 65536) return SLAM2D_E_BADARG;
     long long n_bins = 0;
-    const int brc = check_mcl_bins(bins, &n_bins);
-    if (brc == SLAM2D_E_BADARG) return brc;
+    const int rc = check_mcl_adaptive(check_mcl_step(lidar, level, p_field, n_cap, d_pose_in, d_pose_out, pose_stride, motion, amp, d_ranges, d_lut,
+                                                     lut_n, lut_shift, d_work, d_report), d_n_in, d_n_out, d_ntab, ntab_n, bins, &n_bins);
     if (rc) return rc;
-    if (brc) return brc;
     hipStream_t s = (hipStream_t)stream;
-    const MclWork wk = mcl_work_of(d_work, n_cap);
-    const int words = (int)mcla_bitmap_words(n_bins);                             // (at most 2^20 + 1)
-    unsigned long long* bitmap = (unsigned long long*)d_work + mcl_work_words(n_cap);
-    unsigned long long* tail = bitmap + words;
+    const MclaWork a = mcla_work_of(d_work, n_cap, n_bins);
     unsigned long long* report = (unsigned long long*)d_report;
-    const int per_particle = min(cdiv(n_cap, 256), MCLA_BLOCKS);
-    k_mcla_move<<<min(max(cdiv(n_cap, 256), cdiv(words, 256)), MCLA_BLOCKS), 256, 0, s>>>(d_n_in, n_cap, d_pose_in, pose_stride, motion[0], motion[1],
-        motion[2], amp[0], amp[1], amp[2], seed, scan, wk, bitmap, words, tail, report);
-    k_mcla_score<<<min(cdiv(n_cap, MCL_WAVES), MCLA_SCORE_BLOCKS), 64 * MCL_WAVES, 0, s>>>(*lidar, *level, p_field, d_n_in, n_cap, d_ranges, outside_cost, wk);
-    k_mcla_weigh<<<cdiv(n_cap, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(d_n_in, n_cap, d_lut, lut_n, lut_shift, wk, report);
-    k_mcla_sums<<<1, MCL_SCAN_BLOCK, 0, s>>>(*lidar, d_n_in, n_cap, seed, scan, d_ranges, wk, report);
-    k_mcla_refs<<<min(per_particle, MCLA_REF_BLOCKS), 256, 0, s>>>(d_n_in, n_cap, wk, *bins, bitmap, tail, report);
-    k_mcla_count<<<min(cdiv(words, 256), MCLA_BLOCKS), 256, 0, s>>>(bitmap, words, tail);
-    k_mcla_resample<<<per_particle, 256, 0, s>>>(n_cap, d_ntab, ntab_n, wk, tail, d_pose_out, pose_stride, d_ancestor, d_n_out, report);
+    k_mcla_move<<<a.move_blocks, 256, 0, s>>>(d_n_in, n_cap, d_pose_in, pose_stride, motion[0], motion[1], motion[2], amp[0], amp[1], amp[2], seed, scan,
+                                              a.wk, a.bitmap, a.words, a.tail, report);
+    k_mcla_score<<<a.score_blocks, 64 * MCL_WAVES, 0, s>>>(*lidar, *level, p_field, d_n_in, n_cap, d_ranges, outside_cost, a.wk);
+    k_mcla_weigh<<<cdiv(n_cap, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(d_n_in, n_cap, d_lut, lut_n, lut_shift, a.wk, report);
+    k_mcla_sums<<<1, MCL_SCAN_BLOCK, 0, s>>>(*lidar, d_n_in, n_cap, seed, scan, d_ranges, a.wk, report);
+    return launch_mcla_resampling(a, n_cap, d_n_in, d_n_out, *bins, d_ntab, ntab_n, d_pose_out, pose_stride, d_ancestor, report, s);
+}
+
+int64_t slam2d_mcl_points_work(int32_t N) {
+    const int64_t words = slam2d_mcl_work(N);
+    return words < 0 ? words : words + 2ll * N;                                   // behind the scan form's: cos / sin of the moved headings
+}
+
+int slam2d_mcl_step_points(const Slam2dLevel* level, int32_t p_field, int32_t N, const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                           const double motion[3], const double amp[3], uint64_t seed, uint64_t scan, const double* d_points,
+                           int32_t point_stride, int32_t M, uint32_t outside_cost, const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
+                           int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream) {
+    const int rc = check_mcl_step_points(level, p_field, N, d_pose_in, d_pose_out, pose_stride, motion, amp, d_points, point_stride, M, d_lut, lut_n,
+                                         lut_shift, d_work, d_report);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const MclWork wk = mcl_work_of(d_work, N);
+    double* cs = reinterpret_cast<double*>(d_work + mcl_work_words(N));
+    unsigned long long* report = (unsigned long long*)d_report;
+    k_mclp_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion[0], motion[1], motion[2], amp[0], amp[1], amp[2], seed, scan, wk, cs, report);
+    k_mclp_score<<<cdiv(N, MCLP_WAVES), 64 * MCLP_WAVES, 0, s>>>(*level, p_field, N, d_points, point_stride, M, outside_cost, wk, cs);
+    k_mcl_weigh<<<cdiv(N, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(N, d_lut, lut_n, lut_shift, wk, report);
+    k_mclp_sums<<<1, MCL_SCAN_BLOCK, 0, s>>>(N, seed, scan, d_points, point_stride, M, wk, report);
+    k_mcl_resample<<<cdiv(N, 256), 256, 0, s>>>(N, wk, d_pose_out, pose_stride, d_ancestor, report);
     return launch_status();
+}
+
+int64_t slam2d_mcl_adapt_points_work(int32_t n_cap, const Slam2dMclBins* bins) {
+    const int64_t words = slam2d_mcl_adapt_work(n_cap, bins);
+    return words < 0 ? words : words + 2ll * n_cap;                               // behind the scan form's, as in slam2d_mcl_points_work
+}
+
+int slam2d_mcl_step_adaptive_points(const Slam2dLevel* level, int32_t p_field, int32_t n_cap, const uint32_t* d_n_in, uint32_t* d_n_out,
+                                    const double* d_pose_in, double* d_pose_out, int32_t pose_stride, const double motion[3], const double amp[3],
+                                    uint64_t seed, uint64_t scan, const double* d_points, int32_t point_stride, int32_t M, uint32_t outside_cost,
+                                    const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift, const Slam2dMclBins* bins, const uint32_t* d_ntab,
+                                    int32_t ntab_n, int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream) {
+    long long n_bins = 0;
+    const int rc = check_mcl_adaptive(check_mcl_step_points(level, p_field, n_cap, d_pose_in, d_pose_out, pose_stride, motion, amp, d_points,
+                                                            point_stride, M, d_lut, lut_n, lut_shift, d_work, d_report),
+                                      d_n_in, d_n_out, d_ntab, ntab_n, bins, &n_bins);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const MclaWork a = mcla_work_of(d_work, n_cap, n_bins);
+    double* cs = reinterpret_cast<double*>(a.tail + MCLA_TAIL);
+    unsigned long long* report = (unsigned long long*)d_report;
+    k_mclap_move<<<a.move_blocks, 256, 0, s>>>(d_n_in, n_cap, d_pose_in, pose_stride, motion[0], motion[1], motion[2], amp[0], amp[1], amp[2], seed, scan,
+                                               a.wk, cs, a.bitmap, a.words, a.tail, report);
+    k_mclap_score<<<cdiv(a.score_blocks * MCL_WAVES, MCLP_WAVES), 64 * MCLP_WAVES, 0, s>>>(*level, p_field, d_n_in, n_cap, d_points, point_stride, M, outside_cost, a.wk, cs);
+    k_mcla_weigh<<<cdiv(n_cap, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(d_n_in, n_cap, d_lut, lut_n, lut_shift, a.wk, report);
+    k_mclap_sums<<<1, MCL_SCAN_BLOCK, 0, s>>>(d_n_in, n_cap, seed, scan, d_points, point_stride, M, a.wk, report);
+    return launch_mcla_resampling(a, n_cap, d_n_in, d_n_out, *bins, d_ntab, ntab_n, d_pose_out, pose_stride, d_ancestor, report, s);
 }
 
 int slam2d_grid_update_weights(const Slam2dLidar* lidar, const Slam2dMap* d_maps, int32_t P, const double* d_pose,

@@ -1427,15 +1427,16 @@ class ParticleEngine:
         buffer of the same row length, 3 or more doubles per pose).  ``d_lut``, ``shift``: ``weight_table`` on the device;
         ``d_report``: 16 int64 words (``mcl_report_host`` decodes them); ``d_ancestor``: None or [N] int32.  Five launches on the
         current stream, no synchronisation; the scratch is kept and grown."""
-        self._mcl("slam2d_mcl_step", "_mcl_work", self.L.slam2d_mcl_work(N), "slam2d_mcl_work", level, p_field, N, "N", _lib.MCL_REPORT, (),
-                  d_in, d_out, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift, (), d_report, d_ancestor)
+        self._mcl("slam2d_mcl_step", (C.byref(self.lidar_c),), "_mcl_work", self.L.slam2d_mcl_work(N), "slam2d_mcl_work", level, p_field, N, "N",
+                  _lib.MCL_REPORT, (), d_in, d_out, motion, amp, seed, scan, (_ptr(d_ranges),), outside_cost, d_lut, shift, (), d_report, d_ancestor)
 
-    def _mcl(self, name, scratch, words, what, level, p_field, n, n_name, report_words, counts, d_in, d_out, motion, amp, seed, scan, d_ranges, outside_cost,
-             d_lut, shift, sizing, d_report, d_ancestor):
-        """The body of ``mcl_step`` and ``mcl_step_adaptive``, the library's ``name``, over ``n`` poses (``n_name`` in the messages)
-        and a report of ``report_words``: the two pose buffers, the report and the ancestors, the step's own scratch
-        (``scratch``, ``words``, ``what``: ``_scratch``'s arguments) and the packing of motion, amplitudes, seed and scan.  ``counts``: the adaptive step's count
-        words, after ``n``; ``sizing``: its bins and table, after the weights'."""
+    def _mcl(self, name, head, scratch, words, what, level, p_field, n, n_name, report_words, counts, d_in, d_out, motion, amp, seed, scan, source,
+             outside_cost, d_lut, shift, sizing, d_report, d_ancestor):
+        """The body of the four MCL steps, the library's ``name``, over ``n`` poses (``n_name`` in the messages) and a report of
+        ``report_words``: the two pose buffers, the report and the ancestors, the step's own scratch (``scratch``, ``words``,
+        ``what``: ``_scratch``'s arguments) and the packing of motion, amplitudes, seed and scan.  ``head``: the call's arguments
+        before the level; ``source``: the scan's or the point set's; ``counts``: an adaptive step's count words, after ``n``;
+        ``sizing``: its bins and table, after the weights'."""
         _check_slot(level, p_field)
         stride = d_in.shape[-1] if d_in.dim() > 1 else 3
         if (d_out.shape[-1] if d_out.dim() > 1 else 3) != stride or d_in.numel() < n * stride or d_out.numel() < n * stride:
@@ -1443,9 +1444,9 @@ class ParticleEngine:
         if d_report.numel() < report_words or (d_ancestor is not None and d_ancestor.numel() < n):
             raise ValueError(f"d_report wants {report_words} words, d_ancestor {n_name}")
         work = self._scratch(scratch, words, what)
-        check(getattr(self.L, name)(C.byref(self.lidar_c), C.byref(level.c), p_field, n, *counts, _ptr(d_in), _ptr(d_out), stride,
+        check(getattr(self.L, name)(*head, C.byref(level.c), p_field, n, *counts, _ptr(d_in), _ptr(d_out), stride,
                                     _triple(motion), _triple(amp), int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff,
-                                    _ptr(d_ranges), int(outside_cost), _ptr(d_lut), d_lut.numel(), int(shift), *sizing,
+                                    *source, int(outside_cost), _ptr(d_lut), d_lut.numel(), int(shift), *sizing,
                                     _ptr(d_ancestor), _ptr(work), _ptr(d_report), _stream()), name)
 
     def mcl_step_adaptive(self, level, p_field, d_in, d_out, n_cap, d_count, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift,
@@ -1456,12 +1457,58 @@ class ParticleEngine:
         ``d_ntab`` (``kld_table`` on the device), resamples to that many poses and leaves the count in ``d_count_out`` (default:
         ``d_count`` itself).  ``d_report``: 24 int64 words (``mcl_adapt_report_host``).  Seven launches on the current stream,
         no synchronisation; the scratch is kept and grown."""
+        self._mcl_adaptive("slam2d_mcl_step_adaptive", (C.byref(self.lidar_c),), "slam2d_mcl_adapt_work", level, p_field, d_in, d_out, n_cap, d_count,
+                           motion, amp, seed, scan, (_ptr(d_ranges),), outside_cost, d_lut, shift, bins, d_ntab, d_report, d_ancestor, d_count_out)
+
+    def _mcl_adaptive(self, name, head, what, level, p_field, d_in, d_out, n_cap, d_count, motion, amp, seed, scan, source, outside_cost, d_lut,
+                      shift, bins, d_ntab, d_report, d_ancestor, d_count_out):
+        """``_mcl`` for the two adaptive steps: the count words, the work size ``what`` of the capacity and the bins, the table."""
         d_count_out = d_count if d_count_out is None else d_count_out
         if any(t.numel() < 1 or t.element_size() != 4 for t in (d_count, d_count_out)):
             raise ValueError("d_count wants one 32-bit word")
-        self._mcl("slam2d_mcl_step_adaptive", "_mcl_adapt_work", self.L.slam2d_mcl_adapt_work(n_cap, C.byref(bins)), "slam2d_mcl_adapt_work",
-                  level, p_field, n_cap, "n_cap", _lib.MCL_ADAPT_REPORT, (_ptr(d_count), _ptr(d_count_out)), d_in, d_out, motion, amp, seed, scan,
-                  d_ranges, outside_cost, d_lut, shift, (C.byref(bins), _ptr(d_ntab), d_ntab.numel()), d_report, d_ancestor)
+        self._mcl(name, head, "_mcl_adapt_work", getattr(self.L, what)(n_cap, C.byref(bins)), what, level, p_field, n_cap, "n_cap",
+                  _lib.MCL_ADAPT_REPORT, (_ptr(d_count), _ptr(d_count_out)), d_in, d_out, motion, amp, seed, scan, source, outside_cost, d_lut, shift,
+                  (C.byref(bins), _ptr(d_ntab), d_ntab.numel()), d_report, d_ancestor)
+
+    @staticmethod
+    def _point_source(d_points, M, point_stride):
+        """The one point set of an MCL step as the call's arguments; ValueError where the buffer does not hold it."""
+        M, point_stride = int(M), int(point_stride)
+        if M < 1 or point_stride < 2 or d_points.numel() < (M - 1) * point_stride + 2:
+            raise ValueError(f"d_points {tuple(d_points.shape)}: want {M} points, {point_stride} doubles apart")
+        return _ptr(d_points), point_stride, M
+
+    def score_points(self, level, p_field, d_pose, pose_stride, N, d_points, M, set_stride, point_stride=2):
+        """``score_poses`` for a set of points in the robot's frame instead of a scan (include/slam2d.h, slam2d_score_points):
+        ``set_stride`` 0: the one set ``d_points`` (``M`` points, ``point_stride`` doubles apart) for every pose; >= M *
+        point_stride: a set per pose, that many doubles apart.  The same ``[N, SCORE_STRIDE]`` rows with the number of valid
+        points where ``score_poses`` has the beams in range (``score_host`` calls both ``in_range``).  One launch."""
+        _check_slot(level, p_field)
+        M, point_stride, set_stride = int(M), int(point_stride), int(set_stride)
+        if M < 1 or point_stride < 2 or d_points.numel() < (N - 1) * set_stride + (M - 1) * point_stride + 2:
+            raise ValueError(f"d_points {tuple(d_points.shape)}: want {M} points, {point_stride} doubles apart, sets {set_stride} apart")
+        out = torch.empty((N, _lib.SCORE_STRIDE), dtype=torch.float64, device=self.device)
+        check(self.L.slam2d_score_points(C.byref(level.c), p_field, N, _ptr(d_pose), pose_stride, _ptr(d_points), point_stride, M, set_stride,
+                                         _ptr(out), _stream()), "slam2d_score_points")
+        return out
+
+    def mcl_step_points(self, level, p_field, d_in, d_out, N, motion, amp, seed, scan, d_points, M, outside_cost, d_lut, shift, d_report,
+                        d_ancestor=None, point_stride=2):
+        """``mcl_step`` for a set of points in the robot's frame instead of a scan (include/slam2d.h, slam2d_mcl_step_points): the
+        one set ``d_points`` (``M`` points, ``point_stride`` doubles apart; a row with a NaN or an infinity is dropped) weighs
+        every pose, a valid point that ends outside the field pays ``outside_cost``, and ``in_range`` of the report is the
+        number of valid points.  Five launches on the current stream, no synchronisation; the scratch is kept and grown."""
+        self._mcl("slam2d_mcl_step_points", (), "_mcl_work", self.L.slam2d_mcl_points_work(N), "slam2d_mcl_points_work", level, p_field, N, "N",
+                  _lib.MCL_REPORT, (), d_in, d_out, motion, amp, seed, scan, self._point_source(d_points, M, point_stride), outside_cost, d_lut,
+                  shift, (), d_report, d_ancestor)
+
+    def mcl_step_adaptive_points(self, level, p_field, d_in, d_out, n_cap, d_count, motion, amp, seed, scan, d_points, M, outside_cost, d_lut,
+                                 shift, bins, d_ntab, d_report, d_ancestor=None, d_count_out=None, point_stride=2):
+        """``mcl_step_adaptive`` for a set of points, as ``mcl_step_points`` is ``mcl_step`` for one (include/slam2d.h,
+        slam2d_mcl_step_adaptive_points).  Seven launches on the current stream, no synchronisation."""
+        self._mcl_adaptive("slam2d_mcl_step_adaptive_points", (), "slam2d_mcl_adapt_points_work", level, p_field, d_in, d_out, n_cap, d_count, motion,
+                           amp, seed, scan, self._point_source(d_points, M, point_stride), outside_cost, d_lut, shift, bins, d_ntab, d_report,
+                           d_ancestor, d_count_out)
 
     def grid_update(self, d_pose, stride, d_ranges, d_beam_shift=None):
         self._before_update()

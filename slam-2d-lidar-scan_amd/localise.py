@@ -204,14 +204,18 @@ class Localiser(_OnCover):
         return self.d_pose[self.cur].cpu().numpy()
 
     # ---- the filter ----
-    def _enqueue(self, d_ranges, motion, d_report):
+    def _enqueue(self, source, motion, d_report, points=False):
+        """One step on the device.  ``source``: the scan's ranges, or -- ``points`` -- the set's (d_points, M)."""
         eng, d_in, d_out = self.eng, self.d_pose[self.cur], self.d_pose[1 - self.cur]
+        src = source if points else (source,)
         if self.adaptive is not None:
-            eng.mcl_step_adaptive(self.level, 0, d_in, d_out, self.N, self.d_count, motion, self.amp, self.seed, self.scan, d_ranges,
-                                  self.outside_cost, self.d_lut, self.shift, self.bins, self.d_ntab, d_report, self.d_ancestor)
+            step = eng.mcl_step_adaptive_points if points else eng.mcl_step_adaptive
+            step(self.level, 0, d_in, d_out, self.N, self.d_count, motion, self.amp, self.seed, self.scan, *src,
+                 self.outside_cost, self.d_lut, self.shift, self.bins, self.d_ntab, d_report, self.d_ancestor)
         else:
-            eng.mcl_step(self.level, 0, d_in, d_out, self.N, motion, self.amp, self.seed, self.scan, d_ranges, self.outside_cost, self.d_lut,
-                         self.shift, d_report, self.d_ancestor)
+            step = eng.mcl_step_points if points else eng.mcl_step
+            step(self.level, 0, d_in, d_out, self.N, motion, self.amp, self.seed, self.scan, *src, self.outside_cost, self.d_lut,
+                 self.shift, d_report, self.d_ancestor)
         self.cur = 1 - self.cur
         self.scan += 1
 
@@ -238,8 +242,38 @@ class Localiser(_OnCover):
             host = d_rep.cpu().numpy()
         return [self._decode(row) for row in host]
 
+    def step_points(self, points, motion):
+        """``step`` for a set of points in the robot's frame instead of a scan (slam2d_mcl_step_points, include/slam2d.h):
+        ``points`` is ``[M, 2]`` -- x forward, y to the left, metres; rows with a NaN or an infinity are dropped --, M <=
+        ``_lib.MAX_POINTS``, as the ``points`` module prepares them: several scans merged by odometry, two sensors, a mounted
+        one.  The field is the one the constructor built: a point that ends outside it pays ``outside_cost``.  The same
+        download and the same report, whose ``in_range`` is the number of valid points."""
+        pts = points_of(points)
+        self._enqueue((torch.from_numpy(pts).to(self.eng.device), len(pts)), motion, self.d_report, points=True)
+        return self._decode(self.d_report)
 
-TrackReport = collections.namedtuple("TrackReport", "pose cost start_cost offsets")
+    def run_points(self, point_sets, motions):
+        """A log of point sets: set i, ``[M_i, 2]``, with the motion ``motions[i]`` = (dfwd, dside, dturn) that led to it.  The
+        sets may differ in length: they are padded with NaN rows to the longest.  As in ``run`` every step is enqueued without
+        a synchronisation and ONE download of the reports ends the call.  Returns the list of decoded reports."""
+        sets = [points_of(p) for p in point_sets]
+        motions = [tuple(float(v) for v in m) for m in motions]
+        if not sets or len(motions) != len(sets) or any(len(m) != 3 for m in motions):
+            raise ValueError(f"{len(sets)} point sets and {len(motions)} motions: want one motion of three numbers per set, and a set")
+        M = max(len(p) for p in sets)
+        pts = np.full((len(sets), M, 2), np.nan)
+        for i, p in enumerate(sets):
+            pts[i, :len(p)] = p
+        with pinned_stream():
+            d_pts = torch.from_numpy(pts).to(self.eng.device)
+            d_rep = torch.empty((len(sets), self.d_report.numel()), dtype=torch.int64, device=self.eng.device)
+            for i in range(len(sets)):
+                self._enqueue((d_pts[i], M), motions[i], d_rep[i], points=True)
+            host = d_rep.cpu().numpy()
+        return [self._decode(row) for row in host]
+
+
+TrackReport =collections.namedtuple("TrackReport", "pose cost start_cost offsets")
 
 
 class Tracker(_OnCover):

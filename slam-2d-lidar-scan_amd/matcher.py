@@ -639,6 +639,28 @@ class ScanMatcher:
                             lambda eng, a, b, d_pts, radii, steps, cost, words:
                             eng.refine_points(lv, 0, a, b, N, 3, d_pts, M, 0 if pts.ndim == 2 else 2 * M, radii, steps, cost, d_words=words))
 
+    def scorePoints(self, poses, points, level="fine", window=None, likelihood=None):
+        """``scorePoses`` for a set of points in the robot's frame instead of a scan (include/slam2d.h, slam2d_score_points):
+        ``points`` is ``[M, 2]``, one set for every pose, or ``[N, M, 2]``, a set per pose (rows with a NaN or an infinity are
+        dropped, so sets of different sizes are padded with NaN rows).  The frame is planned as for ``refinePoints`` (the
+        bounding box of the finite poses, or ``window``; the field is ``points_level``'s).  Returns ``scorePoses``' dict with
+        ``valid``, the number of valid points, where that has ``in_range``."""
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        N = len(poses)
+        if N == 0:
+            raise ValueError("no poses")
+        pts = points_of(points, N)
+        M = pts.shape[-2]
+        cx, cy, half = covering_window(poses, window)
+        lv = self.points_level(level, half, pts, likelihood)
+        with self._cover(lv, cx, cy) as (eng, _):
+            rows = eng.score_points(lv, 0, eng.to_device(poses), 3, N, eng.to_device(pts), M, 0 if pts.ndim == 2 else 2 * M)
+            host, = self._download(eng, "scorePoints", rows)
+            self.last_cover = dict(level=lv, window=(cx, cy, half))
+            res = eng.score_host(host)
+        res["valid"] = res.pop("in_range")
+        return res
+
     def searchToMatch(self, probSP, estimatedX, estimatedY, estimatedTheta, rMeasure, xRangeList, yRangeList,
                       searchRadius, searchHalfRad, unitLength, estMovingDist, estMovingTheta, fineSearch=False,
                       matchMax=True):
