@@ -47,6 +47,7 @@ MAX_BLUR_RADIUS = 16
 MAX_BEAMS = 2048
 SPOKE_BAND = 16
 SYNC_WORDS = 4
+SYNC_BOUND_WORD = 59                 # of the groups' 64-word sync block: the bound of the device-side waits in milliseconds (0: 30 s)
 ABI_VERSION = 18
 MATCH_PRUNE_BY_PRIOR = 1
 MATCH_PRIOR_READY = 2

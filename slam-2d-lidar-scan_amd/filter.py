@@ -7,6 +7,7 @@ batch axis of the device state.  Constructor arguments and method names follow t
 reference.  Sharding over several GPUs (one process per GPU) is in ``parallel.py``;
 this class handles the particles of one rank.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -86,7 +87,7 @@ _HOST_WAIT_S = 15.0 + (int(os.environ["SLAM2D_SYNC_TIMEOUT_MS"]) / 1e3 if os.env
 
 
 class _ReportWaiter:
-    """Stands where a torch Event stood in run()'s pending tuple: the scan's report is PUSHED into the pinned host pack by the
+    """The waitable of a scan in flight (_Scan) on the event-free grouped calls, where the one-stream calls have a torch Event: the scan's report is PUSHED into the pinned host pack by the
     device (Slam2dScan.h_seq); synchronize() polls the sequence word from C (GIL released), bounded."""
     __slots__ = ("ptr", "seq")
 
@@ -126,6 +127,216 @@ class _ReadingWindow:
     def __getitem__(self, i):
         self._fill(i)
         return self._buf[i]
+
+
+# the scan in flight of ParticleFilter.run(): its count and reading, the raw heading its odometry step ended at, what to wait on for
+# its report (an event, a _ReportWaiter) and the state of the random stream before the scan's uniforms
+_Scan = collections.namedtuple("_Scan", "count reading raw_heading waitable rng_state")
+
+
+class _OneStreamCalls:
+    """How run() issues a scan on the current stream: slam2d_scan_match, slam2d_scan_commit and an event per scan parity."""
+
+    def __init__(self, pf):
+        self.pf, self.events = pf, [torch.cuda.Event(), torch.cuda.Event()]
+        # a sharded filter commits in three calls around a collective: no device-side abort, no prior folded into the commit
+        self.voids_on_device = self.folds_prior = not pf.sharded
+
+    def stage(self, parity, ranges, uniforms):
+        self.pf._stage_inputs(parity, ranges, uniforms)
+
+    def match(self, reading, prev_raw, dist, has_turn, turn, parity, prior_ready):
+        self.pf._enqueue_match(reading, prev_raw, dist, has_turn, turn, prior_ready)
+
+    def commit(self, abort_mask, parity, next_prior, next_ranges):
+        self.pf._enqueue_commit(abort_mask, next_prior)
+        ev = self.events[parity]
+        ev.record()
+        return ev
+
+    def discard(self, sync_tripped):
+        torch.cuda.current_stream().synchronize()
+        self.pf.engine.flags.zero_()
+
+    def final_flags(self):
+        self.pf.engine.take_flags()    # a bit the last update raised after its launch's snapshot (slam2d_scan_commit) is still there
+
+
+class _GroupedCalls:
+    """How run() issues a scan in particle groups on their own streams: slam2d_groups_match[_begin], slam2d_groups_commit."""
+
+    def __init__(self, pf):
+        if pf._grp is None:
+            pf._setup_groups()
+        self.pf, self.grp = pf, pf._grp
+        self.voids_on_device = not pf.sharded or self.grp.devsync      # (sharded: rank by rank, on the event-free calls only)
+        self.folds_prior = self.grp.devsync
+
+    def stage(self, parity, ranges, uniforms):
+        self.pf._stage_inputs_group(parity, ranges, uniforms)
+
+    def match(self, reading, prev_raw, dist, has_turn, turn, parity, prior_ready):
+        self.pf._enqueue_match_groups(reading, prev_raw, dist, has_turn, turn, parity, prior_ready)
+
+    def commit(self, abort_mask, parity, next_prior, next_ranges):
+        return self.pf._enqueue_commit_groups(abort_mask, parity, next_prior, next_ranges)
+
+    def discard(self, sync_tripped):
+        pf, grp = self.pf, self.grp
+        pf._join_groups()
+        torch.cuda.synchronize(pf.device)
+        grp.flags2.zero_()
+        grp.active = False
+        if sync_tripped and grp.devsync:                 # (every stream is idle: the counters and tickets start from zero again)
+            bound = int(grp.sync[_lib.SYNC_BOUND_WORD].item())
+            grp.sync.zero_()
+            grp.sync[_lib.SYNC_BOUND_WORD] = bound
+            grp.gate_seq = 0
+            torch.cuda.synchronize(pf.device)
+
+    def final_flags(self):
+        """Both buffers of fault bits (a bit an update raised after its launch's snapshot is still there)."""
+        f = self.grp.flags2.cpu().numpy().view(np.uint32)
+        self.grp.flags2.zero_()
+        bad = np.argwhere(f & _lib.FATAL_FLAGS)
+        if bad.size:
+            b, pp = bad[0]
+            raise _lib.Slam2dError(f"particle {int(pp)}: {_lib.describe_flags(int(f[b, pp]) & _lib.FATAL_FLAGS)}")
+
+
+class _Run:
+    """One ParticleFilter.run(): the scan in flight, what the last commit and the last abort left behind, the run's settings, and
+    the steps the loop in ParticleFilter._run is made of."""
+
+    def __init__(self, pf, readings, force_resample, on_scan):
+        self.pf, self.readings, self.force_resample, self.on_scan = pf, readings, force_resample, on_scan
+        self.n_readings = len(readings) if isinstance(readings, (list, tuple)) else None
+        self.stream_rng = pf.rng if pf.rng is not None else np.random
+        grouped = (pf.n_groups > 1 or pf.grouped_single) and pf.lazy_field
+        self.path = _GroupedCalls(pf) if grouped else _OneStreamCalls(pf)
+        # A scan is speculated without knowing whether one of its search windows leaves a map (the reference would grow that map
+        # first, Utils/ScanMatcher_OGBased.py:27): the match raises SLAM2D_F_WINDOW_OUTSIDE_MAP for such a particle and the
+        # commit, told to treat that bit as fatal for the WHOLE scan (abort_mask), does nothing at all on the device.  The host
+        # finds the bit in the scan's report, grows the maps and runs the scan again, step by step.  (Round 2 did not speculate
+        # while any window was within 2.5 m of a map's edge: 39 % of the Intel log's scans.)  Sharded filters commit in three
+        # calls around a collective and keep the conservative rule.
+        # ... Sharded filters on the grouped calls (round 6) void a scan RANK BY RANK: particles are independent, so a rank whose
+        # windows were inside commits its share, and only the normaliser waits -- the voiding rank's groups leave a void partial,
+        # every rank's merge reports the scan as voided and changes nothing; the voiding rank grows and re-issues, the others
+        # answer with another all-gather + merge over the partials they already hold (slam2d_weights_merge_publish_report).  On the
+        # one-stream calls a sharded filter keeps the conservative rule (no speculation near a map's edge).
+        self.abortable = pf.growable and self.path.voids_on_device
+        self.abort_mask = _lib.F_WINDOW_OUTSIDE_MAP if self.abortable else 0
+        self.fold_prior = self.path.folds_prior and os.environ.get("SLAM2D_FILTER_FOLD_PRIOR", "1") != "0"
+        self.reissue = os.environ.get("SLAM2D_FILTER_REISSUE", "1") != "0"
+        self.pending = None                  # the _Scan in flight
+        self.prior_ready = None              # count of the scan whose prior the last commit wrote
+        self.sync_tripped = False            # the last abort was a gate's timeout
+        self.retried = (None, 0)             # (count of the scan last re-issued, how often)
+        self.resamples = []
+
+    def has_reading(self, k):
+        return k < self.n_readings if self.n_readings is not None else self.readings.has(k)
+
+    def was_aborted(self, p):
+        """Wait for scan p's report; True if its commit was a no-op on the device (a window had left a map)."""
+        pf = self.pf
+        p.waitable.synchronize()
+        snap = pf._h_flagsnap.numpy().view(np.uint32)
+        if self.abortable and (snap & self.abort_mask).any():
+            return True
+        if self.abortable and (snap & _lib.F_SCAN_VOIDED).any() and (snap & _lib.F_SYNC_TIMEOUT).any():
+            # a commit's gate gave up waiting for the match's arrivals (a device-side wait ran into its bound: the groups' queues
+            # starved behind another process, a debugger, a hung peer) BEFORE anything of the scan was written: the scan is intact.
+            # It is run again through the calls that wait for nothing on the device, and the sync words start afresh.
+            pf.stats["sync_timeouts"] = pf.stats.get("sync_timeouts", 0) + 1
+            self.sync_tripped = True
+            return True
+        if pf.sharded and self.abortable:
+            while pf._peer_voided():
+                # voided on ANOTHER rank: this rank's commit stands; meet the re-issued scan's partials in another all-gather
+                pf.stats["peer_voids"] = pf.stats.get("peer_voids", 0) + 1
+                pf._sharded_regather().synchronize()
+        pf._check_flag_snapshot()
+        return False
+
+    def judge(self, count):
+        """The reference's degeneracy test after scan `count`, told to on_scan.  Returns whether the reference resamples now."""
+        unb = self.pf.weightUnbalanced()
+        if self.on_scan is not None:
+            self.on_scan(count, self.pf, unb)
+        return unb or count in self.force_resample
+
+    def finish(self, p):
+        """Scan p's results are on the host: bookkeeping + the reference's degeneracy test.  Returns whether the
+        reference resamples after this scan (the caller does it: the random stream may have to be rewound first)."""
+        self.pf._take_report(p.count, p.reading, p.raw_heading)
+        return self.judge(p.count)
+
+    def settle(self, p):
+        """finish(p), and the resample if the reference does one: for a scan with nothing speculated behind it."""
+        if self.finish(p):
+            self.pf._quiesce_groups()
+            self.resamples.append((p.count, self.pf.resample()))
+
+    def plain(self, count, reading):
+        """One scan through the unpipelined calls."""
+        pf = self.pf
+        self.prior_ready = None
+        pf.stats["step_by_step"] += 1
+        pf._quiesce_groups()
+        pf.updateParticles(reading, count)
+        if self.judge(count):
+            self.resamples.append((count, pf.resample()))
+
+    def discard_speculation(self, rng_state):
+        """Throw away what is in flight: its fault flags and its draws from the random stream."""
+        self.prior_ready = None
+        self.path.discard(self.sync_tripped)
+        if rng_state is not None:
+            self.stream_rng.set_state(rng_state)
+
+    def redo_aborted(self, p):
+        """Scan p was voided on the device (and so is everything enqueued after it): back to the random stream's state
+        before its uniforms, then the scan again through the calls that grow the maps."""
+        self.pf.stats["aborted"] = self.pf.stats.get("aborted", 0) + 1
+        self.discard_speculation(p.rng_state)
+        self.plain(p.count, p.reading)
+
+    def recover(self, p):
+        """Scan p was voided, its successor's match is in flight.  True: the maps grew for p and both scans go through the pipeline
+        again; False: p was taken step by step, and its successor has to be.
+
+        A voided scan is re-issued THROUGH THE PIPELINE once the maps have grown for it, as the step-by-step path grows them
+        (Utils/ScanMatcher_OGBased.py:27, once per level): first for the coarse windows, from the poses the host holds; if
+        those were inside already, for the fine windows, from the coarse matched poses the voided commit leaves in the scan's
+        report (its coarse match was the one the step-by-step path would compute: same maps, same inputs, same uniforms).
+        The re-issued coarse match then runs on the grown maps, the reference's on the maps before the growth: the same cells
+        -- growth pads a map with unobserved cells and shifts its low limit by a whole number of cells, and a window's first
+        map column rint((x_lo - lim) / unit) sits an integer away from rounding ties for poses that move in multiples of the
+        match step.  A scan voided three times goes through the step-by-step calls.  (Round 3 ran every voided scan AND its
+        successor step by step: 44 of the Intel log's 910 scans at 0.85 ms each.)  SLAM2D_FILTER_REISSUE=0 restores that."""
+        pf, P = self.pf, self.pf.numParticles
+        pf.stats["redo"] += 1
+        tries = self.retried[1] if self.retried[0] == p.count else 0
+        if self.sync_tripped:                        # a gate's timeout: this scan and its successor through the waiting-free calls
+            self.redo_aborted(p)
+            self.sync_tripped = False
+        elif self.reissue and tries < 2:
+            pf.stats["aborted"] = pf.stats.get("aborted", 0) + 1
+            coarse_xy = pf._h_pack.numpy()[:5 * P].reshape(P, 5)[:, :2].copy()     # (a voided commit reports the coarse poses)
+            self.discard_speculation(p.rng_state)
+            grew = pf._grow_for_windows(pf.prev_matched[:, 0], pf.prev_matched[:, 1], pf.coarse.reach)
+            if not grew:
+                grew = pf._grow_for_windows(coarse_xy[:, 0], coarse_xy[:, 1], pf.fine.reach)
+            if grew:
+                self.retried = (p.count, tries + 1)
+                pf.stats["reissued"] += 1
+                return True
+            self.plain(p.count, p.reading)
+        else:
+            self.redo_aborted(p)
+        return False
 
 
 class ParticleFilter:
@@ -323,8 +534,8 @@ class ParticleFilter:
         rng_in = np.asarray(reading['range'], dtype=np.float64)
         if count == 1 or self.match_max:
             self._stage_inputs(0, rng_in)
+        raw_heading = None
         if count == 1:
-            self.prev_raw_heading = None
             if self.lidar.window_collides(eng.maps[0], reading['x'], reading['y']):
                 # (e.g. an odd number of cells per side with the first pose on the map's centre; the matched poses then stay on
                 # half cells, and the update kernel would flag every scan: SLAM2D_F_UPDATE_CELL_COLLISION)
@@ -333,8 +544,6 @@ class ParticleFilter:
                                        "a map length that is an even number of cells (OccupancyGrid / map_from_poses are exact here)")
             self.d_pose.copy_(torch.tensor([[reading['x'], reading['y'], reading['theta']]] * P, dtype=torch.float64))
             self.d_head.fill_(float("nan"))
-            matched = np.tile([reading['x'], reading['y'], reading['theta']], (P, 1)).astype(np.float64)
-            conf = np.ones(P)
             d_shift = self._grow_for_first_update(reading) if self.growable else None
             eng.grid_update(self.d_pose, 3, self.d_ranges, d_shift)          # :133
             eng.take_flags()
@@ -362,20 +571,34 @@ class ParticleFilter:
             self._normalize_on_device()                             # Algorithm/FastSlam.py:43-48, ahead of weightUnbalanced()
             self._h_pack.copy_(self._d_pack, non_blocking=True)     # poses, confidences, weights, variance
             eng.take_flags()                                        # the one synchronisation of the scan
-            while self.sharded and np.isnan(self._h_pack.numpy()[6 * P]) and self._h_pack.numpy()[6 * P + 1] == -1.0:
+            while self.sharded and self._peer_voided():
                 # another rank voided this scan in its pipelined run() (its groups left the void partial: slam2d.h,
                 # slam2d_weights_merge_publish_report): nothing was merged; gather again -- that rank comes back with the scan
                 self.stats["peer_voids"] = self.stats.get("peer_voids", 0) + 1
                 self._normalizer(self.d_logw, None, 1, self.d_w, self.d_stats, local_done=True)
                 self._h_pack.copy_(self._d_pack, non_blocking=True)
                 torch.cuda.current_stream().synchronize()
+        self._take_report(count, reading, raw_heading)
+
+    def _peer_voided(self):
+        """The merge's void marker in the host pack (slam2d_weights_merge_publish_report): another rank voided the scan."""
+        stats = self._h_pack.numpy()[6 * self.numParticles:]
+        return np.isnan(stats[0]) and stats[1] == -1.0
+
+    def _take_report(self, count, reading, raw_heading):
+        """Scan `count`'s results are on the host -- in the host pack, the first scan's in its reading: the bookkeeping of
+        Particle.update, the same after updateParticles and after a scan of run()'s pipeline."""
+        P = self.numParticles
+        if count == 1:
+            matched = np.tile([reading['x'], reading['y'], reading['theta']], (P, 1)).astype(np.float64)
+            conf = np.ones(P)
+        else:
             rep = self._h_pack.numpy()[:5 * P].reshape(P, 5)
             matched, conf = rep[:, 0:3].copy(), rep[:, 3].copy()
-            self._normalized_step = self.step + 1
-            self.prev_raw_heading = raw_heading
+            self._normalized_step = self.step + 1            # (the commit ran the normaliser: weightUnbalanced reads the pack)
         self.trajectory.append(matched[:, :2].copy())
-        self.prev_matched, self.prev_raw = matched, reading
-        self.last_confidence = conf
+        self.prev_matched, self.prev_raw, self.last_confidence = matched, reading, conf
+        self.prev_raw_heading = raw_heading
         self.step += 1
 
     # ---- the reference's driver loop, pipelined (Algorithm/FastSlam.py:152-162) ----
@@ -404,246 +627,89 @@ class ParticleFilter:
                     pass
 
     def _run(self, readings, first_count, force_resample, on_scan):
-        eng, P = self.engine, self.numParticles
-        # pending = (count, reading, raw_heading, event, state of the random stream before the scan's uniforms) of the scan in flight
-        resamples, pending = [], None
-        events = [torch.cuda.Event(), torch.cuda.Event()]
-        grouped = (self.n_groups > 1 or self.grouped_single) and self.lazy_field
-        if grouped and self._grp is None:
-            self._setup_groups()
-
-        stream_rng = self.rng if self.rng is not None else np.random
-        # A scan is speculated without knowing whether one of its search windows leaves a map (the reference would grow that map
-        # first, Utils/ScanMatcher_OGBased.py:27): the match raises SLAM2D_F_WINDOW_OUTSIDE_MAP for such a particle and the
-        # commit, told to treat that bit as fatal for the WHOLE scan (abort_mask), does nothing at all on the device.  The host
-        # finds the bit in the scan's report, grows the maps and runs the scan again, step by step.  (Round 2 did not speculate
-        # while any window was within 2.5 m of a map's edge: 39 % of the Intel log's scans.)  Sharded filters commit in three
-        # calls around a collective and keep the conservative rule.
-        # ... Sharded filters on the grouped calls (round 6) void a scan RANK BY RANK: particles are independent, so a rank whose
-        # windows were inside commits its share, and only the normaliser waits -- the voiding rank's groups leave a void partial,
-        # every rank's merge reports the scan as voided and changes nothing; the voiding rank grows and re-issues, the others
-        # answer with another all-gather + merge over the partials they already hold (slam2d_weights_merge_publish_report).  On the
-        # one-stream calls a sharded filter keeps the conservative rule (no speculation near a map's edge).
-        abortable = self.growable and (not self.sharded or (grouped and self._grp.devsync))
-        abort_mask = _lib.F_WINDOW_OUTSIDE_MAP if abortable else 0
-
-        sync_tripped = [False]
-
-        def was_aborted(p):
-            """Wait for scan p's report; True if its commit was a no-op on the device (a window had left a map)."""
-            p[3].synchronize()
-            snap = self._h_flagsnap.numpy().view(np.uint32)
-            if abortable and (snap & abort_mask).any():
-                return True
-            if abortable and (snap & _lib.F_SCAN_VOIDED).any() and (snap & _lib.F_SYNC_TIMEOUT).any():
-                # a commit's gate gave up waiting for the match's arrivals (a device-side wait ran into its bound: the groups' queues
-                # starved behind another process, a debugger, a hung peer) BEFORE anything of the scan was written: the scan is intact.
-                # It is run again through the calls that wait for nothing on the device, and the sync words start afresh.
-                self.stats["sync_timeouts"] = self.stats.get("sync_timeouts", 0) + 1
-                sync_tripped[0] = True
-                return True
-            if self.sharded and abortable:
-                while np.isnan(self._h_pack.numpy()[6 * P]) and self._h_pack.numpy()[6 * P + 1] == -1.0:
-                    # voided on ANOTHER rank: this rank's commit stands; meet the re-issued scan's partials in another all-gather
-                    self.stats["peer_voids"] = self.stats.get("peer_voids", 0) + 1
-                    self._sharded_regather().synchronize()
-            self._check_flag_snapshot()
-            return False
-
-        def finish(p):
-            """Scan p's results are on the host: bookkeeping + the reference's degeneracy test.  Returns whether the
-            reference resamples after this scan (the caller does it: the random stream may have to be rewound first)."""
-            count, reading, raw_heading = p[0], p[1], p[2]
-            rep = self._h_pack.numpy()[:5 * P].reshape(P, 5)
-            matched, conf = rep[:, 0:3].copy(), rep[:, 3].copy()
-            self.trajectory.append(matched[:, :2].copy())
-            self.prev_matched, self.prev_raw, self.last_confidence = matched, reading, conf
-            self.prev_raw_heading = raw_heading
-            self.step += 1
-            self._normalized_step = self.step
-            unb = self.weightUnbalanced()
-            if on_scan is not None:
-                on_scan(count, self, unb)
-            return unb or count in force_resample
-
-        # the next scan's pose prior rides in this scan's commit (slam2d_scan_commit_next) when the next reading is at hand:
-        # prior_ready = count of the scan whose prior the last commit wrote (its match then skips the prior's launch)
-        fold_prior = ((not grouped and not self.sharded) or (grouped and self._grp.devsync)) and os.environ.get("SLAM2D_FILTER_FOLD_PRIOR", "1") != "0"
-        prior_ready = [None]
-
-        def plain(count, reading):
-            """One scan through the unpipelined calls."""
-            prior_ready[0] = None
-            self.stats["step_by_step"] += 1
-            self._quiesce_groups()
-            self.updateParticles(reading, count)
-            unb = self.weightUnbalanced()
-            if on_scan is not None:
-                on_scan(count, self, unb)
-            if unb or count in force_resample:
-                resamples.append((count, self.resample()))
-
-        def discard_speculation(rng_state):
-            """Throw away what is in flight: its fault flags and its draws from the random stream."""
-            prior_ready[0] = None
-            if grouped:
-                self._join_groups()
-                torch.cuda.synchronize(self.device)
-                self._grp.flags2.zero_()
-                self._grp.active = False
-                if sync_tripped[0] and self._grp.devsync:          # (every stream is idle: the counters and tickets start from zero again)
-                    bound = int(self._grp.sync[59].item())
-                    self._grp.sync.zero_()
-                    self._grp.sync[59] = bound
-                    self._grp.gate_seq = 0
-                    torch.cuda.synchronize(self.device)
-            else:
-                torch.cuda.current_stream().synchronize()
-                eng.flags.zero_()
-            if rng_state is not None:
-                stream_rng.set_state(rng_state)
-
-        def redo_aborted(p):
-            """Scan p was voided on the device (and so is everything enqueued after it): back to the random stream's state
-            before its uniforms, then the scan again through the calls that grow the maps."""
-            self.stats["aborted"] = self.stats.get("aborted", 0) + 1
-            discard_speculation(p[4])
-            plain(p[0], p[1])
-
-        # A voided scan is re-issued THROUGH THE PIPELINE once the maps have grown for it, as the step-by-step path grows them
-        # (Utils/ScanMatcher_OGBased.py:27, once per level): first for the coarse windows, from the poses the host holds; if
-        # those were inside already, for the fine windows, from the coarse matched poses the voided commit leaves in the scan's
-        # report (its coarse match was the one the step-by-step path would compute: same maps, same inputs, same uniforms).
-        # The re-issued coarse match then runs on the grown maps, the reference's on the maps before the growth: the same cells
-        # -- growth pads a map with unobserved cells and shifts its low limit by a whole number of cells, and a window's first
-        # map column rint((x_lo - lim) / unit) sits an integer away from rounding ties for poses that move in multiples of the
-        # match step.  A scan voided three times goes through the step-by-step calls.  (Round 3 ran every voided scan AND its
-        # successor step by step: 44 of the Intel log's 910 scans at 0.85 ms each.)  SLAM2D_FILTER_REISSUE=0 restores that.
-        reissue = os.environ.get("SLAM2D_FILTER_REISSUE", "1") != "0"
-        retried = (None, 0)                                  # (count of the scan last re-issued, how often)
         if not isinstance(readings, (list, tuple)):
             readings = _ReadingWindow(readings)              # a generator (a live sensor) stays lazy: the loop steps back two items at most
-
-        def has_reading(k):
-            return (k < len(readings)) if isinstance(readings, (list, tuple)) else readings.has(k)
-
+        run = _Run(self, readings, force_resample, on_scan)
+        path, stream_rng = run.path, run.stream_rng
         i = 0
-        while has_reading(i):
+        while run.has_reading(i):
             count, reading = first_count + i, readings[i]
             i += 1
-            if count == 1 or (pending is None and self.prev_raw is None) or not self.lazy_field:
-                assert pending is None
-                plain(count, reading)
+            if count == 1 or (run.pending is None and self.prev_raw is None) or not self.lazy_field:
+                assert run.pending is None
+                run.plain(count, reading)
                 continue
-            if self.growable and not abortable and self.prev_matched is not None:
+            if self.growable and not run.abortable and self.prev_matched is not None:
                 # (no device-side abort: no speculation while some particle's window hugs its map's edge, judged from the poses
                 # the host already has, one or two scans old, with 1 m of slack for the motion since)
                 slack = (self.coarse.ncell + 1) * self.coarse.step + 1.0
                 if self._outside(self.prev_matched[:, 0], self.prev_matched[:, 1], self.coarse.reach + slack).size:
-                    if pending is not None:
-                        prev_count = pending[0]
-                        was_aborted(pending)
-                        if finish(pending):
-                            self._quiesce_groups()
-                            resamples.append((prev_count, self.resample()))
-                        pending = None
-                    plain(count, reading)
+                    if run.pending is not None:
+                        run.was_aborted(run.pending)
+                        run.settle(run.pending)
+                        run.pending = None
+                    run.plain(count, reading)
                     continue
             parity = count & 1
-            if pending is None:
+            prev, run.pending = run.pending, None
+            if prev is None:
                 prev_raw, prev_raw_heading = self.prev_raw, self.prev_raw_heading
             else:
-                prev_raw, prev_raw_heading = pending[1], pending[2]
+                prev_raw, prev_raw_heading = prev.reading, prev.raw_heading
             dist, raw_heading, has_turn, turn = self._raw_odometry(reading, prev_raw, prev_raw_heading)
             rng_state = stream_rng.get_state()
             state_before = rng_state
-            if grouped:
-                self._stage_inputs_group(parity, np.asarray(reading['range'], dtype=np.float64), None if self.match_max else self._draw_uniforms())
-                self._enqueue_match_groups(reading, prev_raw, dist, has_turn, turn, parity, prior_ready[0] == count)
-            else:
-                self._stage_inputs(parity, np.asarray(reading['range'], dtype=np.float64), None if self.match_max else self._draw_uniforms())
-                self._enqueue_match(reading, prev_raw, dist, has_turn, turn, prior_ready[0] == count)   # speculative: scan count-1 not seen yet
+            path.stage(parity, np.asarray(reading['range'], dtype=np.float64), None if self.match_max else self._draw_uniforms())
+            path.match(reading, prev_raw, dist, has_turn, turn, parity, run.prior_ready == count)   # speculative: scan count-1 not seen yet
             redo = False
-            if pending is not None:
-                prev_count = pending[0]
-                if was_aborted(pending):
+            if prev is not None:
+                if run.was_aborted(prev):
                     # scan count-1 did not happen on the device: redo it (with the growth it needs), then this scan, whose
                     # speculative match started from a state that never was
-                    p, pending = pending, None
-                    self.stats["redo"] += 1
-                    tries = retried[1] if retried[0] == p[0] else 0
-                    if sync_tripped[0]:                        # a gate's timeout: this scan and its successor through the waiting-free calls
-                        redo_aborted(p)
-                        sync_tripped[0] = False
-                    elif reissue and tries < 2:
-                        self.stats["aborted"] = self.stats.get("aborted", 0) + 1
-                        coarse_xy = self._h_pack.numpy()[:5 * P].reshape(P, 5)[:, :2].copy()     # (a voided commit reports the coarse poses)
-                        discard_speculation(p[4])
-                        grew = self._grow_for_windows(self.prev_matched[:, 0], self.prev_matched[:, 1], self.coarse.reach)
-                        if not grew:
-                            grew = self._grow_for_windows(coarse_xy[:, 0], coarse_xy[:, 1], self.fine.reach)
-                        if grew:
-                            retried = (p[0], tries + 1)
-                            self.stats["reissued"] += 1
-                            i -= 2                              # both scans again, speculatively
-                            continue
-                        plain(p[0], p[1])
+                    if run.recover(prev):
+                        i -= 2                                  # both scans again, speculatively
                     else:
-                        redo_aborted(p)
-                    plain(count, reading)
+                        run.plain(count, reading)
                     continue
-                if finish(pending):
+                if run.finish(prev):
                     # the reference draws the resample indices BEFORE this scan's uniforms: rewind, resample, redo the scan
                     stream_rng.set_state(rng_state)
                     self._quiesce_groups()                      # (the speculative match of this scan reads the maps a resample moves)
                     idx = self.resample()
-                    resamples.append((prev_count, idx))
+                    run.resamples.append((prev.count, idx))
                     rng_state = None
                     # ... unless the draw moved nothing (always so with one particle, whose degeneracy test is always true,
                     # Algorithm/FastSlam.py:37) and the speculative match consumed no uniform (match_max): it stands as it is
                     redo = not (self.match_max and np.array_equal(np.asarray(idx), np.arange(self.total_particles)))
                     if not redo:
                         state_before = stream_rng.get_state()
-                pending = None
-            if not abortable:
+            if not run.abortable:
                 est_xy = self.prev_matched
                 margin = (self.coarse.ncell + 1) * self.coarse.step
                 if not redo and self.growable and self._outside(est_xy[:, 0], est_xy[:, 1], self.coarse.reach + margin).size:
                     redo = True                                                     # a window may leave a map: grow, step by step
             if redo:
                 self.stats["redo"] += 1
-                discard_speculation(rng_state)
-                plain(count, reading)
+                run.discard_speculation(rng_state)
+                run.plain(count, reading)
                 continue
+            # the next scan's pose prior rides in this scan's commit (slam2d_scan_commit_next) when the next reading is at hand:
+            # prior_ready = count of the scan whose prior the last commit wrote (its match then skips the prior's launch)
             nxt = None
-            if fold_prior and has_reading(i):
+            if run.fold_prior and run.has_reading(i):
                 _, _, n_has_turn, n_turn = self._raw_odometry(readings[i], reading, raw_heading)
                 nxt = (float(readings[i]['theta']), float(reading['theta']), int(n_has_turn), float(n_turn))
-                prior_ready[0] = count + 1
-            if grouped:
-                ev = self._enqueue_commit_groups(abort_mask, parity, nxt, readings[i]['range'] if nxt is not None else None)
+                run.prior_ready = count + 1
+            waitable = path.commit(run.abort_mask, parity, nxt, readings[i]['range'] if nxt is not None else None)
+            run.pending = _Scan(count, reading, raw_heading, waitable, state_before)
+        if run.pending is not None:
+            if run.was_aborted(run.pending):
+                run.redo_aborted(run.pending)
             else:
-                self._enqueue_commit(abort_mask, nxt)
-                ev = events[parity]
-                ev.record()
-            pending = (count, reading, raw_heading, ev, state_before)
-        if pending is not None:
-            if was_aborted(pending):
-                redo_aborted(pending)
-            elif finish(pending):
-                self._quiesce_groups()
-                resamples.append((pending[0], self.resample()))
+                run.settle(run.pending)
         self._quiesce_groups()
-        if grouped:             # both buffers of fault bits (a bit an update raised after its launch's snapshot is still there)
-            f = self._grp.flags2.cpu().numpy().view(np.uint32)
-            self._grp.flags2.zero_()
-            bad = np.argwhere(f & _lib.FATAL_FLAGS)
-            if bad.size:
-                b, pp = bad[0]
-                raise _lib.Slam2dError(f"particle {int(pp)}: {_lib.describe_flags(int(f[b, pp]) & _lib.FATAL_FLAGS)}")
-        else:
-            eng.take_flags()    # a bit the last update raised after its launch's snapshot (slam2d_scan_commit) is still there
-        return resamples
+        path.final_flags()
+        return run.resamples
 
     # ---- particle groups on streams (run() only): slam2d_groups_match / slam2d_groups_commit ----
     def _setup_groups(self):
@@ -708,8 +774,8 @@ class ParticleFilter:
             sc.ev_inputs = sc.ev_merged = sc.norm_stream = None
             sc.d_norm_sync = grp.sync.data_ptr()
             ms = os.environ.get("SLAM2D_SYNC_TIMEOUT_MS", "")
-            if ms.isdigit():                             # the bound of the device-side waits (word 59; default 30 s)
-                grp.sync[59] = int(ms)
+            if ms.isdigit():                             # the bound of the device-side waits (default 30 s)
+                grp.sync[_lib.SYNC_BOUND_WORD] = int(ms)
             if not self.sharded:                         # (sharded: the merge on the normaliser's stream pushes the report, slam2d_weights_merge_publish_report)
                 sc.h_seq, sc.h_pack, sc.d_pack = grp.h_seq.data_ptr(), self._h_pack.data_ptr(), self._d_pack.data_ptr()
                 sc.pack_doubles = self._d_pack.numel()
