@@ -517,6 +517,57 @@ int slam2d_score_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int32
                        const double* d_ranges, int32_t ranges_stride,
                        double* d_out, void* stream);
 
+/* A geometric ray in a field's own frame, for any number of free poses, and the first cost built on it: the range a field expects
+ * at a pose, per beam (slam2d_cast_rays), and slam2d_search_lattice's cost plus a charge per beam whose measured range lies beyond
+ * a wall of the field (slam2d_score_rays) -- the endpoint model charges a beam only where it ends, so a pose on the wrong side of a
+ * wall pays nothing for the beams it sends through it (Thrun, Burgard, Fox, Probabilistic Robotics, 6.3-6.4).  Not
+ * slam2d_predict_scan, which is the map update's inverse on the sensor's spoke tables (map resolution, heading quantised to a
+ * spoke, one wave per beam).  Added symbols: no struct and no existing signature changed, the ABI number stays.
+ * Read by both calls: level->frames[p_field] (xlo, ylo, fh, fw), level->step, fmax, fpitch; of `lidar` beams, fov, max_range;
+ * d_dist2, the image slam2d_field_build_distance wrote for the same slot and frame: uint32, cell (i, j) of slot p at
+ * (p * fmax + i) * fpitch + j.  slam2d_score_rays also reads that slot of level->field.  Nothing else of `lidar` or `level` is read.
+ * PRECONDITION: d_dist2 was made with lut_n >= 2 -- then a value of 0 means occupied and nothing else does, and any clamped
+ * value v is a lower bound on the true squared distance --, on this stream or ordered in front of the call, and nothing has
+ * written the slot's frame since (slam2d_score_rays: nor its field; any FULL build may have made the field, on the same frame).
+ * THE RAY of pose n = (x, y, theta) at d_pose[n * pose_stride + 0..2] and beam b: a_b as in step 1 of slam2d_score_poses,
+ * c = cos(a_b), s = sin(a_b); sample k = 0, 1, 2, ..., every operation rounded, in this order, no contraction:
+ *     t = (double)k * step,  px = x + c * t,  py = y + s * t,  qx = (px - xlo) / step,  qy = (py - ylo) / step
+ * A sample is INSIDE iff 0 <= qx < 1e9 and 0 <= qy < 1e9 (a NaN fails) and (int)qx < fw and (int)qy < fh; its cell is
+ * ((int)qy, (int)qx).  Note the `0 <=`: a sample with a quotient in (-1, 0) is OUTSIDE, where the endpoint rule of
+ * slam2d_score_poses truncates such a quotient into cell 0 -- on purpose: every ray cell is a unit square, which the kernel's
+ * skips over provably free samples need.  The ray ENDS at the first sample that is not inside (LEFT at
+ * that k) or at the first inside sample whose cell is occupied (HIT at that k); a ray that reaches its limit K with neither is
+ * NONE.  A pose with a non-finite component is LEFT at 0.  No access leaves [0, fh) x [0, fw), and no quotient that fails the
+ * guard is converted to an integer.  Integer results: the same inputs give the same bits on every call, whatever the clamp of
+ * d_dist2 (it changes which samples are examined, never the answer).
+ * slam2d_cast_rays: d_out[n * beams + b] = kind << 30 | k, kind SLAM2D_RAY_HIT (0), SLAM2D_RAY_LEFT (1), or SLAM2D_RAY_NONE (2)
+ * with k = K + 1; 0 <= K < 2^20.  ONE launch on `stream`, a wave per 64 beams of a pose; no allocation, no fault bit, no
+ * synchronisation.  SLAM2D_E_BADARG, before any HIP call: a NULL lidar, level, d_dist2, d_pose or d_out, a level without frames,
+ * N <= 0, p_field < 0, pose_stride < 3, K < 0, beams < 1 or > SLAM2D_MAX_BEAMS, !(max_range > 0), !(step > 0), fmax <= 0 or
+ * fpitch < fmax; SLAM2D_E_TOOLARGE: K >= 2^20, fmax * fpitch >= 2^29, N * ceil(beams / 64) waves exceed one launch (fewer than
+ * 2^32 threads).
+ * slam2d_score_rays: for pose n and its scan at d_ranges + n * ranges_stride (0: one scan for all poses; >= beams: a scan per
+ * pose), steps 1-4 of slam2d_score_poses give IN RANGE, INSIDE and sum_b exactly as they do there.  A beam in range is CHECKED iff
+ * its quotient r_b / step (one true division) lies in [0, 1e9); then kend = (int64)(r_b / step) - margin, margin >= 0, and the
+ * beam is THROUGH iff kend >= 0 and its ray is HIT at some k <= kend; depth_b = kend - k_hit of a through beam.
+ *     cost = sum_b + (uint64)(in_range - inside) * outside_cost + (uint64)through * through_cost            (below 2^53)
+ *     d_out[n * SLAM2D_RAYS_STRIDE + 0..7] = (double)cost, (double)sum_b, inside, in_range, through, checked, sum of depth_b, 0
+ * With through_cost == 0 the cost is slam2d_search_lattice's.  ONE launch on `stream`, a wave per pose (slam2d_score_poses'
+ * shape); the sums of a pose are joined as integers, no atomic; no allocation, no fault bit, no synchronisation.
+ * SLAM2D_E_BADARG, before any HIP call: the cases of slam2d_cast_rays but K's, a level without a field, a NULL d_ranges,
+ * ranges_stride neither 0 nor >= beams, margin < 0; SLAM2D_E_TOOLARGE: fmax * fpitch >= 2^29, the poses exceed one launch (4
+ * poses per 256 threads, fewer than 2^32 threads). */
+#define SLAM2D_RAYS_STRIDE 8
+#define SLAM2D_RAY_HIT  0u
+#define SLAM2D_RAY_LEFT 1u
+#define SLAM2D_RAY_NONE 2u
+#define SLAM2D_RAY_MAX_K (1 << 20)
+int slam2d_cast_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t N,
+                     const double* d_pose, int32_t pose_stride, int32_t K, uint32_t* d_out, void* stream);
+int slam2d_score_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t N,
+                      const double* d_pose, int32_t pose_stride, const double* d_ranges, int32_t ranges_stride,
+                      int32_t margin, uint32_t outside_cost, uint32_t through_cost, double* d_out, void* stream);
+
 /* The best heading and its cost at every position of a lattice of poses, for one scan in a level's field: the global search
  * built on slam2d_score_poses' definition, on the device from the lattice's nine numbers to a [ny][nx] image -- no pose is
  * uploaded, nothing is stored per pose (an added symbol: no struct and no existing signature changed, the ABI number stays).

@@ -56,7 +56,10 @@ BNB_MARGIN = 30.0
 MOMENTS_STRIDE = 16                  # doubles per particle of slam2d_match_moments' output row
 PREDICT_STRIDE = 4                   # doubles per (pose, beam) of slam2d_predict_scan's output: r_hit, r_far, n_hit, 0
 SCORE_STRIDE = 8                     # doubles per pose of slam2d_score_poses' output: score, |U|, beam score, inside, in range, sum_u, sum_b, 0
-SEARCH_CHUNK = 8                     # headings per block row of slam2d_search_lattice's search launch, at least (csrc: SEARCH_CHUNK)
+RAYS_STRIDE = 8                      # doubles per pose of slam2d_score_rays' output: cost, sum_b, inside, in range, through, checked, depth, 0
+RAY_HIT, RAY_LEFT, RAY_NONE = 0, 1, 2    # the kind in bits 30-31 of a word of slam2d_cast_rays, the sample index k below it
+RAY_MAX_K = 1 << 20                  # slam2d_cast_rays: K stays below it
+SEARCH_CHUNK = 8                    # headings per block row of slam2d_search_lattice's search launch, at least (csrc: SEARCH_CHUNK)
 SEARCH_WAVES = 4096                  # ... and more where fewer than this many waves of 64 positions would not fill the card otherwise
 REFINE_STRIDE = 2                    # 64-bit words per seed of slam2d_refine_poses' output: cost << 20 | candidate, the seed's own cost
 REFINE_MAX_CANDIDATES = 1 << 20      # most candidates (nx * ny * nth) of one seed
@@ -192,6 +195,9 @@ SIGNATURES = {
     "slam2d_grid_update": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "slam2d_predict_scan": (C.c_int, [C.POINTER(Slam2dLidar), _vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_double, C.c_double, _vp, _vp]),
     "slam2d_score_poses": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
+    "slam2d_cast_rays": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    "slam2d_score_rays": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32,
+                                    C.c_int32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "slam2d_search_lattice": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_uint32, _vp, _vp, _vp]),
     "slam2d_search_lattice_work": (C.c_int64, [C.POINTER(Slam2dLidar), C.c_int32, C.c_int32, C.c_int32]),

@@ -4510,8 +4510,156 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_score_poses(Slam2dLidar li
     }
 }
 
+// ---- a geometric ray in a field's frame (slam2d_cast_rays, slam2d_score_rays): include/slam2d.h states the ray, DESIGN.md
+// section 4 proves the skip rule ----
+#define RAY_WAVES 4                  // waves per block of both kernels: a wave is 64 beams of a pose (cast) or a pose (score)
+
+// What a ray reads of its slot: the frame's origin and clipped size, the step, the slot's squared-distance image
+struct RayField { double xlo, ylo, step; int fw, fh, pitch; const uint32_t* __restrict__ d2; };
+__device__ __forceinline__ RayField ray_field(const Slam2dLevel& lv, const int p_field, const uint32_t* __restrict__ dist2) {
+    const Slam2dFrame fr = lv.frames[p_field];
+    const FieldSize fs = frame_clip(lv, fr);
+    return RayField{fr.xlo, fr.ylo, lv.step, fs.fw, fs.fh, lv.fpitch, dist2 + (size_t)p_field * lv.fmax * lv.fpitch};
+}
+
+// Sample k of the ray from (x, y) along (c, s): INSIDE or not, and its cell.  One rounded operation at a time, in the header's
+// order; a quotient that fails the guard -- a NaN, a negative one: the `0 <=` is the ray's, not the endpoint's -- never reaches
+// the conversion.
+__device__ __forceinline__ bool ray_sample(const RayField& f, const double x, const double y, const double c, const double s, const int k,
+                                           int& cx, int& cy) {
+    const double t = (double)k * f.step;
+    const double px = x + c * t, py = y + s * t;
+    const double qx = (px - f.xlo) / f.step, qy = (py - f.ylo) / f.step;
+    if (!(qx >= 0.0 && qx < 1e9 && qy >= 0.0 && qy < 1e9)) return false;
+    cx = (int)qx;
+    cy = (int)qy;
+    return cx < f.fw && cy < f.fh;
+}
+
+// floor(sqrt(v)) of a 32-bit value: the float root is within one of it, and one step either way settles it
+__device__ __forceinline__ uint32_t ray_isqrt(const uint32_t v) {
+    uint32_t d = (uint32_t)__fsqrt_rn((float)v);
+    d = min(d, 65535u);
+    if (d * d > v) --d;
+    else if (d < 65535u && (d + 1u) * (d + 1u) <= v) ++d;
+    return d;
+}
+
+// The ray of one lane up to sample `limit` (0 <= limit < 2^30): kind << 30 | k as slam2d_cast_rays writes it.  Every lane of the
+// wave calls it; a lane with !active walks nothing and gets RAY_NONE.
+//   Frame exit: every operation of the sample formula is monotone in k, so the inside samples of a ray are one interval of k;
+// with sample 0 inside, its end k_exit is found by bisection -- arithmetic only -- and the walk runs on [0, min(limit + 1,
+// k_exit)) without ever looking for the first outside sample.
+//   Skip rule: at an examined sample in a cell of value v > 0, D = isqrt(v), no sample before k + max(1, D - 1) can lie in an
+// occupied cell (samples are one cell apart, a sample within 0.7072 of its cell's centre), so that is the next one examined.
+//   The loop is wave-uniform: it ends when no lane is live, finished lanes idle.  A ray is a chain of dependent 4-byte gathers.
+__device__ __forceinline__ uint32_t ray_walk(const RayField& f, const double x, const double y, const double c, const double s, const int limit,
+                                             const bool active) {
+    int cx = 0, cy = 0;
+    uint32_t word = (SLAM2D_RAY_NONE << 30) | (uint32_t)(limit + 1);
+    bool live = active;
+    int k_exit = limit + 1;
+    if (live && !ray_sample(f, x, y, c, s, 0, cx, cy)) {                            // (a non-finite pose ends here too)
+        word = SLAM2D_RAY_LEFT << 30;
+        live = false;
+    }
+    if (live) {
+        int lo = 0;                                                              // (inside), k_exit: outside, or limit + 1
+        while (k_exit - lo > 1) {
+            const int mid = lo + ((k_exit - lo) >> 1);
+            int ux, uy;
+            if (ray_sample(f, x, y, c, s, mid, ux, uy)) lo = mid; else k_exit = mid;
+        }
+        if (k_exit <= limit) word = (SLAM2D_RAY_LEFT << 30) | (uint32_t)k_exit;
+    }
+    int k = 0;
+    while (__ballot(live)) {
+        if (live) {
+            const uint32_t v = f.d2[(size_t)cy * f.pitch + cx];                  // (cx, cy): sample k, inside
+            if (v == 0u) {
+                word = (SLAM2D_RAY_HIT << 30) | (uint32_t)k;
+                live = false;
+            } else {
+                const uint32_t d = ray_isqrt(v);
+                k += d > 2u ? (int)d - 1 : 1;
+                live = k < k_exit && ray_sample(f, x, y, c, s, k, cx, cy);        // (k < k_exit is inside: the guard runs all the same)
+            }
+        }
+    }
+    return word;
+}
+
+// slam2d_cast_rays: wave w of the launch is beams 64 g .. 64 g + 63 of pose n, w = n * groups + g; a lane per beam.
+__global__ __launch_bounds__(64 * RAY_WAVES) void k_cast_rays(Slam2dLidar lid, Slam2dLevel lv, int p_field, const uint32_t* __restrict__ dist2,
+                                                              int N, int groups, const double* __restrict__ pose, int pstride, int K,
+                                                              uint32_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * RAY_WAVES + (threadIdx.x >> 6);
+    if (w >= (long long)N * groups) return;                                      // (wave-uniform)
+    const int n = (int)(w / groups), b = (int)(w % groups) * 64 + lane;
+    const RayField f = ray_field(lv, p_field, dist2);
+    const double x = pose[(size_t)n * pstride], y = pose[(size_t)n * pstride + 1], th = pose[(size_t)n * pstride + 2];
+    const bool active = b < lid.beams;
+    const double a = fan_of(lid, th).angle(active ? b : 0);
+    const uint32_t word = ray_walk(f, x, y, cos(a), sin(a), K, active);
+    if (active) out[(size_t)n * lid.beams + b] = word;
+}
+
+// slam2d_score_rays: k_score_poses' shape -- a wave per pose, beams interleaved over the lanes -- without its hash set: the
+// endpoint lookup of steps 1-4, then the ray of every CHECKED beam with kend >= 0 up to kend.  A pose is one wave, so its
+// integer sums are joined by the DPP wave reduction alone; lane 0 writes the row.
+__global__ __launch_bounds__(64 * RAY_WAVES) void k_score_rays(Slam2dLidar lid, Slam2dLevel lv, int p_field, const uint32_t* __restrict__ dist2,
+                                                               int N, const double* __restrict__ pose, int pstride,
+                                                               const double* __restrict__ ranges, int rstride, int margin,
+                                                               uint32_t outside_cost, uint32_t through_cost, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * RAY_WAVES + (threadIdx.x >> 6);
+    if (n >= N) return;                                                          // (wave-uniform)
+    const RayField f = ray_field(lv, p_field, dist2);
+    const uint32_t* __restrict__ field = lv.field + (size_t)p_field * lv.fmax * lv.fpitch;
+    const double x = pose[(size_t)n * pstride], y = pose[(size_t)n * pstride + 1], th = pose[(size_t)n * pstride + 2];
+    const double* __restrict__ rg = ranges + (size_t)n * rstride;
+    const int B = lid.beams;
+    const BeamFan fan = fan_of(lid, th);
+    unsigned long long sum_b = 0ull, sum_depth = 0ull;                           // (this lane's share)
+    int n_in = 0, n_rng = 0, n_thr = 0, n_chk = 0;                               // (the wave's counts: ballots)
+    for (int b0 = 0; b0 < B; b0 += 64) {                                         // (wave-uniform trip count)
+        const int b = b0 + lane;
+        const double r = b < B ? rg[b] : NAN;
+        const bool in_range = r < lid.max_range;                                 // (NaN and +inf are out, 0 and negatives in)
+        const double a = fan.angle(b < B ? b : 0);
+        const double c = cos(a), s = sin(a);
+        bool inside = false;
+        if (in_range) {
+            int cx, cy;
+            if (score_cell(x + c * r, y + s * r, f.xlo, f.ylo, f.step, f.fw, f.fh, cx, cy)) {
+                inside = true;
+                sum_b += field[(size_t)cy * f.pitch + cx];
+            }
+        }
+        const double q = r / f.step;
+        const bool checked = in_range && q >= 0.0 && q < 1e9;
+        const long long kend = checked ? (long long)q - margin : -1ll;
+        const uint32_t word = ray_walk(f, x, y, c, s, kend >= 0 ? (int)kend : 0, kend >= 0);
+        const bool through = kend >= 0 && (word >> 30) == SLAM2D_RAY_HIT;           // (a HIT lies at k <= the limit, kend)
+        if (through) sum_depth += (unsigned long long)(kend - (long long)(word & 0x3fffffffu));
+        n_rng += __popcll(__ballot(in_range));
+        n_in += __popcll(__ballot(inside));
+        n_chk += __popcll(__ballot(checked));
+        n_thr += __popcll(__ballot(through));
+    }
+    sum_b = wave64_sum_u64(sum_b);
+    sum_depth = wave64_sum_u64(sum_depth);
+    if (lane == 0) {
+        const unsigned long long cost = sum_b + (unsigned long long)(n_rng - n_in) * outside_cost + (unsigned long long)n_thr * through_cost;
+        double* o = out + (size_t)n * SLAM2D_RAYS_STRIDE;
+        o[0] = (double)cost; o[1] = (double)sum_b; o[2] = (double)n_in; o[3] = (double)n_rng;
+        o[4] = (double)n_thr; o[5] = (double)n_chk; o[6] = (double)sum_depth; o[7] = 0.0;
+    }
+}
+
 // ---- the best heading and its cost at every position of a lattice of poses (slam2d_search_lattice) ----
-#define SEARCH_CHUNK 8               // headings one block row takes at least (tests/test_gpu_search.py names it)
+#define SEARCH_CHUNK 8              // headings one block row takes at least (tests/test_gpu_search.py names it)
 #define SEARCH_UNROLL 4              // beams of one trip of the search's inner loop: their table entries and gathers are in flight together
 #define SEARCH_WAVES 4096            // waves that fill the card: 256 CUs x 4 SIMDs x 4; windows with fewer split their headings further
 
@@ -6424,6 +6572,46 @@ int slam2d_score_points(const Slam2dLevel* level, int32_t p_field, int32_t N, co
     if (blocks * (64 * waves) > 0xffffffffll) return SLAM2D_E_TOOLARGE;           // (a launch holds fewer than 2^32 threads)
     k_score_points<<<(unsigned)blocks, 64 * waves, (size_t)waves * hsize * sizeof(int), (hipStream_t)stream>>>(
         *level, p_field, N, hsize, d_pose, pose_stride, d_points, point_stride, M, set_stride, d_out);
+    return launch_status();
+}
+
+// What the two ray calls ask of their lidar and level (they read beams, fov, max_range; frames, step, fmax, fpitch): every
+// SLAM2D_E_BADARG in front of the one SLAM2D_E_TOOLARGE, as in check_level_field
+static int check_ray_field(const Slam2dLidar* lidar, const Slam2dLevel* level, int p_field) {
+    if (!lidar || lidar->beams < 1 || lidar->beams > SLAM2D_MAX_BEAMS || !(lidar->max_range > 0.0)) return SLAM2D_E_BADARG;
+    if (!level || !level->frames || p_field < 0 || !(level->step > 0.0)) return SLAM2D_E_BADARG;   // (the negated forms refuse a NaN)
+    if (level->fmax <= 0 || level->fpitch < level->fmax) return SLAM2D_E_BADARG;
+    if ((long long)level->fmax * level->fpitch >= (1ll << 29)) return SLAM2D_E_TOOLARGE;
+    return 0;
+}
+
+int slam2d_cast_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t N,
+                     const double* d_pose, int32_t pose_stride, int32_t K, uint32_t* d_out, void* stream) {
+    const int rc = check_ray_field(lidar, level, p_field);
+    if (rc == SLAM2D_E_BADARG) return rc;
+    if (!d_dist2 || !d_pose || !d_out || N <= 0 || pose_stride < 3 || K < 0) return SLAM2D_E_BADARG;
+    if (rc) return rc;
+    if (K >= SLAM2D_RAY_MAX_K) return SLAM2D_E_TOOLARGE;
+    const int groups = cdiv(lidar->beams, 64);
+    const long long blocks = ((long long)N * groups + RAY_WAVES - 1) / RAY_WAVES;
+    if (blocks * (64 * RAY_WAVES) > 0xffffffffll) return SLAM2D_E_TOOLARGE;       // (a launch holds fewer than 2^32 threads)
+    k_cast_rays<<<(unsigned)blocks, 64 * RAY_WAVES, 0, (hipStream_t)stream>>>(*lidar, *level, p_field, d_dist2, N, groups, d_pose, pose_stride, K,
+                                                                              d_out);
+    return launch_status();
+}
+
+int slam2d_score_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t N,
+                      const double* d_pose, int32_t pose_stride, const double* d_ranges, int32_t ranges_stride, int32_t margin,
+                      uint32_t outside_cost, uint32_t through_cost, double* d_out, void* stream) {
+    const int rc = check_ray_field(lidar, level, p_field);
+    if (rc == SLAM2D_E_BADARG) return rc;
+    if (!level->field || !d_dist2 || !d_pose || !d_ranges || !d_out || N <= 0 || pose_stride < 3 || margin < 0) return SLAM2D_E_BADARG;
+    if (ranges_stride != 0 && ranges_stride < lidar->beams) return SLAM2D_E_BADARG;
+    if (rc) return rc;
+    const long long blocks = ((long long)N + RAY_WAVES - 1) / RAY_WAVES;
+    if (blocks * (64 * RAY_WAVES) > 0xffffffffll) return SLAM2D_E_TOOLARGE;       // (a launch holds fewer than 2^32 threads)
+    k_score_rays<<<(unsigned)blocks, 64 * RAY_WAVES, 0, (hipStream_t)stream>>>(*lidar, *level, p_field, d_dist2, N, d_pose, pose_stride, d_ranges,
+                                                                               ranges_stride, margin, outside_cost, through_cost, d_out);
     return launch_status();
 }
 

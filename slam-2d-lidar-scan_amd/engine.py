@@ -1320,6 +1320,52 @@ class ParticleEngine:
         return dict(score=r[:, 0].copy(), cells=r[:, 1].astype(np.int64), beam_score=r[:, 2].copy(), inside=inside, in_range=in_range,
                     outside=in_range - inside)
 
+    def cast_rays(self, level, p_field, d_dist2, d_pose, pose_stride, N, K):
+        """The range slot ``p_field`` of ``level`` expects at N free poses ``d_pose[n * pose_stride + 0..2]``, per beam: a
+        geometric ray in the field's own frame, sampled every ``level.step`` up to sample ``K`` (include/slam2d.h,
+        slam2d_cast_rays).  ``d_dist2``: what ``field_build_distance(..., dist2=True)`` returned for that level and frame, from a
+        table of at least two entries.  ``[N, beams]`` int32 words on the device, kind << 30 | k; one launch on the current
+        stream; ``cast_host`` decodes."""
+        _check_slot(level, p_field)
+        out = torch.empty((N, self.lidar.beams), dtype=torch.int32, device=self.device)
+        check(self.L.slam2d_cast_rays(C.byref(self.lidar_c), C.byref(level.c), p_field, _ptr(d_dist2), N, _ptr(d_pose), pose_stride,
+                                      int(K), _ptr(out), _stream()), "slam2d_cast_rays")
+        return out
+
+    @staticmethod
+    def cast_host(words, step):
+        """Words of ``cast_rays`` as a dict of host arrays shaped like ``words``: ``kind`` (``_lib.RAY_HIT``, ``RAY_LEFT``,
+        ``RAY_NONE``), ``k`` (the sample the ray ended at; K + 1 for RAY_NONE) and ``range`` = k * step where the ray hit a
+        wall, ``inf`` elsewhere."""
+        w = np.ascontiguousarray(_host(words)).view(np.uint32)
+        kind, k = (w >> np.uint32(30)).astype(np.int64), (w & np.uint32(0x3fffffff)).astype(np.int64)
+        return dict(kind=kind, k=k, range=np.where(kind == _lib.RAY_HIT, k * float(step), np.inf))
+
+    def score_rays(self, level, p_field, d_dist2, d_pose, pose_stride, N, d_ranges, ranges_stride, margin, outside_cost, through_cost):
+        """``search_lattice``'s cost of a scan at N free poses plus ``through_cost`` for every beam whose measured range lies more
+        than ``margin`` samples beyond a wall of the field (include/slam2d.h, slam2d_score_rays): ``[N, RAYS_STRIDE]`` on the
+        device.  ``d_dist2`` as in ``cast_rays``, of the frame the slot's field stands on; ``ranges_stride`` 0: the one scan
+        ``d_ranges[0..beams)`` for every pose; >= beams: a scan per pose.  One launch on the current stream; ``rays_host``
+        unpacks the rows."""
+        _check_slot(level, p_field)
+        out = torch.empty((N, _lib.RAYS_STRIDE), dtype=torch.float64, device=self.device)
+        check(self.L.slam2d_score_rays(C.byref(self.lidar_c), C.byref(level.c), p_field, _ptr(d_dist2), N, _ptr(d_pose), pose_stride,
+                                       _ptr(d_ranges), ranges_stride, int(margin), int(outside_cost), int(through_cost), _ptr(out),
+                                       _stream()), "slam2d_score_rays")
+        return out
+
+    @staticmethod
+    def rays_host(rows, cost_scale):
+        """Rows of ``score_rays`` as a dict of host arrays [N]: ``cost`` (uint64), ``score`` = -cost / cost_scale, ``beam_score``
+        (minus the field's sum over the inside beams, over cost_scale), ``inside``, ``in_range``, ``outside`` = in_range - inside,
+        ``through`` (beams that crossed a wall), ``checked`` (beams whose ray was asked for) and ``depth`` (samples beyond the
+        walls, summed over the through beams) (int)."""
+        r = _host(rows).reshape(-1, _lib.RAYS_STRIDE)
+        inside, in_range = r[:, 2].astype(np.int64), r[:, 3].astype(np.int64)
+        return dict(cost=r[:, 0].astype(np.uint64), score=-r[:, 0] / cost_scale, beam_score=-r[:, 1] / cost_scale, inside=inside,
+                    in_range=in_range, outside=in_range - inside, through=r[:, 4].astype(np.int64), checked=r[:, 5].astype(np.int64),
+                    depth=r[:, 6].astype(np.int64))
+
     def _scratch(self, attr, n, what):
         """The int64 scratch kept as ``self.<attr>``, at least ``n`` words of it: ``n`` is the answer of the ``*_work`` function
         ``what``, and below zero that function's error.  Kept while it is large enough, else allocated anew.  (No ``*_work``

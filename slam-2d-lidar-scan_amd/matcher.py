@@ -196,6 +196,30 @@ def clearance_table_of(max_dist, step):
     return (np.arange(n, dtype=np.uint32), 1.0), ("clearance", n)
 
 
+# ---- the rays of ScanMatcher.scoreRays ----
+def ray_margin(wall_thickness, step):
+    """The default ``margin`` of ``scoreRays`` in samples: ceil(wallThickness / step) + 1 -- the wall the map update itself paints
+    in front of an endpoint, plus one cell of discretisation.  A true pose's beams end inside it and are not THROUGH."""
+    return math.ceil(float(wall_thickness) / float(step)) + 1
+
+
+_same_frames = set()
+
+
+def same_frames(lv, lvd):
+    """``scoreRays`` without a likelihood reads the field of ``lv`` and the squared distances of ``lvd``, both just built about
+    one centre: their frames have to agree in xlo, ylo, fh, fw.  Checked on the first call of a pair of cached levels (one
+    small download); Slam2dError if they differ."""
+    if (id(lv), id(lvd)) in _same_frames:
+        return
+    a, b = lv.frames()[0], lvd.frames()[0]
+    differ = [k for k in ("xlo", "ylo", "fh", "fw") if a[k] != b[k]]
+    if differ:
+        raise _lib.Slam2dError(f"scoreRays: the field's frame and the distance image's differ in {differ}")
+    if lv in _level_cache.values() and lvd in _level_cache.values():              # (cached levels live as long as the process)
+        _same_frames.add((id(lv), id(lvd)))
+
+
 # ---- the lattice of ScanMatcher.searchPoses and the peaks of its image, on the host ----
 Peak = collections.namedtuple("Peak", "x y theta score cost")
 
@@ -517,6 +541,72 @@ class ScanMatcher:
             host, = self._download(eng, "scorePoses", rows)
             self.last_cover = dict(level=lv, window=(cx, cy, half))
             return eng.score_host(host)
+
+    def _distance_twin(self, level, half):
+        """The cached distance level that stands on the frames of the blurred covering level of ``half``: ``clearance``'s."""
+        return self._covering_level(level, half, True, lambda step: clearance_table_of(None, step))
+
+    def castScans(self, poses, level="fine", window=None, max_range=None):
+        """The scan the map expects at N free poses (include/slam2d.h, slam2d_cast_rays): per pose ``poses[n] = (x, y, theta)``
+        and beam, a geometric ray through the occupied cells of the covering field of ``scorePoses`` (the same frame planning:
+        the bounding box of the finite poses, or ``window``), sampled every field step up to ``max_range`` metres (default:
+        lidarMaxRange), in ONE launch.  Returns the [N, beams] host arrays of ``ParticleEngine.cast_host``: ``kind``
+        (``_lib.RAY_HIT``, ``RAY_LEFT`` the field, ``RAY_NONE`` within the range), ``k`` and ``range`` = k * step, ``inf``
+        without a wall.  Unlike ``OccupancyGrid.predictScan`` the ray runs at the field's resolution with the beam's own
+        heading, for any number of poses in one map.  ``self.last_cover`` keeps the distance level and its window."""
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        N = len(poses)
+        if N == 0:
+            raise ValueError("no poses")
+        max_range = float(self.og.lidarMaxRange if max_range is None else max_range)
+        if not (math.isfinite(max_range) and max_range >= 0):
+            raise ValueError(f"max_range wants a finite number >= 0, not {max_range!r}")
+        cx, cy, half = covering_window(poses, window)
+        lvd = self._distance_twin(level, half)
+        K = math.ceil(max_range / lvd.step)
+        if K >= _lib.RAY_MAX_K:
+            raise ValueError(f"max_range: {K} samples of {lvd.step:g} m (fewer than {_lib.RAY_MAX_K})")
+        with self._cover(lvd, cx, cy, dist2=True) as (eng, d2):
+            words = eng.cast_rays(lvd, 0, d2, eng.to_device(poses), 3, N, K)
+            host, = self._download(eng, "castScans", words.to(torch.int64))
+            self.last_cover = dict(level=lvd, window=(cx, cy, half))
+            return eng.cast_host(host.astype(np.uint32), lvd.step)
+
+    def scoreRays(self, poses, reading_or_ranges, level="fine", window=None, likelihood=None, margin=None, through_cost=None,
+                  outside_cost=None):
+        """``searchPoses``' cost of a scan at N free poses plus a charge for every beam that crosses a wall of the map on its
+        way (include/slam2d.h, slam2d_score_rays), in ONE launch: the endpoint cost cannot tell a pose from one on the wrong side
+        of a wall, this can.  ``poses``, ``reading_or_ranges``, ``level``, ``window`` and ``likelihood`` as in ``scorePoses``;
+        ``outside_cost`` as in ``searchPoses``.  A beam is THROUGH when its ray meets an occupied field cell more than ``margin``
+        samples (field steps) short of its measured range -- default ``ray_margin``: ceil(wallThickness / step) + 1, the wall
+        the map update itself paints in front of an endpoint plus one cell of discretisation -- and pays ``through_cost``
+        (default: ``outside_cost`` -- what a beam that leaves the map pays).  With ``likelihood`` one distance build gives the
+        field and the squared distances the rays skip by; without, the blurred covering level gives the field and
+        ``clearance``'s cached distance level of the same window the distances.  Returns the [N] host arrays of
+        ``ParticleEngine.rays_host``: ``cost``, ``score``, ``beam_score``, ``inside``, ``in_range``, ``outside``, ``through``,
+        ``checked``, ``depth``.  ``self.last_cover`` keeps the field's level, its window, ``margin`` and the two costs."""
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+        N, B = len(poses), self.og.numSamplesPerRev
+        if N == 0:
+            raise ValueError("no poses")
+        rng = ranges_of(reading_or_ranges, B, N)
+        cx, cy, half = covering_window(poses, window)
+        lv = self.covering_level(level, half, likelihood=likelihood)
+        margin = ray_margin(self.og.wallThickness, lv.step) if margin is None else int(margin)
+        if margin < 0:
+            raise ValueError(f"margin wants a count of samples >= 0, not {margin}")
+        lvd = lv if likelihood is not None else self._distance_twin(level, half)
+        with self._cover(lvd, cx, cy, dist2=True) as (eng, d2), _Exclusive(*(() if lvd is lv else (lv,))):
+            if lvd is not lv:
+                self.build_cover(eng, lv, cx, cy)
+                same_frames(lv, lvd)
+            outside_cost = self.outside_cost_of(lv) if outside_cost is None else int(outside_cost)
+            through_cost = outside_cost if through_cost is None else int(through_cost)
+            rows = eng.score_rays(lv, 0, d2, eng.to_device(poses), 3, N, eng.to_device(rng), 0 if rng.ndim == 1 else B, margin,
+                                  outside_cost, through_cost)
+            host, = self._download(eng, "scoreRays", rows)
+            self.last_cover = dict(level=lv, window=(cx, cy, half), margin=margin, outside_cost=outside_cost, through_cost=through_cost)
+            return eng.rays_host(host, lv.cost_scale)
 
     def searchPoses(self, reading_or_ranges, window, step=None, headings=120, level="fine", top=5, separation=None, outside_cost=None,
                     likelihood=None):
