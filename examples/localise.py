@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Monte-Carlo localisation in a finished map with Localiser: follow the robot scan by scan, the hypotheses never leaving the device.
 
-    python examples/localise.py [--scans 40] [--particles 4096] [--temperature 64] [--level fine] [--adaptive] [--likelihood [SIGMA]] [--track] [--merge K]
+    python examples/localise.py [--scans 40] [--particles 4096] [--temperature 64] [--level fine] [--adaptive] [--likelihood [SIGMA]] [--rays [STRIDE]] [--track] [--merge K]
 
 Maps a seeded walk through a synthetic world at its true poses (map_from_poses), then forgets the poses: the first scan is
 searched for in the whole window (ScanMatcher.searchPoses), the particle set is seeded around the search's peaks
@@ -18,6 +18,11 @@ from the pose bins it occupies: the count is printed per scan as it falls from t
 --likelihood weighs the poses against the likelihood field instead of the blurred one (slam2d_field_build_distance: a table of
 the exact distance from a beam's end to the nearest wall, SIGMA metres wide, default 0.2), in the search and in the filter: a
 hypothesis half a metre off then still pays less than one across the building.
+
+--rays runs the filter with the charge for beams that cross walls (Localiser(rays=dict(stride=STRIDE)), slam2d_mcl_step_rays;
+default stride 4: one beam in four is cast per scan, every beam once in four scans) and prints the through beams per live particle
+beside the table.  With --adaptive it follows the log with and without the charge and prints the scan at which each run's mean
+pose first comes within one cell of the pose the scan was taken at.
 
 --track follows the same log once more with a Tracker: ONE pose on the device, from the search's best peak, moved by the odometry
 increment and refined by a local search per scan (slam2d_refine_poses); its error is printed beside the filter's.
@@ -71,6 +76,8 @@ def main():
     ap.add_argument("--adaptive", action="store_true", help="start from a uniform set of --particles poses and let the count adapt")
     ap.add_argument("--likelihood", type=float, nargs="?", const=0.2, default=None, metavar="SIGMA",
                     help="weigh against the likelihood field of this sigma in metres (default 0.2) instead of the blurred field")
+    ap.add_argument("--rays", type=int, nargs="?", const=4, default=None, metavar="STRIDE",
+                    help="charge the hypotheses for beams that cross walls, one beam in STRIDE per scan (default 4)")
     ap.add_argument("--track", action="store_true", help="also follow the log with a Tracker -- one pose -- from the search's best peak")
     ap.add_argument("--merge", type=int, default=0, metavar="K",
                     help="also follow the log with the last K scans of every step merged into one point set (Localiser.run_points)")
@@ -79,6 +86,10 @@ def main():
         ap.error("--track starts from the search's best peak: not with --adaptive")
     if args.merge < 0:
         ap.error("--merge wants a number of scans, 1 or more")
+    if args.rays is not None and args.rays < 1:
+        ap.error("--rays wants a stride, 1 or more")
+    if args.rays is not None and args.merge:
+        ap.error("--merge follows the log with point sets, which take no rays: not with --rays")
     likelihood = None if args.likelihood is None else dict(sigma=args.likelihood)
     pkg = importlib.import_module("slam-2d-lidar-scan_amd")
     true, log, grid, window = synthetic(args.scans)
@@ -89,10 +100,10 @@ def main():
         for q in found["peaks"]:
             print(f"search peak ({q.x:7.2f}, {q.y:7.2f}, {q.theta:6.3f}) score {q.score:9.2f}")
 
-    def seeded():
+    def seeded(rays=None if args.rays is None else dict(stride=args.rays)):
         """A filter of seed 1 on the window, lost (--adaptive) or around the search's peaks: the same set every time."""
         loc = pkg.Localiser(sm, window, particles=args.particles, level=args.level, sigma=(0.03, 0.03, 0.02), temperature=args.temperature, seed=1,
-                            adaptive={} if args.adaptive else None, likelihood=likelihood)
+                            adaptive={} if args.adaptive else None, likelihood=likelihood, rays=rays)
         if args.adaptive:
             loc.seed_uniform()
         else:
@@ -106,12 +117,22 @@ def main():
             print(f"true ({r['x']:7.2f}, {r['y']:7.2f}, {r['theta']:6.3f})  mean ({x:7.2f}, {y:7.2f}, {th:6.3f})  off by "
                   f"{math.hypot(x - r['x'], y - r['y']):.3f} m, {abs(dth):.3f} rad  {rep['distinct']:5d} distinct ancestors of "
                   f"{rep.get('n_out', args.particles)}, {rep['positive']:5d} weights above zero"
-                  + (f"  count {rep['n_in']:7d} -> {rep['n_out']:7d} ({rep['bins']} bins)" if args.adaptive else ""))
+                  + (f"  count {rep['n_in']:7d} -> {rep['n_out']:7d} ({rep['bins']} bins)" if args.adaptive else "")
+                  + (f"  through {rep['through'] / rep.get('n_in', args.particles):6.2f} per particle" if "through" in rep else ""))
         print(f"{len(log)} {what}, {args.particles} particles: {1e3 * dt / len(log):.3f} ms per step, upload and the one download included")
+
+    def converged(reports):
+        """The first scan whose mean pose lies within one cell of the pose it was taken at; None: never."""
+        near = [i for i, (r, rep) in enumerate(zip(true, reports)) if math.hypot(rep["mean_pose"][0] - r["x"], rep["mean_pose"][1] - r["y"])
+                <= grid["unitGridSize"]]
+        return near[0] if near else None
 
     t0 = time.perf_counter()
     reports = seeded().run(log)
     table(reports, time.perf_counter() - t0, "scans")
+    if args.rays is not None and args.adaptive:
+        print(f"within one cell of the true pose from scan: {converged(reports)} with the charge (stride {args.rays}), "
+              f"{converged(seeded(rays=None).run(log))} without")
     if args.merge:
         # the same log as points: per step the last K scans joined through the odometry, in the frame of the last one
         points = importlib.import_module("slam-2d-lidar-scan_amd.points")

@@ -821,6 +821,61 @@ int slam2d_mcl_step_adaptive(const Slam2dLidar* lidar, const Slam2dLevel* level,
                              const Slam2dMclBins* bins, const uint32_t* d_ntab, int32_t ntab_n,
                              int32_t* d_ancestor, uint64_t* d_work, uint64_t* d_report, void* stream);
 
+/* slam2d_mcl_step and slam2d_mcl_step_adaptive with slam2d_score_rays' charge per beam that crosses a wall inside the WEIGH step, on
+ * a stride of the beams: a cloud on the wrong side of a wall pays for the beams it sends through it and loses the resampling,
+ * where the endpoint model lets it live for as many scans as the endpoints alone need (added symbols: no struct and no existing
+ * signature changed, the ABI number stays).  PRECONDITION: those of slam2d_mcl_step and of slam2d_score_rays -- d_dist2 is the image
+ * slam2d_field_build_distance wrote for slot p_field with lut_n >= 2, on the frame the slot's field was built on.  The same members
+ * of `level` and `lidar` are read.  Integer operations and ONE rounded IEEE operation at a time: the same inputs give the same bits
+ * on every call.
+ * slam2d_mcl_step_rays: steps a (NOISE), b (MOVE), d (RESAMPLE) and e (REPORT) are slam2d_mcl_step's as written there, and
+ *   c. WEIGH.  sum_b, INSIDE and IN RANGE of the moved pose exactly as in slam2d_mcl_step.  Beam b is CAST iff
+ *      b % ray_stride == ray_phase.  A CAST beam in range is CHECKED iff its quotient r_b / step (one true division) lies in
+ *      [0, 1e9); then kend = (int64)(r_b / step) - margin, and the beam is THROUGH iff kend >= 0 and THE RAY (above
+ *      slam2d_cast_rays: the same sample formula, the `0 <=` guard, d_dist2) of the moved pose along the beam's own a_b is HIT at
+ *      some k <= kend.  through_n = the number of THROUGH beams of particle n;
+ *        cost_n = sum_b + (uint64)(in_range - inside) * outside_cost + (uint64)through_n * through_cost
+ *      -- below 2^44: sum_b and the outside term together are at most 2048 * 2^32 = 2^43 and so is the through term, so
+ *      cost << 20 | n still fits 64 bits.  cmin, best and w_n as in slam2d_mcl_step, on this cost.
+ *   REPORT.  Words 0-14 as in slam2d_mcl_step, on this cost; word 15 = the sum of through_n over the N particles, an integer atomic
+ *      add, reset with the other joined words by the first launch.
+ *   d_through: NULL, or [N]: d_through[n] = through_n of the MOVED particle n, before the resampling.
+ * slam2d_mcl_step_adaptive_rays: slam2d_mcl_step_adaptive with that WEIGH step over n < N; its steps d-h are as written there,
+ * word 15 is the sum over n < N, d_through is NULL or [n_cap] and its rows n >= N are untouched.
+ * EQUIVALENCES.  (i) With through_cost == 0, or no CAST beam (ray_phase >= beams), the output poses, d_ancestor and report words
+ * 0-14 are slam2d_mcl_step's (slam2d_mcl_step_adaptive's) bit for bit.  (ii) With ray_stride == 1 and motion = amp = 0, word 0 is
+ * the minimum of slam2d_score_rays' cost (same margin and costs, the one scan) over the input poses, word 1 the lowest index that
+ * attains it, and d_through equals its slot 4.  (iii) The EQUIVALENCE clause of slam2d_mcl_step_adaptive holds against
+ * slam2d_mcl_step_rays, word 15 and d_through included.
+ * d_work: slam2d_mcl_rays_work(N) == slam2d_mcl_work(N) words, slam2d_mcl_adapt_rays_work(n_cap, bins) ==
+ * slam2d_mcl_adapt_work(n_cap, bins); the caller need not initialise d_work, d_report, d_pose_out, d_ancestor or d_through.  Both
+ * calls allocate nothing, raise no fault bit and do not synchronise.  Five launches (adaptive: seven) on `stream`, as in the plain
+ * steps: the move launch also resets word 15; the score launch is a wave per particle -- slam2d_mcl_step's endpoint trips, then the
+ * CAST beams packed over the wave's lanes, 64 rays per trip (180 beams at stride 4: 45 rays in one trip), through_n joined by
+ * ballots, the sixteen particles of a block joined in LDS in front of the block's one integer atomic --; the sums launch leaves word 15 alone; the weigh, reference, count
+ * and resample launches are the plain steps' own kernels.  Every ray ends: its sample index strictly increases below kend + 1 < 2^30.
+ * SLAM2D_E_BADARG, before any HIP call: every case of slam2d_mcl_step (slam2d_mcl_step_adaptive), a NULL d_dist2, ray_stride < 1
+ * or > SLAM2D_MAX_BEAMS, ray_phase < 0 or >= ray_stride, margin < 0; SLAM2D_E_TOOLARGE: as there.  The two *_work functions make no
+ * HIP call and answer what slam2d_mcl_work and slam2d_mcl_adapt_work answer, error codes included. */
+int64_t slam2d_mcl_rays_work(int32_t N);                        /* slam2d_mcl_work(N) */
+int slam2d_mcl_step_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t N,
+                         const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                         const double motion[3], const double amp[3], uint64_t seed, uint64_t scan,
+                         const double* d_ranges, uint32_t outside_cost,
+                         int32_t ray_stride, int32_t ray_phase, int32_t margin, uint32_t through_cost,
+                         const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
+                         int32_t* d_ancestor, uint32_t* d_through, uint64_t* d_work, uint64_t* d_report, void* stream);
+int64_t slam2d_mcl_adapt_rays_work(int32_t n_cap, const Slam2dMclBins* bins);   /* slam2d_mcl_adapt_work(n_cap, bins) */
+int slam2d_mcl_step_adaptive_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2,
+                                  int32_t n_cap, const uint32_t* d_n_in, uint32_t* d_n_out,
+                                  const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                                  const double motion[3], const double amp[3], uint64_t seed, uint64_t scan,
+                                  const double* d_ranges, uint32_t outside_cost,
+                                  int32_t ray_stride, int32_t ray_phase, int32_t margin, uint32_t through_cost,
+                                  const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift,
+                                  const Slam2dMclBins* bins, const uint32_t* d_ntab, int32_t ntab_n,
+                                  int32_t* d_ancestor, uint32_t* d_through, uint64_t* d_work, uint64_t* d_report, void* stream);
+
 /* The point forms of slam2d_score_poses, slam2d_mcl_step and slam2d_mcl_step_adaptive: the same calls for a SET OF POINTS in the
  * robot's frame (the comment above SLAM2D_MAX_POINTS: point k at d_points[k * point_stride + 0..1], steps 1-4 of its cost) instead
  * of one scan of one sensor, so that a caller who found a place with slam2d_search_points can grade pose sets and follow the robot

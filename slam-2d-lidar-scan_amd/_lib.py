@@ -220,6 +220,15 @@ SIGNATURES = {
     "slam2d_mcl_step_adaptive": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                            _vp, C.c_int32, C.c_int32, C.POINTER(Slam2dMclBins), _vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "slam2d_mcl_rays_work": (C.c_int64, [C.c_int32]),
+    "slam2d_mcl_step_rays": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_uint64, _vp, C.c_uint32,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "slam2d_mcl_adapt_rays_work": (C.c_int64, [C.c_int32, C.POINTER(Slam2dMclBins)]),
+    "slam2d_mcl_step_adaptive_rays": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp,
+                                                C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_uint64, _vp, C.c_uint32,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _vp, C.c_int32, C.c_int32,
+                                                C.POINTER(Slam2dMclBins), _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "slam2d_score_points": (C.c_int, [C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "slam2d_mcl_points_work": (C.c_int64, [C.c_int32]),
     "slam2d_mcl_step_points": (C.c_int, [C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32,

@@ -5253,8 +5253,9 @@ __global__ __launch_bounds__(MCL_SCAN_BLOCK / 4) void k_mcl_weigh(int N, const u
 
 // One block of MCL_SCAN_BLOCK threads: the scan blocks' sums become their exclusive prefix sums; W, the resampler's word and u0,
 // and the report's words 0-15 that need no particle loop.  counted(t): thread t's share of word 5 -- the beams in range
-// (mcl_beams_in_range) or the valid points (mclp_points_valid) among items t, t + MCL_SCAN_BLOCK, ...
-template <class Counted>
+// (mcl_beams_in_range) or the valid points (mclp_points_valid) among items t, t + MCL_SCAN_BLOCK, ...  KEEP15: word 15 is a sum the
+// scoring launch has joined (the ray forms' through beams) and is left alone; every other form's word 15 is 0.
+template <bool KEEP15 = false, class Counted>
 __device__ __forceinline__ void mcl_sums_block(const int N, const uint64_t seed, const uint64_t scan, const Counted counted, const MclWork& wk,
                                                unsigned long long* __restrict__ report) {
     __shared__ unsigned long long lds[16];
@@ -5277,7 +5278,7 @@ __device__ __forceinline__ void mcl_sums_block(const int N, const uint64_t seed,
         report[4] = (W >> 32) * r + (((W & 0xffffffffull) * r) >> 32);          // floor(r * W / 2^32), W < 2^44
         report[5] = n_rng;
         for (int i = 0; i < 3; ++i) report[7 + i] = (unsigned long long)__double_as_longlong(wk.moved[best * 3 + i]);
-        report[15] = 0ull;
+        if (!KEEP15) report[15] = 0ull;
     }
 }
 
@@ -5543,6 +5544,149 @@ __global__ __launch_bounds__(256) void k_mcla_resample(int n_cap, const uint32_t
         mcl_emit_offspring(j, a, first, wk, out, pstride, ancestor, part);
     }
     mcl_join_sums(part, acc, report);
+}
+
+// ---- the two steps with a charge per beam that crosses a wall (slam2d_mcl_step_rays, slam2d_mcl_step_adaptive_rays) ----
+// WEIGH with slam2d_score_rays' THROUGH beams on a stride of the scan: the endpoint trips are mcl_beams, the ray pass behind them
+// is ray_walk.  Only the move launch (it also resets word 15, which the scoring waves join), the score launch and the sums launch
+// (it must not clear that word) differ from slam2d_mcl_step's: the weigh, reference, count and resample launches are its own.
+
+// k_mcl_move, and word 15 = 0
+__global__ __launch_bounds__(256) void k_mcl_move_rays(int N, const double* __restrict__ pose, int pstride, double dfwd, double dside, double dturn,
+                                                       double amp0, double amp1, double amp2, uint64_t seed, uint64_t scan, MclWork wk,
+                                                       unsigned long long* __restrict__ report) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0) {
+        mcl_reset_joined(wk, report);
+        report[15] = 0ull;
+    }
+    if (n >= N) return;
+    mcl_move_particle(n, pose, pstride, dfwd, dside, dturn, amp0, amp1, amp2, seed, scan, wk);
+}
+
+// k_mcla_move, and word 15 = 0
+__global__ __launch_bounds__(256) void k_mcla_move_rays(const uint32_t* __restrict__ n_in, int n_cap, const double* __restrict__ pose, int pstride,
+                                                        double dfwd, double dside, double dturn, double amp0, double amp1, double amp2,
+                                                        uint64_t seed, uint64_t scan, MclWork wk, unsigned long long* __restrict__ bitmap, int words,
+                                                        unsigned long long* __restrict__ tail, unsigned long long* __restrict__ report) {
+    const int N = mcla_live(n_in, n_cap), t0 = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    if (t0 == 0) {
+        mcl_reset_joined(wk, report);
+        report[15] = 0ull;
+        tail[0] = 0ull; tail[1] = 0ull;
+    }
+    for (int i = t0; i < words; i += stride) bitmap[i] = 0ull;
+    for (int n = t0; n < N; n += stride) mcl_move_particle(n, pose, pstride, dfwd, dside, dturn, amp0, amp1, amp2, seed, scan, wk);
+}
+
+#define MCLR_WAVES 16                // particles (waves) per block of the ray forms' scoring launches: one join of word 15 per block
+
+// What the ray pass of a step takes beside the endpoint pass's arguments: the CAST beams (b % stride == phase), the margin and
+// the charge, and where through_n goes (NULL: nowhere)
+struct MclRays { int stride, phase, margin; unsigned through_cost; uint32_t* __restrict__ through; };
+
+// Particle n on this wave: mcl_score_particle's endpoint trips -- mcl_beams, unchanged --, then the ray pass.  ray_walk is a
+// wave-uniform loop that lasts as long as its longest ray, so a stride applied inside the endpoint trips would leave most lanes
+// idle and still pay every trip; the CAST beams are packed over the lanes instead.  J = the number of cast beams; lane l of ray
+// trip t takes cast beam j = 64 t + l, beam b = phase + j * stride (below B): 180 beams at stride 4 are 45 rays in ONE ray_walk.
+// The lane evaluates its beam's a_b, cos and sin with the expression of the endpoint pass (fan.angle, cos, sin), so their bits are
+// the endpoint's; CHECKED, kend and THROUGH are k_score_rays' lines.  Every ray ends: ray_walk's k strictly increases below
+// k_exit <= kend + 1 < 2^30 (the quotient is below 1e9, margin >= 0), and a lane without a cast beam or with kend < 0 walks
+// nothing.  through_n is joined by ballots; lane 0 writes the cost and d_through[n] and joins cost << 20 | n as mcl_score_particle
+// does.  Returns through_n (the same on every lane) for mclr_join_block.
+__device__ __forceinline__ int mcl_score_rays_particle(const int n, const int lane, const Slam2dLidar& lid, const Slam2dLevel& lv, const SlotField& sf,
+                                                        const RayField& f, const double* __restrict__ ranges, const unsigned outside_cost,
+                                                        const MclRays& ry, const MclWork& wk) {
+    const double x = wk.moved[(size_t)n * 3], y = wk.moved[(size_t)n * 3 + 1], th = wk.moved[(size_t)n * 3 + 2];
+    const int B = lid.beams, trips = (B + 63) >> 6;
+    const BeamFan fan = fan_of(lid, th);
+    unsigned long long sum_b = 0ull;                                             // (this lane's share)
+    int n_in = 0, n_rng = 0, n_thr = 0;                                          // (the wave's counts: ballots)
+    int t = 0;
+    for (; t + MCL_UNROLL <= trips; t += MCL_UNROLL)                             // (wave-uniform trip counts)
+        mcl_beams<MCL_UNROLL>(64 * t, lane, B, ranges, lid.max_range, fan, x, y, sf.fr, lv.step, sf.fs, lv.fpitch, sf.field, sum_b, n_in, n_rng);
+    for (; t < trips; ++t) mcl_beams<1>(64 * t, lane, B, ranges, lid.max_range, fan, x, y, sf.fr, lv.step, sf.fs, lv.fpitch, sf.field, sum_b, n_in, n_rng);
+    const int J = ry.phase < B ? (B - 1 - ry.phase) / ry.stride + 1 : 0;         // (phase + (J - 1) * stride <= B - 1)
+    for (int j0 = 0; j0 < J; j0 += 64) {                                         // (wave-uniform trip count)
+        const bool cast = j0 + lane < J;
+        const int b = cast ? ry.phase + (j0 + lane) * ry.stride : 0;
+        const double r = cast ? ranges[b] : NAN;
+        const bool in_range = r < lid.max_range;                                 // (NaN and +inf are out, 0 and negatives in)
+        const double a = fan.angle(b);
+        const double q = r / f.step;
+        const bool checked = in_range && q >= 0.0 && q < 1e9;
+        const long long kend = checked ? (long long)q - ry.margin : -1ll;
+        const uint32_t word = ray_walk(f, x, y, cos(a), sin(a), kend >= 0 ? (int)kend : 0, kend >= 0);
+        const bool through = kend >= 0 && (word >> 30) == SLAM2D_RAY_HIT;           // (a HIT lies at k <= the limit, kend)
+        n_thr += __popcll(__ballot(through));
+    }
+    sum_b = wave64_sum_u64(sum_b);
+    if (lane == 0) {
+        const unsigned long long cost = sum_b + (unsigned long long)(n_rng - n_in) * outside_cost
+                                        + (unsigned long long)n_thr * ry.through_cost;                  // (below 2^44: two terms of at most 2^43)
+        wk.cost[n] = cost;
+        if (ry.through) ry.through[n] = (uint32_t)n_thr;
+        const unsigned long long v = (cost << 20) | (unsigned long long)n;
+        if (v < __hip_atomic_load(wk.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(wk.key, v);
+    }
+    return n_thr;
+}
+
+// The waves' through beams joined per block in LDS, then ONE integer atomic add on word 15, and none where the block has no
+// through beam.  With an atomic per particle the waves of a large set send tens of thousands of them to the one address, and
+// the launch waits for them, not for the rays: 0.52 ms of the 0.63 ms of a step of 65 536 particles at stride 4
+// (profiles/r26_mcl_rays.md) -- what mclp_join_block met for the packed minimum.  Every thread of the block calls it.
+__device__ __forceinline__ void mclr_join_block(const int thr, const int wv, const int lane, unsigned long long* __restrict__ report) {
+    __shared__ int wthr[MCLR_WAVES];
+    if (lane == 0) wthr[wv] = thr;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sum = 0ull;
+        for (int i = 0; i < MCLR_WAVES; ++i) sum += (unsigned long long)wthr[i];
+        if (sum) atomicAdd(&report[15], sum);
+    }
+}
+
+// Score: one wave per particle (mcl_score_rays_particle), MCLR_WAVES of them per block (mclr_join_block).  Reads frames[p_field],
+// the slot's field and squared distances, the moved poses and the ranges; writes the costs and d_through; no fault bit.
+__global__ __launch_bounds__(64 * MCLR_WAVES) void k_mcl_score_rays(Slam2dLidar lid, Slam2dLevel lv, int p_field, const uint32_t* __restrict__ dist2, int N,
+                                                                   const double* __restrict__ ranges, unsigned outside_cost, MclRays ry, MclWork wk,
+                                                                   unsigned long long* __restrict__ report) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = blockIdx.x * MCLR_WAVES + wv;
+    const SlotField sf = slot_field(lv, p_field);
+    int thr = 0;
+    if (n < N) thr = mcl_score_rays_particle(n, lane, lid, lv, sf, ray_field(lv, p_field, dist2), ranges, outside_cost, ry, wk);    // (wave-uniform)
+    mclr_join_block(thr, wv, lane, report);
+}
+
+// mcl_score_rays_particle: a wave takes particles wave, wave + the grid's waves, ... below N and keeps their through beams for
+// mclr_join_block
+__global__ __launch_bounds__(64 * MCLR_WAVES) void k_mcla_score_rays(Slam2dLidar lid, Slam2dLevel lv, int p_field, const uint32_t* __restrict__ dist2,
+                                                                    const uint32_t* __restrict__ n_in, int n_cap, const double* __restrict__ ranges,
+                                                                    unsigned outside_cost, MclRays ry, MclWork wk,
+                                                                    unsigned long long* __restrict__ report) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int N = mcla_live(n_in, n_cap);
+    const SlotField sf = slot_field(lv, p_field);
+    const RayField f = ray_field(lv, p_field, dist2);
+    int thr = 0;                                                                 // (at most 2048 each of at most 2^20 particles: below 2^31)
+    for (int n = blockIdx.x * MCLR_WAVES + wv; n < N; n += gridDim.x * MCLR_WAVES)  // (wave-uniform)
+        thr += mcl_score_rays_particle(n, lane, lid, lv, sf, f, ranges, outside_cost, ry, wk);
+    mclr_join_block(thr, wv, lane, report);
+}
+
+// k_mcl_sums and k_mcla_sums with word 15 kept
+__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcl_sums_rays(Slam2dLidar lid, int N, uint64_t seed, uint64_t scan, const double* __restrict__ ranges,
+                                                                  MclWork wk, unsigned long long* __restrict__ report) {
+    mcl_sums_block<true>(N, seed, scan, mcl_beams_in_range(lid, ranges), wk, report);
+}
+__global__ __launch_bounds__(MCL_SCAN_BLOCK) void k_mcla_sums_rays(Slam2dLidar lid, const uint32_t* __restrict__ n_in, int n_cap, uint64_t seed,
+                                                                   uint64_t scan, const double* __restrict__ ranges, MclWork wk,
+                                                                   unsigned long long* __restrict__ report) {
+    const int N = mcla_live(n_in, n_cap);
+    mcl_sums_block<true>(N, seed, scan, mcl_beams_in_range(lid, ranges), wk, report);
+    mcla_report_live(N, report);
 }
 
 // ---- the two steps for a set of points in the robot's frame (slam2d_mcl_step_points, slam2d_mcl_step_adaptive_points) ----
@@ -6889,6 +7033,59 @@ int slam2d_mcl_step_adaptive(const Slam2dLidar* lidar, const Slam2dLevel* level,
     k_mcla_score<<<a.score_blocks, 64 * MCL_WAVES, 0, s>>>(*lidar, *level, p_field, d_n_in, n_cap, d_ranges, outside_cost, a.wk);
     k_mcla_weigh<<<cdiv(n_cap, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(d_n_in, n_cap, d_lut, lut_n, lut_shift, a.wk, report);
     k_mcla_sums<<<1, MCL_SCAN_BLOCK, 0, s>>>(*lidar, d_n_in, n_cap, seed, scan, d_ranges, a.wk, report);
+    return launch_mcla_resampling(a, n_cap, d_n_in, d_n_out, *bins, d_ntab, ntab_n, d_pose_out, pose_stride, d_ancestor, report, s);
+}
+
+int64_t slam2d_mcl_rays_work(int32_t N) { return slam2d_mcl_work(N); }
+int64_t slam2d_mcl_adapt_rays_work(int32_t n_cap, const Slam2dMclBins* bins) { return slam2d_mcl_adapt_work(n_cap, bins); }
+
+// What the two ray steps check behind their plain step's answer rc: SLAM2D_E_BADARG in front of its SLAM2D_E_TOOLARGE
+static int check_mcl_rays(int rc, const uint32_t* d_dist2, int ray_stride, int ray_phase, int margin) {
+    if (rc == SLAM2D_E_BADARG) return rc;
+    if (!d_dist2 || ray_stride < 1 || ray_stride > SLAM2D_MAX_BEAMS || ray_phase < 0 || ray_phase >= ray_stride || margin < 0) return SLAM2D_E_BADARG;
+    return rc;
+}
+
+int slam2d_mcl_step_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t N,
+                         const double* d_pose_in, double* d_pose_out, int32_t pose_stride, const double motion[3], const double amp[3],
+                         uint64_t seed, uint64_t scan, const double* d_ranges, uint32_t outside_cost, int32_t ray_stride, int32_t ray_phase,
+                         int32_t margin, uint32_t through_cost, const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift, int32_t* d_ancestor,
+                         uint32_t* d_through, uint64_t* d_work, uint64_t* d_report, void* stream) {
+    const int rc = check_mcl_rays(check_mcl_step(lidar, level, p_field, N, d_pose_in, d_pose_out, pose_stride, motion, amp, d_ranges, d_lut, lut_n,
+                                                 lut_shift, d_work, d_report), d_dist2, ray_stride, ray_phase, margin);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const MclWork wk = mcl_work_of(d_work, N);
+    const MclRays ry{ray_stride, ray_phase, margin, through_cost, d_through};
+    unsigned long long* report = (unsigned long long*)d_report;
+    k_mcl_move_rays<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion[0], motion[1], motion[2], amp[0], amp[1], amp[2], seed, scan, wk, report);
+    k_mcl_score_rays<<<cdiv(N, MCLR_WAVES), 64 * MCLR_WAVES, 0, s>>>(*lidar, *level, p_field, d_dist2, N, d_ranges, outside_cost, ry, wk, report);
+    k_mcl_weigh<<<cdiv(N, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(N, d_lut, lut_n, lut_shift, wk, report);
+    k_mcl_sums_rays<<<1, MCL_SCAN_BLOCK, 0, s>>>(*lidar, N, seed, scan, d_ranges, wk, report);
+    k_mcl_resample<<<cdiv(N, 256), 256, 0, s>>>(N, wk, d_pose_out, pose_stride, d_ancestor, report);
+    return launch_status();
+}
+
+int slam2d_mcl_step_adaptive_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t n_cap,
+                                  const uint32_t* d_n_in, uint32_t* d_n_out, const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                                  const double motion[3], const double amp[3], uint64_t seed, uint64_t scan, const double* d_ranges,
+                                  uint32_t outside_cost, int32_t ray_stride, int32_t ray_phase, int32_t margin, uint32_t through_cost,
+                                  const uint32_t* d_lut, int32_t lut_n, int32_t lut_shift, const Slam2dMclBins* bins, const uint32_t* d_ntab,
+                                  int32_t ntab_n, int32_t* d_ancestor, uint32_t* d_through, uint64_t* d_work, uint64_t* d_report, void* stream) {
+    long long n_bins = 0;
+    const int rc = check_mcl_adaptive(check_mcl_rays(check_mcl_step(lidar, level, p_field, n_cap, d_pose_in, d_pose_out, pose_stride, motion, amp,
+                                                                    d_ranges, d_lut, lut_n, lut_shift, d_work, d_report),
+                                                     d_dist2, ray_stride, ray_phase, margin), d_n_in, d_n_out, d_ntab, ntab_n, bins, &n_bins);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const MclaWork a = mcla_work_of(d_work, n_cap, n_bins);
+    const MclRays ry{ray_stride, ray_phase, margin, through_cost, d_through};
+    unsigned long long* report = (unsigned long long*)d_report;
+    k_mcla_move_rays<<<a.move_blocks, 256, 0, s>>>(d_n_in, n_cap, d_pose_in, pose_stride, motion[0], motion[1], motion[2], amp[0], amp[1], amp[2], seed,
+                                                   scan, a.wk, a.bitmap, a.words, a.tail, report);
+    k_mcla_score_rays<<<cdiv(a.score_blocks * MCL_WAVES, MCLR_WAVES), 64 * MCLR_WAVES, 0, s>>>(*lidar, *level, p_field, d_dist2, d_n_in, n_cap, d_ranges, outside_cost, ry, a.wk, report);
+    k_mcla_weigh<<<cdiv(n_cap, MCL_SCAN_BLOCK), MCL_SCAN_BLOCK / 4, 0, s>>>(d_n_in, n_cap, d_lut, lut_n, lut_shift, a.wk, report);
+    k_mcla_sums_rays<<<1, MCL_SCAN_BLOCK, 0, s>>>(*lidar, d_n_in, n_cap, seed, scan, d_ranges, a.wk, report);
     return launch_mcla_resampling(a, n_cap, d_n_in, d_n_out, *bins, d_ntab, ntab_n, d_pose_out, pose_stride, d_ancestor, report, s);
 }
 

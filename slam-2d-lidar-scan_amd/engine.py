@@ -371,6 +371,17 @@ def mcl_adapt_report_host(words):
     return out
 
 
+def mcl_rays_report_host(words):
+    """The report of slam2d_mcl_step_rays (16 words: ``mcl_report_host``'s dict) or slam2d_mcl_step_adaptive_rays (24:
+    ``mcl_adapt_report_host``'s) with ``through``, word 15: the through beams summed over the particles the step weighed."""
+    w = np.ascontiguousarray(_host(words)).reshape(-1).view(np.uint64)
+    if w.size not in (_lib.MCL_REPORT, _lib.MCL_ADAPT_REPORT):
+        raise ValueError(f"{w.size} words: want {_lib.MCL_REPORT} or {_lib.MCL_ADAPT_REPORT}")
+    out = mcl_report_host(w) if w.size == _lib.MCL_REPORT else mcl_adapt_report_host(w)
+    out.update(through=int(w[15]))
+    return out
+
+
 # ----------------------------------------------------------------------------
 # Lidar model + polar spoke LUT (Utils/OccupancyGrid.py:22-57)
 # ----------------------------------------------------------------------------
@@ -1477,23 +1488,43 @@ class ParticleEngine:
                   _lib.MCL_REPORT, (), d_in, d_out, motion, amp, seed, scan, (_ptr(d_ranges),), outside_cost, d_lut, shift, (), d_report, d_ancestor)
 
     def _mcl(self, name, head, scratch, words, what, level, p_field, n, n_name, report_words, counts, d_in, d_out, motion, amp, seed, scan, source,
-             outside_cost, d_lut, shift, sizing, d_report, d_ancestor):
+             outside_cost, d_lut, shift, sizing, d_report, d_ancestor, rays=None):
         """The body of the four MCL steps, the library's ``name``, over ``n`` poses (``n_name`` in the messages) and a report of
         ``report_words``: the two pose buffers, the report and the ancestors, the step's own scratch (``scratch``, ``words``,
         ``what``: ``_scratch``'s arguments) and the packing of motion, amplitudes, seed and scan.  ``head``: the call's arguments
         before the level; ``source``: the scan's or the point set's; ``counts``: an adaptive step's count words, after ``n``;
-        ``sizing``: its bins and table, after the weights'."""
+        ``sizing``: its bins and table, after the weights'; ``rays``: a ray step's ``_ray_charge``."""
         _check_slot(level, p_field)
+        dist2, charge, through = ((), (), ()) if rays is None else rays
         stride = d_in.shape[-1] if d_in.dim() > 1 else 3
         if (d_out.shape[-1] if d_out.dim() > 1 else 3) != stride or d_in.numel() < n * stride or d_out.numel() < n * stride:
             raise ValueError(f"d_in {tuple(d_in.shape)} and d_out {tuple(d_out.shape)}: want two buffers of {n} poses of one row length")
         if d_report.numel() < report_words or (d_ancestor is not None and d_ancestor.numel() < n):
             raise ValueError(f"d_report wants {report_words} words, d_ancestor {n_name}")
         work = self._scratch(scratch, words, what)
-        check(getattr(self.L, name)(*head, C.byref(level.c), p_field, n, *counts, _ptr(d_in), _ptr(d_out), stride,
+        check(getattr(self.L, name)(*head, C.byref(level.c), p_field, *dist2, n, *counts, _ptr(d_in), _ptr(d_out), stride,
                                     _triple(motion), _triple(amp), int(seed) & 0xffffffffffffffff, int(scan) & 0xffffffffffffffff,
-                                    *source, int(outside_cost), _ptr(d_lut), d_lut.numel(), int(shift), *sizing,
-                                    _ptr(d_ancestor), _ptr(work), _ptr(d_report), _stream()), name)
+                                    *source, int(outside_cost), *charge, _ptr(d_lut), d_lut.numel(), int(shift), *sizing,
+                                    _ptr(d_ancestor), *through, _ptr(work), _ptr(d_report), _stream()), name)
+
+    @staticmethod
+    def _ray_charge(n, d_dist2, ray_stride, ray_phase, margin, through_cost, d_through):
+        """What a ray step adds to ``_mcl``'s call, as its ``rays``: the squared distances behind the slot, the four ray
+        arguments behind ``outside_cost`` and ``d_through`` (None, or ``n`` 32-bit words) behind the ancestors."""
+        if d_through is not None and (d_through.numel() < n or d_through.element_size() != 4):
+            raise ValueError(f"d_through wants {n} 32-bit words")
+        return (_ptr(d_dist2),), (int(ray_stride), int(ray_phase), int(margin), int(through_cost)), (_ptr(d_through),)
+
+    def mcl_step_rays(self, level, p_field, d_dist2, d_in, d_out, N, motion, amp, seed, scan, d_ranges, outside_cost, ray_stride, ray_phase, margin,
+                      through_cost, d_lut, shift, d_report, d_ancestor=None, d_through=None):
+        """``mcl_step`` with ``score_rays``' charge inside the weighing (include/slam2d.h, slam2d_mcl_step_rays): every beam b with
+        ``b % ray_stride == ray_phase`` whose measured range lies more than ``margin`` samples beyond a wall of the field costs
+        the moved particle ``through_cost``.  ``d_dist2`` as in ``cast_rays``, of the frame the slot's field stands on;
+        ``d_through``: None or [N] int32, the particles' through beams before the resampling; word 15 of ``d_report`` is their sum
+        (``mcl_rays_report_host`` decodes).  Five launches on the current stream, no synchronisation; ``mcl_step``'s scratch."""
+        self._mcl("slam2d_mcl_step_rays", (C.byref(self.lidar_c),), "_mcl_work", self.L.slam2d_mcl_rays_work(N), "slam2d_mcl_rays_work", level,
+                  p_field, N, "N", _lib.MCL_REPORT, (), d_in, d_out, motion, amp, seed, scan, (_ptr(d_ranges),), outside_cost, d_lut, shift, (),
+                  d_report, d_ancestor, rays=self._ray_charge(N, d_dist2, ray_stride, ray_phase, margin, through_cost, d_through))
 
     def mcl_step_adaptive(self, level, p_field, d_in, d_out, n_cap, d_count, motion, amp, seed, scan, d_ranges, outside_cost, d_lut, shift,
                           bins, d_ntab, d_report, d_ancestor=None, d_count_out=None):
@@ -1506,15 +1537,25 @@ class ParticleEngine:
         self._mcl_adaptive("slam2d_mcl_step_adaptive", (C.byref(self.lidar_c),), "slam2d_mcl_adapt_work", level, p_field, d_in, d_out, n_cap, d_count,
                            motion, amp, seed, scan, (_ptr(d_ranges),), outside_cost, d_lut, shift, bins, d_ntab, d_report, d_ancestor, d_count_out)
 
+    def mcl_step_adaptive_rays(self, level, p_field, d_dist2, d_in, d_out, n_cap, d_count, motion, amp, seed, scan, d_ranges, outside_cost,
+                               ray_stride, ray_phase, margin, through_cost, d_lut, shift, bins, d_ntab, d_report, d_ancestor=None,
+                               d_through=None, d_count_out=None):
+        """``mcl_step_adaptive`` with the charge of ``mcl_step_rays`` (include/slam2d.h, slam2d_mcl_step_adaptive_rays);
+        ``d_through``: None or [n_cap] int32, rows at and beyond the live count untouched.  Seven launches on the current stream,
+        no synchronisation."""
+        self._mcl_adaptive("slam2d_mcl_step_adaptive_rays", (C.byref(self.lidar_c),), "slam2d_mcl_adapt_rays_work", level, p_field, d_in, d_out, n_cap,
+                           d_count, motion, amp, seed, scan, (_ptr(d_ranges),), outside_cost, d_lut, shift, bins, d_ntab, d_report, d_ancestor,
+                           d_count_out, rays=self._ray_charge(n_cap, d_dist2, ray_stride, ray_phase, margin, through_cost, d_through))
+
     def _mcl_adaptive(self, name, head, what, level, p_field, d_in, d_out, n_cap, d_count, motion, amp, seed, scan, source, outside_cost, d_lut,
-                      shift, bins, d_ntab, d_report, d_ancestor, d_count_out):
+                      shift, bins, d_ntab, d_report, d_ancestor, d_count_out, rays=None):
         """``_mcl`` for the two adaptive steps: the count words, the work size ``what`` of the capacity and the bins, the table."""
         d_count_out = d_count if d_count_out is None else d_count_out
         if any(t.numel() < 1 or t.element_size() != 4 for t in (d_count, d_count_out)):
             raise ValueError("d_count wants one 32-bit word")
         self._mcl(name, head, "_mcl_adapt_work", getattr(self.L, what)(n_cap, C.byref(bins)), what, level, p_field, n_cap, "n_cap",
                   _lib.MCL_ADAPT_REPORT, (_ptr(d_count), _ptr(d_count_out)), d_in, d_out, motion, amp, seed, scan, source, outside_cost, d_lut, shift,
-                  (C.byref(bins), _ptr(d_ntab), d_ntab.numel()), d_report, d_ancestor)
+                  (C.byref(bins), _ptr(d_ntab), d_ntab.numel()), d_report, d_ancestor, rays=rays)
 
     @staticmethod
     def _point_source(d_points, M, point_stride):

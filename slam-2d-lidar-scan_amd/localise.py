@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import kld_table, mcl_adapt_report_host, mcl_report_host, pinned_stream, refine_host, weight_table
-from .matcher import check_stages, covering_window, points_of, ranges_of
+from .engine import kld_table, mcl_adapt_report_host, mcl_rays_report_host, mcl_report_host, pinned_stream, refine_host, weight_table
+from .matcher import check_stages, covering_window, points_of, ranges_of, ray_margin, same_frames
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 _MASK = np.uint64(0xffffffff)
@@ -57,6 +57,27 @@ def odometry_motion(prev, cur):
     return c * dx + s * dy, c * dy - s * dx, float(t1) - float(t0)
 
 
+def ray_options(rays, beams, step, wall_thickness, outside_cost):
+    """``Localiser``'s ``rays`` with its defaults filled in: ``stride`` (4: one beam in four is cast), ``margin``
+    (``matcher.ray_margin`` of the wall thickness and the field's step), ``through_cost`` (min(stride * outside_cost, 2^32 - 1): a
+    cast beam stands for ``stride`` beams) and ``rotate`` (True: the phase is the scan number mod stride).  ValueError for an
+    unknown key, a stride outside 1 .. beams, a margin below 0 or a through_cost outside 32 bits."""
+    opt = dict(rays)
+    unknown = set(opt) - {"stride", "margin", "through_cost", "rotate"}
+    if unknown:
+        raise ValueError(f"rays: unknown keys {sorted(unknown)}")
+    stride = int(opt.get("stride", 4))
+    if not 1 <= stride <= int(beams):
+        raise ValueError(f"rays: stride wants 1 .. {int(beams)} (the beams), not {opt.get('stride')!r}")
+    margin = int(opt.get("margin", ray_margin(wall_thickness, step)))
+    if margin < 0:
+        raise ValueError(f"rays: margin wants a count of samples >= 0, not {margin}")
+    through_cost = int(opt.get("through_cost", min(stride * int(outside_cost), 2 ** 32 - 1)))
+    if not 0 <= through_cost < 2 ** 32:
+        raise ValueError(f"rays: through_cost wants 0 .. 2^32 - 1, not {through_cost}")
+    return dict(stride=stride, margin=margin, through_cost=through_cost, rotate=bool(opt.get("rotate", True)))
+
+
 class _OnCover:
     """What ``Localiser`` and ``Tracker`` start from: the covering field of a window, built ONCE in a level of the object's own."""
 
@@ -68,12 +89,13 @@ class _OnCover:
         self.outside_cost = matcher.outside_cost_of(lv) if outside_cost is None else int(outside_cost)
         return lv
 
-    def _build_cover(self):
-        """The level's field (``ScanMatcher._cover``) and its fault bits.  Returns the engine's device."""
-        with self.matcher._cover(self.level, *self.window[:2]) as (eng, _):
+    def _build_cover(self, dist2=False):
+        """The level's field (``ScanMatcher._cover``) and its fault bits.  Returns the engine's device; ``dist2``: and what the
+        build returned -- a distance level's squared distances."""
+        with self.matcher._cover(self.level, *self.window[:2], dist2=dist2) as (eng, built):
             self.eng = eng
             eng.take_flags()
-        return eng.device
+        return (eng.device, built) if dist2 else eng.device
 
 
 class Localiser(_OnCover):
@@ -96,10 +118,20 @@ class Localiser(_OnCover):
     ``bin_xy`` x ``bin_xy`` x ``bin_theta`` over the window that the resampled set occupies and resamples to as many poses as
     the table wants for that number, between ``n_min`` and the capacity.  The count lives in one device word and travels from
     call to call there; ``count`` downloads it, the reports carry it (``n_in``, ``n_out``), and the seeding calls take any
-    ``count`` from 1 to the capacity."""
+    ``count`` from 1 to the capacity.
+
+    ``rays``: None -- the endpoint model alone, and nothing more is built or kept -- or a dict of ``stride``, ``margin``,
+    ``through_cost`` and ``rotate`` (``ray_options`` has the defaults): every step charges a hypothesis ``through_cost`` for each
+    cast beam -- one in ``stride``, all of them once in ``stride`` scans with ``rotate`` -- whose measured range lies more than
+    ``margin`` samples beyond a wall of the map (slam2d_mcl_step_rays), so a cloud on the wrong side of a wall loses the
+    resampling.  The squared wall distances the rays skip by are the Localiser's own: with ``likelihood`` what its one distance
+    build returns, else a copy of what ``clearance``'s cached distance level of the same window gives.  The reports gain
+    ``through`` (``engine.mcl_rays_report_host``); the point forms take no rays."""
+
+    rays = None                                                # (the filled-in options; None: the endpoint model alone)
 
     def __init__(self, matcher, window, particles=4096, level="fine", sigma=(0.05, 0.05, 0.02), temperature=1.0, seed=0,
-                 outside_cost=None, adaptive=None, likelihood=None):
+                 outside_cost=None, adaptive=None, likelihood=None, rays=None):
         self.N = int(particles)
         if not 1 <= self.N <= _lib.MCL_MAX_PARTICLES:
             raise ValueError(f"particles wants 1 .. {_lib.MCL_MAX_PARTICLES}, not {particles!r}")
@@ -110,7 +142,14 @@ class Localiser(_OnCover):
         self.seed = int(seed) & 0xffffffffffffffff
         self.scan = 0                                          # the number of the next scan: part of the generator's counter
         lv = self._plan_cover(matcher, window, level, likelihood, outside_cost)
-        dev = self._build_cover()
+        self.rays = None if rays is None else ray_options(rays, matcher.og.numSamplesPerRev, lv.step, matcher.og.wallThickness, self.outside_cost)
+        if self.rays is None:
+            dev = self._build_cover()
+        elif likelihood is not None:
+            dev, self.d_dist2 = self._build_cover(dist2=True)
+        else:
+            dev = self._build_cover()
+            self.d_dist2 = self._twin_dist2(level)
         lut, self.shift = weight_table(lv.cost_scale, temperature)          # (the distance build has put its table's scale there)
         self.d_lut = torch.from_numpy(lut.view(np.int32)).to(dev)
         self.d_pose = [torch.zeros((self.N, 3), dtype=torch.float64, device=dev) for _ in range(2)]     # ping-pong
@@ -122,6 +161,17 @@ class Localiser(_OnCover):
         self._decode = mcl_report_host                          # of a report, and through its length of the step, chosen once
         if adaptive is not None:
             self._init_adaptive(dict(adaptive))
+        if self.rays is not None:
+            self._decode = mcl_rays_report_host                 # (either length)
+
+    def _twin_dist2(self, level):
+        """The squared distances of the blurred field's frame: a copy of what the matcher's cached distance level of this window
+        gives -- that level is shared, and other calls rebuild it."""
+        lvd = self.matcher._distance_twin(level, self.window[2])
+        with self.matcher._cover(lvd, *self.window[:2], dist2=True) as (eng, d2):
+            same_frames(self.level, lvd)
+            eng.take_flags()
+            return d2.clone()
 
     def _init_adaptive(self, opt):
         unknown = set(opt) - {"n_min", "bin_xy", "bin_theta", "epsilon", "z"}
@@ -208,7 +258,17 @@ class Localiser(_OnCover):
         """One step on the device.  ``source``: the scan's ranges, or -- ``points`` -- the set's (d_points, M)."""
         eng, d_in, d_out = self.eng, self.d_pose[self.cur], self.d_pose[1 - self.cur]
         src = source if points else (source,)
-        if self.adaptive is not None:
+        if self.rays is not None:
+            r = self.rays
+            charge = (r["stride"], self.scan % r["stride"] if r["rotate"] else 0, r["margin"], r["through_cost"])
+            if self.adaptive is not None:
+                eng.mcl_step_adaptive_rays(self.level, 0, self.d_dist2, d_in, d_out, self.N, self.d_count, motion, self.amp, self.seed, self.scan,
+                                           *src, self.outside_cost, *charge, self.d_lut, self.shift, self.bins, self.d_ntab, d_report,
+                                           self.d_ancestor)
+            else:
+                eng.mcl_step_rays(self.level, 0, self.d_dist2, d_in, d_out, self.N, motion, self.amp, self.seed, self.scan, *src,
+                                  self.outside_cost, *charge, self.d_lut, self.shift, d_report, self.d_ancestor)
+        elif self.adaptive is not None:
             step = eng.mcl_step_adaptive_points if points else eng.mcl_step_adaptive
             step(self.level, 0, d_in, d_out, self.N, self.d_count, motion, self.amp, self.seed, self.scan, *src,
                  self.outside_cost, self.d_lut, self.shift, self.bins, self.d_ntab, d_report, self.d_ancestor)
@@ -242,12 +302,17 @@ class Localiser(_OnCover):
             host = d_rep.cpu().numpy()
         return [self._decode(row) for row in host]
 
+    def _no_rays(self, name):
+        if self.rays is not None:
+            raise ValueError(f"{name}: a Localiser with rays takes scans only -- a point set has no single ray origin (rays=None)")
+
     def step_points(self, points, motion):
         """``step`` for a set of points in the robot's frame instead of a scan (slam2d_mcl_step_points, include/slam2d.h):
         ``points`` is ``[M, 2]`` -- x forward, y to the left, metres; rows with a NaN or an infinity are dropped --, M <=
         ``_lib.MAX_POINTS``, as the ``points`` module prepares them: several scans merged by odometry, two sensors, a mounted
         one.  The field is the one the constructor built: a point that ends outside it pays ``outside_cost``.  The same
         download and the same report, whose ``in_range`` is the number of valid points."""
+        self._no_rays("step_points")
         pts = points_of(points)
         self._enqueue((torch.from_numpy(pts).to(self.eng.device), len(pts)), motion, self.d_report, points=True)
         return self._decode(self.d_report)
@@ -256,6 +321,7 @@ class Localiser(_OnCover):
         """A log of point sets: set i, ``[M_i, 2]``, with the motion ``motions[i]`` = (dfwd, dside, dturn) that led to it.  The
         sets may differ in length: they are padded with NaN rows to the longest.  As in ``run`` every step is enqueued without
         a synchronisation and ONE download of the reports ends the call.  Returns the list of decoded reports."""
+        self._no_rays("run_points")
         sets = [points_of(p) for p in point_sets]
         motions = [tuple(float(v) for v in m) for m in motions]
         if not sets or len(motions) != len(sets) or any(len(m) != 3 for m in motions):
