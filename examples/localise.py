@@ -25,7 +25,9 @@ beside the table.  With --adaptive it follows the log with and without the charg
 pose first comes within one cell of the pose the scan was taken at.
 
 --track follows the same log once more with a Tracker: ONE pose on the device, from the search's best peak, moved by the odometry
-increment and refined by a local search per scan (slam2d_refine_poses); its error is printed beside the filter's.
+increment and refined by a local search per scan (slam2d_refine_poses); its error is printed beside the filter's.  With --rays
+the Tracker's search carries the charge too (Tracker(rays=dict(stride=STRIDE)), slam2d_refine_poses_rays) and the through beams of
+each scan's refined pose are printed.
 
 --merge K follows the same log once more with a second filter of the same seed that is given POINTS instead of scans: per step
 the last K scans joined through their odometry (points.merge_scans) -- Localiser.run_points, slam2d_mcl_step_points -- and
@@ -145,7 +147,7 @@ def main():
         table(merged, time.perf_counter() - t0, f"sets of up to {max(len(q) for q in sets)} points ({args.merge} scans each)")
     if args.track:
         # position tracking with ONE pose (Tracker, slam2d_refine_poses): from the search's best peak, refined on the first scan
-        tr = pkg.Tracker(sm, window, level=args.level, likelihood=likelihood)
+        tr = pkg.Tracker(sm, window, level=args.level, likelihood=likelihood, rays=None if args.rays is None else dict(stride=args.rays))
         p = found["peaks"][0]
         tr.set_pose((p.x, p.y, p.theta))
         t0 = time.perf_counter()
@@ -155,7 +157,8 @@ def main():
             x, y, th = t.pose
             mx, my, _ = rep["mean_pose"]
             print(f"true ({r['x']:7.2f}, {r['y']:7.2f}, {r['theta']:6.3f})  tracked ({x:7.3f}, {y:7.3f}, {th:6.3f})  off by "
-                  f"{math.hypot(x - r['x'], y - r['y']):.3f} m (the filter: {math.hypot(mx - r['x'], my - r['y']):.3f} m)  cost {t.start_cost} -> {t.cost}")
+                  f"{math.hypot(x - r['x'], y - r['y']):.3f} m (the filter: {math.hypot(mx - r['x'], my - r['y']):.3f} m)  cost {t.start_cost} -> {t.cost}"
+                  + ("" if args.rays is None else f"  through {int(t.through[-1])}"))
         print(f"{len(log)} scans, one pose: {1e3 * dt / len(log):.3f} ms per scan, upload and the one download included")
 
 

@@ -22,7 +22,9 @@ is printed for both, per point: the last few scans together tell places apart th
 
 With --rays (and --on-device) the peaks are ranked once more by ScanMatcher.scoreRays' cost (slam2d_score_rays): the same cost
 plus, for every beam whose ray crosses a wall of the map well short of its measured range, what a beam that leaves the map pays.
-`through` is printed per peak: a place that fits only because nothing asked what the beams crossed falls behind.
+`through` is printed per peak: a place that fits only because nothing asked what the beams crossed falls behind.  The peaks are
+then refined with that same charged cost (refinePoses(rays=dict(stride=1)), slam2d_refine_poses_rays), so the ranking and the
+refinement agree on what a pose costs; each refined peak's through beams are printed.
 
 `beam_score` (the field's cost summed over every beam) ranks the candidates, not `score` (summed over the set of cells the beams
 end in, the reference's own score): the latter rewards a pose that folds the scan into few cells.  The peak at the true pose is
@@ -127,11 +129,14 @@ def main():
               f"off by {np.hypot(matched['x'] - r['x'], matched['y'] - r['y']):.2f} m, {abs(dth):.3f} rad  [{1e3 * dt:.1f} ms for the lattice, build and download included]")
         if args.on_device:
             # every peak refined in one call (ScanMatcher.refinePoses, slam2d_refine_poses): the best one beside matchScan's, the runners-up too
-            ref = sm.refinePoses([(q.x, q.y, q.theta) for q in found["peaks"]], r, level=args.level, window=window, **lik)
+            # (with --rays: by the charged cost the peaks are ranked by below -- every beam cast, scoreRays' margin and charge)
+            ray_kw = dict(rays=dict(stride=1)) if args.rays else {}
+            ref = sm.refinePoses([(q.x, q.y, q.theta) for q in found["peaks"]], r, level=args.level, window=window, **lik, **ray_kw)
             for i, (q, (x, y, th)) in enumerate(zip(found["peaks"], ref["poses"])):
                 print(f"     {'best     ' if i == 0 else 'runner-up'} ({q.x:7.2f}, {q.y:7.2f}, {q.theta:6.3f}) score {q.score:9.2f}  refinePoses "
                       f"({x:7.3f}, {y:7.3f}, {th:6.3f}) score {ref['score'][i]:9.2f} (cost {int(ref['start_cost'][i])} -> {int(ref['cost'][i])})  "
-                      f"off by {np.hypot(x - r['x'], y - r['y']):.2f} m")
+                      f"off by {np.hypot(x - r['x'], y - r['y']):.2f} m"
+                      + (f"  through {int(ref['through'][i, -1])}" if args.rays else ""))
         if args.on_device and args.rays:
             # the peaks ranked again by a cost that also charges the beams a pose sends through walls (ScanMatcher.scoreRays)
             rays = sm.scoreRays([(q.x, q.y, q.theta) for q in found["peaks"]], r, level=args.level, window=window, **lik)

@@ -653,6 +653,57 @@ int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int3
                         int32_t rx, int32_t ry, int32_t rt, double dx, double dy, double dth,
                         uint32_t outside_cost, uint64_t* d_work, uint64_t* d_out, void* stream);
 
+/* slam2d_refine_poses with slam2d_score_rays' charge per beam that crosses a wall inside the COST of every candidate, on a stride
+ * of the beams: a lattice that straddles a wall no longer steps to the wrong side of it for nothing, which matters most to a
+ * tracker of ONE pose, which has no cloud to outvote the mistake (added symbols: no struct and no existing signature changed, the
+ * ABI number stays).  PRECONDITION: those of slam2d_refine_poses and of slam2d_score_rays -- d_dist2 is the image
+ * slam2d_field_build_distance wrote for slot p_field with lut_n >= 2, on the frame the slot's field was built on.  The same members
+ * of `level` and `lidar` are read.  Integer operations and ONE rounded IEEE operation at a time (no contraction): NumPy reproduces
+ * it bit for bit and the same inputs give the same bits on every call.
+ * Steps a (MOVE), b (CANDIDATES), d (RESULT) and e are slam2d_refine_poses' as written there, and
+ *   c. COST.  For candidate f = (x', y', th') and the seed's scan, sum_b, INSIDE and IN RANGE exactly as in slam2d_refine_poses.
+ *      Beam b is CAST iff b % ray_stride == ray_phase.  A CAST beam in range is CHECKED iff its quotient r_b / step (one true
+ *      division) lies in [0, 1e9); then kend = (int64)(r_b / step) - margin, and the beam is THROUGH iff kend >= 0 and THE RAY
+ *      (above slam2d_cast_rays: the same sample formula, the `0 <=` guard, d_dist2) from (x', y') along a_b -- formed from th'
+ *      exactly as the endpoint's: a0 = th' - fov/2, ..., c = cos(a_b), s = sin(a_b) -- is HIT at some k <= kend.  through(f) = the
+ *      number of THROUGH beams of the candidate;
+ *        cost(f) = sum_b + (uint64)(in_range - inside) * outside_cost + (uint64)through(f) * through_cost
+ *      -- below 2^44 by the argument of slam2d_mcl_step_rays (two terms of at most 2048 * 2^32 = 2^43), so cost(f) << 20 | f still
+ *      fits one 64-bit word.
+ *   RESULT.  d_out[n * SLAM2D_REFINE_STRIDE + 0] = the 64-bit minimum over f of (cost(f) << 20 | f) on this cost, word 1 = the
+ *      charged cost(0), d_pose_out the winning candidate by the three operations of b.  d_through: NULL (not wanted), or [N]:
+ *      d_through[n] = through(f) of the winning candidate.  A seed with a non-finite component keeps f = 0 with through = 0: its
+ *      ray is LEFT at 0 on every beam.
+ * EQUIVALENCES.  (i) With through_cost == 0, or no CAST beam (ray_phase >= beams), or a margin beyond every range's quotient, the
+ * two words and d_pose_out are slam2d_refine_poses' bit for bit.  (ii) With ray_stride == 1, word 0 is the minimum over f of
+ * (slot 0 of slam2d_score_rays at the materialised candidate f, same margin and costs, the seed's scan) << 20 | f, word 1 is that
+ * call's slot 0 at f = 0, and d_through[n] its slot 4 at the winner.
+ * d_work: slam2d_refine_rays_work(N) == slam2d_refine_work(N) words; the caller need not initialise d_work, d_out, d_pose_out or
+ * d_through.  The call allocates nothing, raises no fault bit, does not synchronise and enqueues three launches on `stream`: the
+ * move, slam2d_refine_poses' own; the search, a block of 256 threads per seed and hc headings -- hc is slam2d_refine_poses': hc =
+ * min(max(1, 2048 / beams), ceil(nth / ceil(1024 / N))); the block keeps a second LDS table, the unit vectors (cos a_b, sin a_b)
+ * per heading and KEPT beam, beside the endpoint offsets, both from one evaluation of cos / sin: the headings per row stay, the
+ * block's LDS grows to 16 hc (beams + J) + 4 (beams + J) bytes, J the number of cast beams, at most 80 KiB --, where
+ * the KEPT beams are the cast beams that are CHECKED with kend >= 0 (no other can be THROUGH at any pose), compacted once per
+ * block, the lanes of a wave are neighbouring positions of one heading and walk one beam's parallel rays together, and the join
+ * is the 64-bit integer atomicMin on d_out; the winners, where d_through is wanted a wave per seed, which recasts the winner's
+ * cast beams packed over its lanes by the search's own expressions (d_through == NULL: slam2d_refine_poses' own last launch).
+ * Every ray ends: its sample index strictly increases below kend + 1 < 2^30.
+ * SLAM2D_E_BADARG, before any HIP call: every case of slam2d_refine_poses, a NULL d_dist2, ray_stride < 1 or > SLAM2D_MAX_BEAMS,
+ * ray_phase < 0 or >= ray_stride, margin < 0; SLAM2D_E_TOOLARGE: as there -- nx * ny * nth > SLAM2D_REFINE_MAX_CANDIDATES, more
+ * than SLAM2D_REFINE_MAX_BLOCKS blocks in the search launch, N * ceil(nth / hc) with the hc above (the last launch has
+ * ceil(N / 4)), fmax * fpitch >= 2^29, a device that does not grant the block its LDS.  slam2d_refine_rays_work makes no HIP call and answers what slam2d_refine_work answers,
+ * error codes included. */
+int64_t slam2d_refine_rays_work(int32_t N);                     /* slam2d_refine_work(N) */
+int slam2d_refine_poses_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t N,
+                             const double* d_pose_in, double* d_pose_out, int32_t pose_stride,
+                             const double* d_ranges, int32_t ranges_stride,
+                             const double motion[3],            /* NULL: none */
+                             int32_t rx, int32_t ry, int32_t rt, double dx, double dy, double dth, uint32_t outside_cost,
+                             int32_t ray_stride, int32_t ray_phase, int32_t margin, uint32_t through_cost,
+                             uint32_t* d_through,               /* NULL: not wanted */
+                             uint64_t* d_work, uint64_t* d_out, void* stream);
+
 /* The two on-device searches for a SET OF POINTS in the robot's frame instead of one scan of one sensor: several scans joined by
  * odometry, two sensors on one robot, a sensor off the robot's origin, a driver's own or de-skewed beam angles -- whatever the
  * caller can express as points (added symbols: no struct and no existing signature changed, the ABI number stays).  The scan

@@ -40,6 +40,7 @@ _LAZY = {
     "Localiser": ("localise", "Localiser"),
     "Tracker": ("localise", "Tracker"),
     "TrackReport": ("localise", "TrackReport"),
+    "TrackRaysReport": ("localise", "TrackRaysReport"),
 }
 
 

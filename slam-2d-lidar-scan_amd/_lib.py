@@ -205,6 +205,10 @@ SIGNATURES = {
     "slam2d_refine_poses": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_int32,
                                       C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
                                       C.c_uint32, _vp, _vp, _vp]),
+    "slam2d_refine_rays_work": (C.c_int64, [C.c_int32]),
+    "slam2d_refine_poses_rays": (C.c_int, [C.POINTER(Slam2dLidar), C.POINTER(Slam2dLevel), C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp,
+                                           C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                           C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "slam2d_search_points_work": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "slam2d_search_points": (C.c_int, [C.POINTER(Slam2dLevel), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_int32, C.c_int32,

@@ -4899,6 +4899,151 @@ __global__ __launch_bounds__(256) void k_refine_pose(int N, RefineLattice lat, c
     o[2] = moved[(size_t)n * 3 + 2] + (double)refine_off(jt) * lat.dth;
 }
 
+// ---- the local search with a charge per beam that crosses a wall (slam2d_refine_poses_rays) ----
+// COST with slam2d_score_rays' THROUGH beams on a stride of the scan: the endpoint part of a candidate is offsets_cost on
+// k_refine_search's table, the ray pass behind it is ray_walk.  The move launch is k_refine_move; the search and the last launch
+// are this section's.
+#define REFINE_RAYS_WAVES 4          // seeds (waves) per block of the last launch
+
+// The CAST beams, the margin and the charge of a refinement
+struct RefineRays { int stride, phase, margin; unsigned through_cost; };
+
+// CHECKED and kend of a beam in range, k_score_rays' lines: -1 where the beam is not checked (never THROUGH, as kend < 0)
+__device__ __forceinline__ long long refine_ray_kend(const double r, const double step, const int margin) {
+    const double q = r / step;
+    return q >= 0.0 && q < 1e9 ? (long long)q - margin : -1ll;
+}
+
+// J, the number of CAST beams: phase + (J - 1) * stride <= B - 1
+__host__ __device__ __forceinline__ int refine_rays_cast(const int B, const int stride, const int phase) {
+    return phase < B ? (B - 1 - phase) / stride + 1 : 0;
+}
+// The search block's dynamic LDS: E[hc][B] and U[hc][J] of 16 bytes, kend_s[J] of 4, bidx[B] and kslot[B] of 2 -- 40 KB at 180
+// beams, stride 4 and the most headings a row takes (11), at most 80 KiB (2048 beams, stride 1)
+static size_t refine_rays_lds_bytes(const int hc, const int B, const int J) { return 16 * (size_t)hc * (B + J) + 4 * (size_t)(B + J); }
+
+// Search launch: k_refine_search's block and headings per block row (the same hc: the second table enlarges the block's LDS,
+// which is dynamic so that a block asks for what its beams need and several share a CU), its phases with three things more:
+//   1. beside the beams IN RANGE (bidx), the KEPT ones among them -- CAST, CHECKED and kend >= 0: the others are never THROUGH,
+//      whatever the pose --, compacted in beam order: kslot[k] = the kept slot of the k-th beam in range (NO_SLOT: not kept),
+//      kend_s[j] = kend of the j-th kept beam;
+//   2. with E[h][k], U[h][j] = (cos(a), sin(a)) of heading h and the j-th kept beam: ONE evaluation of cos / sin gives both (E's
+//      rounded products cannot give them back);
+//   3. the candidates, jx fastest over the threads as in refine_candidates, in WHOLE waves: ray_walk is a ballot loop, so a lane
+//      behind the last candidate runs every trip with active = false (it walks nothing and costs nothing).  A lane's endpoint cost
+//      is offsets_cost; then the kept beams in turn, one ray_walk per beam for the wave -- its lanes are neighbouring positions of
+//      (mostly) one heading: parallel rays about a cell apart, of one length, whose gathers fall on neighbouring cells.  A
+//      non-finite candidate is LEFT at 0 on every beam.  cost << 20 | f is joined as in refine_candidates; the thread that holds
+//      f == 0 stores its charged cost in out[2 n + 1].
+// Every ray ends: ray_walk's k strictly increases below kend + 1 < 2^30.  Reads frames[p_field], the slot's field and squared
+// distances, the moved seeds and the ranges; no fault bit.
+#define REFINE_NO_SLOT 0xffffu
+__global__ __launch_bounds__(256) void k_refine_search_rays(Slam2dLidar lid, Slam2dLevel lv, int p_field, const uint32_t* __restrict__ dist2, int rows,
+                                                            int hc, RefineLattice lat, const double* __restrict__ moved,
+                                                            const double* __restrict__ ranges, int rstride, unsigned outside_cost, RefineRays ry,
+                                                            unsigned long long* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char refine_rays_lds[];     // refine_rays_lds_bytes(hc, B, J)
+    __shared__ int wcount[4];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const RefineBlock rb = refine_block(rows, hc, lat, moved);
+    const SlotField sf = slot_field(lv, p_field);
+    const RayField f = ray_field(lv, p_field, dist2);
+    const double* __restrict__ rg = ranges + (size_t)rb.n * rstride;
+    const int B = lid.beams, J = refine_rays_cast(B, ry.stride, ry.phase);
+    double2* E = reinterpret_cast<double2*>(refine_rays_lds);                    // [hc][B]: hn * n_rng in use
+    double2* U = E + (size_t)hc * B;                                             // [hc][J]: hn * n_kept in use
+    int* kend_s = reinterpret_cast<int*>(U + (size_t)hc * J);                    // [J]
+    unsigned short* bidx = reinterpret_cast<unsigned short*>(kend_s + J);        // [B]
+    unsigned short* kslot = bidx + B;                                            // [B]
+    int n_rng = 0, n_kept = 0;                                                   // beams in range, kept beams (block-uniform)
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int b = b0 + tid;
+        const double r = b < B ? rg[b] : NAN;
+        const bool in_range = r < lid.max_range;                                 // :84 (NaN and +inf are out, 0 and negatives in)
+        const long long kend = in_range && b % ry.stride == ry.phase ? refine_ray_kend(r, lv.step, ry.margin) : -1ll;
+        const int slot = block_compact_slot(in_range, wcount, wv, lane, n_rng);
+        const int kept = block_compact_slot(kend >= 0, wcount, wv, lane, n_kept);
+        if (in_range) {
+            bidx[slot] = (unsigned short)b;
+            kslot[slot] = kend >= 0 ? (unsigned short)kept : (unsigned short)REFINE_NO_SLOT;
+        }
+        if (kend >= 0) kend_s[kept] = (int)kend;                                 // (below 1e9)
+    }
+    __syncthreads();
+    for (int i = tid; i < rb.hn * n_rng; i += 256) {                             // (hn * n_rng <= REFINE_TABLE)
+        const int h = i / n_rng, k = i - h * n_rng, b = bidx[k];
+        const double r = rg[b];
+        const double a = fan_of(lid, rb.tm + (double)refine_off(rb.jt0 + h) * lat.dth).angle(b);
+        const double c = cos(a), s = sin(a);
+        E[i] = make_double2(c * r, s * r);                                       // :87-88
+        const unsigned j = kslot[k];
+        if (j != REFINE_NO_SLOT) U[h * n_kept + (int)j] = make_double2(c, s);
+    }
+    __syncthreads();
+    const int P = lat.nx * lat.ny, f0 = rb.jt0 * P, total = rb.hn * P;           // (nx * ny * nth <= 2^20)
+    unsigned long long best = ~0ull;
+    for (int c0 = 0; c0 < total; c0 += 256) {                                    // (block-uniform: whole waves reach ray_walk)
+        const int c = c0 + tid;
+        const bool active = c < total;
+        const int h = active ? c / P : 0, p = active ? c - h * P : 0, jy = p / lat.nx, jx = p - jy * lat.nx;
+        const double x = rb.xm + (double)refine_off(jx) * lat.dx, y = rb.ym + (double)refine_off(jy) * lat.dy;
+        unsigned long long cost = 0ull;
+        if (active) cost = offsets_cost(E + h * n_rng, n_rng, x, y, sf.fr, lv.step, sf.fs, lv.fpitch, sf.field, outside_cost);
+        const double2* __restrict__ u = U + h * n_kept;
+        int thr = 0;
+        for (int j = 0; j < n_kept; ++j) {                                       // (block-uniform)
+            const double2 d = u[j];
+            const uint32_t word = ray_walk(f, x, y, d.x, d.y, kend_s[j], active);
+            thr += active && (word >> 30) == SLAM2D_RAY_HIT;                      // (a HIT lies at k <= the limit, kend)
+        }
+        if (active) {
+            cost += (unsigned long long)thr * ry.through_cost;                   // (below 2^44: two terms of at most 2^43)
+            if (f0 + c == 0) out[(size_t)rb.n * SLAM2D_REFINE_STRIDE + 1] = cost;
+            best = min(best, (cost << 20) | (unsigned long long)(f0 + c));
+        }
+    }
+    best = wave64_min_u64(best);
+    if (lane == 0 && best != ~0ull) atomicMin(&out[(size_t)rb.n * SLAM2D_REFINE_STRIDE], best);
+}
+
+// Last launch, a wave per seed: k_refine_pose's winning pose -- every lane forms it, lane 0 stores it --, then that pose's CAST
+// beams packed over the lanes as in mcl_score_rays_particle, 64 rays a trip: a_b, cos and sin by the search's own expressions on
+// the same th', so the rays are the searching thread's bit for bit and through[n] is the count inside the winning word.
+__global__ __launch_bounds__(64 * REFINE_RAYS_WAVES) void k_refine_pose_rays(Slam2dLidar lid, Slam2dLevel lv, int p_field,
+                                                                            const uint32_t* __restrict__ dist2, int N, RefineLattice lat,
+                                                                            const double* __restrict__ moved, const double* __restrict__ ranges,
+                                                                            int rstride, RefineRays ry, const unsigned long long* __restrict__ out,
+                                                                            double* __restrict__ pose, int pstride, uint32_t* __restrict__ through) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * REFINE_RAYS_WAVES + (threadIdx.x >> 6);
+    if (n >= N) return;                                                          // (wave-uniform)
+    const int fi = (int)(out[(size_t)n * SLAM2D_REFINE_STRIDE] & 0xfffffull);
+    const int P = lat.nx * lat.ny, jt = fi / P, p = fi - jt * P, jy = p / lat.nx, jx = p - jy * lat.nx;
+    const double x = moved[(size_t)n * 3] + (double)refine_off(jx) * lat.dx;
+    const double y = moved[(size_t)n * 3 + 1] + (double)refine_off(jy) * lat.dy;
+    const double th = moved[(size_t)n * 3 + 2] + (double)refine_off(jt) * lat.dth;
+    if (lane == 0) {
+        double* o = pose + (size_t)n * pstride;
+        o[0] = x; o[1] = y; o[2] = th;
+    }
+    const RayField f = ray_field(lv, p_field, dist2);
+    const double* __restrict__ rg = ranges + (size_t)n * rstride;
+    const int B = lid.beams;
+    const BeamFan fan = fan_of(lid, th);
+    const int J = refine_rays_cast(B, ry.stride, ry.phase);
+    int n_thr = 0;
+    for (int j0 = 0; j0 < J; j0 += 64) {                                         // (wave-uniform trip count)
+        const bool cast = j0 + lane < J;
+        const int b = cast ? ry.phase + (j0 + lane) * ry.stride : 0;
+        const double r = cast ? rg[b] : NAN;
+        const long long kend = r < lid.max_range ? refine_ray_kend(r, lv.step, ry.margin) : -1ll;
+        const double a = fan.angle(b);
+        const uint32_t word = ray_walk(f, x, y, cos(a), sin(a), kend >= 0 ? (int)kend : 0, kend >= 0);
+        n_thr += __popcll(__ballot(kend >= 0 && (word >> 30) == SLAM2D_RAY_HIT));
+    }
+    if (lane == 0) through[n] = (uint32_t)n_thr;
+}
+
 // ---- the two searches for a set of points in the robot's frame (slam2d_search_points, slam2d_refine_points) ----
 // The table is the only place where the searches look at their input: E[heading][k] = R(heading) q of the k-th VALID point q, and
 // offsets_cost, the packed minima and the joins behind it are the scan forms'.  A heading costs ONE cos / sin, whatever M.
@@ -6858,6 +7003,41 @@ int slam2d_refine_poses(const Slam2dLidar* lidar, const Slam2dLevel* level, int3
     return launch_refine(N, d_pose_in, d_pose_out, pose_stride, motion, w, d_work, d_out, s, [&](unsigned blocks, double* moved, unsigned long long* out) {
         k_refine_search<<<blocks, 256, 0, s>>>(*lidar, *level, p_field, (int)w.rows, w.hc, w.lat, moved, d_ranges, ranges_stride, outside_cost, out);
     });
+}
+
+int64_t slam2d_refine_rays_work(int32_t N) { return slam2d_refine_work(N); }
+
+int slam2d_refine_poses_rays(const Slam2dLidar* lidar, const Slam2dLevel* level, int32_t p_field, const uint32_t* d_dist2, int32_t N,
+                             const double* d_pose_in, double* d_pose_out, int32_t pose_stride, const double* d_ranges, int32_t ranges_stride,
+                             const double motion[3], int32_t rx, int32_t ry, int32_t rt, double dx, double dy, double dth, uint32_t outside_cost,
+                             int32_t ray_stride, int32_t ray_phase, int32_t margin, uint32_t through_cost, uint32_t* d_through, uint64_t* d_work,
+                             uint64_t* d_out, void* stream) {
+    const int frc = check_scored_field(lidar, level, p_field);
+    if (frc == SLAM2D_E_BADARG) return frc;
+    if (!d_dist2 || !d_pose_in || !d_pose_out || !d_ranges || !d_out || !d_work || d_pose_in == d_pose_out) return SLAM2D_E_BADARG;
+    if (N < 1 || pose_stride < 3 || (ranges_stride != 0 && ranges_stride < lidar->beams)) return SLAM2D_E_BADARG;
+    if (ray_stride < 1 || ray_stride > SLAM2D_MAX_BEAMS || ray_phase < 0 || ray_phase >= ray_stride || margin < 0) return SLAM2D_E_BADARG;
+    RefineWindow w;
+    const int wrc = check_refine_window(N, lidar->beams, rx, ry, rt, dx, dy, dth, motion, &w);   // (the search's blocks; the last launch has N / 4)
+    if (wrc) return wrc;
+    if (frc) return frc;
+    hipStream_t s = (hipStream_t)stream;
+    double* moved = reinterpret_cast<double*>(d_work);
+    unsigned long long* out = (unsigned long long*)d_out;
+    const RefineRays rays{ray_stride, ray_phase, margin, through_cost};
+    const size_t lds = refine_rays_lds_bytes(w.hc, lidar->beams, refine_rays_cast(lidar->beams, ray_stride, ray_phase));
+    static size_t granted[64] = {};
+    if (!grant_dynamic_lds(reinterpret_cast<const void*>(k_refine_search_rays), granted, lds)) return SLAM2D_E_TOOLARGE;     // (above 64 KiB: asked for once)
+    k_refine_move<<<cdiv(N, 256), 256, 0, s>>>(N, d_pose_in, pose_stride, motion != nullptr, motion ? motion[0] : 0.0, motion ? motion[1] : 0.0,
+                                               motion ? motion[2] : 0.0, moved, out);
+    k_refine_search_rays<<<(unsigned)(N * w.rows), 256, lds, s>>>(*lidar, *level, p_field, d_dist2, (int)w.rows, w.hc, w.lat, moved, d_ranges,
+                                                                ranges_stride, outside_cost, rays, out);
+    if (d_through)
+        k_refine_pose_rays<<<cdiv(N, REFINE_RAYS_WAVES), 64 * REFINE_RAYS_WAVES, 0, s>>>(*lidar, *level, p_field, d_dist2, N, w.lat, moved, d_ranges,
+                                                                                         ranges_stride, rays, out, d_pose_out, pose_stride, d_through);
+    else
+        k_refine_pose<<<cdiv(N, 256), 256, 0, s>>>(N, w.lat, moved, out, d_pose_out, pose_stride);
+    return launch_status();
 }
 
 // the checks slam2d_search_points and its work size share; *words: the 8-byte words of d_work (the offset table)

@@ -1434,10 +1434,26 @@ class ParticleEngine:
         return self._refine("slam2d_refine_poses", (C.byref(self.lidar_c),), level, p_field, d_in, d_out, N, pose_stride,
                             (_ptr(d_ranges), ranges_stride), radii, steps, outside_cost, motion, d_words)
 
-    def _refine(self, name, head, level, p_field, d_in, d_out, N, pose_stride, source, radii, steps, outside_cost, motion, d_words):
-        """The body of ``refine_poses`` and ``refine_points``, the library's ``name``: the two pose buffers, the shared scratch, the
-        words and the packing of radii, steps and motion.  ``head``: the call's arguments before the level; ``source``: the scans'
-        or the point sets' arguments."""
+    def refine_poses_rays(self, level, p_field, d_dist2, d_in, d_out, N, pose_stride, d_ranges, ranges_stride, radii, steps, outside_cost,
+                          ray_stride, ray_phase, margin, through_cost, motion=None, d_words=None, d_through=None):
+        """``refine_poses`` with ``score_rays``' charge inside every candidate's cost (include/slam2d.h, slam2d_refine_poses_rays):
+        every beam b with ``b % ray_stride == ray_phase`` whose measured range lies more than ``margin`` samples beyond a wall of
+        the field costs the candidate ``through_cost``.  ``d_dist2`` as in ``cast_rays``, of the frame the slot's field stands on;
+        ``d_through``: None or [N] int32, the through beams of every seed's winner.  The same ``[N, 2]`` int64 words on the charged
+        cost -- ``refine_host`` decodes them unchanged -- and the winning poses in ``d_out``.  Three launches on the current stream,
+        no synchronisation; ``refine_poses``' scratch."""
+        if d_through is not None and (d_through.numel() < N or d_through.element_size() != 4):
+            raise ValueError(f"d_through wants {N} 32-bit words")
+        return self._refine("slam2d_refine_poses_rays", (C.byref(self.lidar_c),), level, p_field, d_in, d_out, N, pose_stride,
+                            (_ptr(d_ranges), ranges_stride), radii, steps, outside_cost, motion, d_words,
+                            rays=((_ptr(d_dist2),), (int(ray_stride), int(ray_phase), int(margin), int(through_cost), _ptr(d_through))))
+
+    def _refine(self, name, head, level, p_field, d_in, d_out, N, pose_stride, source, radii, steps, outside_cost, motion, d_words,
+                rays=((), ())):
+        """The body of ``refine_poses``, ``refine_points`` and ``refine_poses_rays``, the library's ``name``: the two pose buffers,
+        the shared scratch, the words and the packing of radii, steps and motion.  ``head``: the call's arguments before the level;
+        ``source``: the scans' or the point sets' arguments; ``rays``: what the ray form adds behind the slot and behind
+        ``outside_cost``."""
         _check_slot(level, p_field)
         work = self._scratch("_refine_work", self.L.slam2d_refine_work(N), "slam2d_refine_work")
         if d_in.numel() < (N - 1) * pose_stride + 3 or d_out.numel() < (N - 1) * pose_stride + 3:
@@ -1447,9 +1463,9 @@ class ParticleEngine:
             raise ValueError(f"d_words wants {N} x {_lib.REFINE_STRIDE} 64-bit words")
         rx, ry, rt = (int(v) for v in radii)
         dx, dy, dth = (float(v) for v in steps)
-        check(getattr(self.L, name)(*head, C.byref(level.c), p_field, N, _ptr(d_in), _ptr(d_out), pose_stride, *source,
-                                    None if motion is None else _triple(motion), rx, ry, rt, dx, dy, dth, int(outside_cost), _ptr(work), _ptr(out),
-                                    _stream()), name)
+        check(getattr(self.L, name)(*head, C.byref(level.c), p_field, *rays[0], N, _ptr(d_in), _ptr(d_out), pose_stride, *source,
+                                    None if motion is None else _triple(motion), rx, ry, rt, dx, dy, dth, int(outside_cost), *rays[1],
+                                    _ptr(work), _ptr(out), _stream()), name)
         return out
 
     refine_host = staticmethod(refine_host)

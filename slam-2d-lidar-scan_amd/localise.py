@@ -97,6 +97,15 @@ class _OnCover:
             eng.take_flags()
         return (eng.device, built) if dist2 else eng.device
 
+    def _twin_dist2(self, level):
+        """The squared distances of the blurred field's frame: a copy of what the matcher's cached distance level of this window
+        gives -- that level is shared, and other calls rebuild it."""
+        lvd = self.matcher._distance_twin(level, self.window[2])
+        with self.matcher._cover(lvd, *self.window[:2], dist2=True) as (eng, d2):
+            same_frames(self.level, lvd)
+            eng.take_flags()
+            return d2.clone()
+
 
 class Localiser(_OnCover):
     """Monte-Carlo localisation in ``matcher``'s map, taken as static.
@@ -163,15 +172,6 @@ class Localiser(_OnCover):
             self._init_adaptive(dict(adaptive))
         if self.rays is not None:
             self._decode = mcl_rays_report_host                 # (either length)
-
-    def _twin_dist2(self, level):
-        """The squared distances of the blurred field's frame: a copy of what the matcher's cached distance level of this window
-        gives -- that level is shared, and other calls rebuild it."""
-        lvd = self.matcher._distance_twin(level, self.window[2])
-        with self.matcher._cover(lvd, *self.window[:2], dist2=True) as (eng, d2):
-            same_frames(self.level, lvd)
-            eng.take_flags()
-            return d2.clone()
 
     def _init_adaptive(self, opt):
         unknown = set(opt) - {"n_min", "bin_xy", "bin_theta", "epsilon", "z"}
@@ -340,6 +340,20 @@ class Localiser(_OnCover):
 
 
 TrackReport =collections.namedtuple("TrackReport", "pose cost start_cost offsets")
+TrackRaysReport = collections.namedtuple("TrackRaysReport", "pose cost start_cost offsets through")
+
+
+def track_report_host(row, stages, cost_scale, rays=False):
+    """A downloaded row of a ``Tracker``'s scan -- the pose, the stages' two words as doubles' bits and, with ``rays``, the stages'
+    through counts, 32-bit words two to a double -- as a ``TrackReport`` or a ``TrackRaysReport``."""
+    row = np.ascontiguousarray(row, dtype=np.float64).reshape(-1)
+    n = 3 + _lib.REFINE_STRIDE * len(stages)
+    words = row[3:n].view(np.uint64).reshape(len(stages), _lib.REFINE_STRIDE)
+    dec = [refine_host(words[i], radii, steps, cost_scale) for i, (radii, steps) in enumerate(stages)]
+    head = (tuple(float(v) for v in row[:3]), int(dec[-1]["cost"][0]), int(dec[0]["start_cost"][0]), np.stack([d["offsets"][0] for d in dec]))
+    if not rays:
+        return TrackReport(*head)
+    return TrackRaysReport(*head, row[n:].view(np.uint32)[:len(stages)].astype(np.int64))
 
 
 class Tracker(_OnCover):
@@ -351,17 +365,37 @@ class Tracker(_OnCover):
     the level's step).  A scan moves the pose by the odometry increment and searches the stages' lattices about it
     (slam2d_refine_poses, include/slam2d.h, with N = 1; the motion goes into the first stage): the pose lives on the device
     across calls, a scan costs an upload of its ranges and, if the pose is wanted at once, a download of 24 + 16 bytes per
-    stage.  Integer costs and rounded operations: a run is the same bits every time."""
+    stage.  Integer costs and rounded operations: a run is the same bits every time.
 
-    def __init__(self, matcher, window, level="fine", stages=None, likelihood=None, outside_cost=None):
+    ``rays``: None -- the endpoint cost alone: nothing more is built, kept or downloaded -- or a dict as for ``Localiser``
+    (``ray_options``: ``stride``, ``margin``, ``through_cost``, ``rotate``): every candidate of every stage pays ``through_cost``
+    for each cast beam whose measured range lies more than ``margin`` samples beyond a wall of the map
+    (slam2d_refine_poses_rays), so the one pose does not step through a wall that its lattice straddles; one phase per scan --
+    the scan number mod ``stride`` with ``rotate`` -- serves all its stages.  The squared distances come as ``Localiser``'s do.
+    ``step`` and ``run`` then return ``TrackRaysReport``s, with ``through`` [stages]: the through beams of each stage's winner,
+    four more bytes per stage in the same download; ``step_points`` takes no rays."""
+
+    rays = None                                                # (the filled-in options; None: the endpoint cost alone)
+
+    def __init__(self, matcher, window, level="fine", stages=None, likelihood=None, outside_cost=None, rays=None):
         lv = self._plan_cover(matcher, window, level, likelihood, outside_cost)
         self.stages = check_stages(stages, lv.step)
-        dev = self._build_cover()
+        self.rays = None if rays is None else ray_options(rays, matcher.og.numSamplesPerRev, lv.step, matcher.og.wallThickness, self.outside_cost)
+        self.scan = 0                                          # the number of the next scan: the phase of a rotating stride
+        if self.rays is None:
+            dev = self._build_cover()
+        elif likelihood is not None:
+            dev, self.d_dist2 = self._build_cover(dist2=True)
+        else:
+            dev = self._build_cover()
+            self.d_dist2 = self._twin_dist2(level)
         self.d_pose = [torch.zeros(3, dtype=torch.float64, device=dev) for _ in range(2)]               # ping-pong
         self.cur = 0
         self.d_ranges = torch.empty(matcher.og.numSamplesPerRev, dtype=torch.float64, device=dev)
         # what one step downloads: the pose, then the stages' words (as doubles' bits)
-        self.d_report = torch.empty(3 + _lib.REFINE_STRIDE * len(self.stages), dtype=torch.float64, device=dev)
+        # (with rays: and the stages' through counts, 32-bit words two to a double)
+        self._words = 3 + _lib.REFINE_STRIDE * len(self.stages)
+        self.d_report = torch.empty(self._words + (0 if self.rays is None else (len(self.stages) + 1) // 2), dtype=torch.float64, device=dev)
 
     def set_pose(self, pose):
         pose = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(3))
@@ -376,19 +410,26 @@ class Tracker(_OnCover):
         """The stages of one scan or one point set: ``refine`` is the engine's ``refine_poses`` or ``refine_points``, ``source`` its
         arguments between the pose stride and the radii.  The last stage's pose also goes to the head of ``d_report`` (a row like
         ``self.d_report``), the stages' words behind it."""
-        d_words = d_report[3:].view(torch.int64).view(len(self.stages), _lib.REFINE_STRIDE)
+        d_words = d_report[3:self._words].view(torch.int64).view(len(self.stages), _lib.REFINE_STRIDE)
+        if self.rays is not None:
+            r = self.rays
+            charge = (r["stride"], self.scan % r["stride"] if r["rotate"] else 0, r["margin"], r["through_cost"])
+            d_through = d_report[self._words:].view(torch.int32)
         for i, (radii, steps) in enumerate(self.stages):
-            refine(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], 1, 3, *source, radii, steps, self.outside_cost,
-                   motion=motion if i == 0 else None, d_words=d_words[i])
+            if self.rays is not None:
+                self.eng.refine_poses_rays(self.level, 0, self.d_dist2, self.d_pose[self.cur], self.d_pose[1 - self.cur], 1, 3, *source, radii, steps,
+                                           self.outside_cost, *charge, motion=motion if i == 0 else None, d_words=d_words[i],
+                                           d_through=d_through[i:i + 1])
+            else:
+                refine(self.level, 0, self.d_pose[self.cur], self.d_pose[1 - self.cur], 1, 3, *source, radii, steps, self.outside_cost,
+                       motion=motion if i == 0 else None, d_words=d_words[i])
             self.cur = 1 - self.cur
         d_report[:3].copy_(self.d_pose[self.cur])
+        self.scan += 1
 
     def _report(self, row):
         """A downloaded row of ``_enqueue`` as a ``TrackReport``."""
-        words = row[3:].view(np.uint64).reshape(len(self.stages), _lib.REFINE_STRIDE)
-        dec = [refine_host(words[i], radii, steps, self.level.cost_scale) for i, (radii, steps) in enumerate(self.stages)]
-        return TrackReport(tuple(float(v) for v in row[:3]), int(dec[-1]["cost"][0]), int(dec[0]["start_cost"][0]),
-                           np.stack([d["offsets"][0] for d in dec]))
+        return track_report_host(row, self.stages, self.level.cost_scale, self.rays is not None)
 
     def step(self, reading_or_ranges, motion):
         """One scan: the pose moved by ``motion`` = (dfwd, dside, dturn) in the robot's own previous frame (None: not moved), then
@@ -404,6 +445,8 @@ class Tracker(_OnCover):
         ``points`` is ``[M, 2]`` -- x forward, y to the left, metres; rows with a NaN or an infinity are dropped --, M <=
         ``_lib.MAX_POINTS``, as the ``points`` module prepares them.  The field is the one the constructor built: a point that
         ends outside it pays ``outside_cost``.  The same stages, the same download, the same ``TrackReport``."""
+        if self.rays is not None:
+            raise ValueError("step_points: a Tracker with rays takes scans only -- a point set has no single ray origin (rays=None)")
         pts = points_of(points)
         with pinned_stream():
             self._enqueue(self.eng.refine_points, (torch.from_numpy(pts).to(self.eng.device), len(pts), 0), motion, self.d_report)

@@ -292,6 +292,21 @@ def check_stages(stages, step):
     return tuple(out)
 
 
+def refine_ray_options(rays, beams, step, wall_thickness, outside_cost):
+    """``refinePoses``' ``rays`` with its defaults filled in: ``stride``, ``margin`` and ``through_cost`` as ``localise.ray_options``
+    fills and checks them, and ``phase`` (0) -- which beams are cast, b % stride == phase -- in place of ``rotate``.  ValueError for
+    an unknown key (``rotate`` among them), a phase outside 0 .. stride - 1 and whatever ``ray_options`` refuses."""
+    from .localise import ray_options                          # (localise imports this module)
+    opt = dict(rays)
+    if "rotate" in opt:
+        raise ValueError("rays: unknown keys ['rotate'] (a refinement takes a phase)")
+    phase = opt.pop("phase", 0)
+    full = ray_options(opt, beams, step, wall_thickness, outside_cost)
+    if int(phase) != phase or not 0 <= int(phase) < full["stride"]:
+        raise ValueError(f"rays: phase wants 0 .. {full['stride'] - 1} (below the stride), not {phase!r}")
+    return dict(stride=full["stride"], phase=int(phase), margin=full["margin"], through_cost=full["through_cost"])
+
+
 class ScanMatcher:
     def __init__(self, og, searchRadius, searchHalfRad, scanSigmaInNumGrid, moveRSigma, maxMoveDeviation, turnSigma,
                  missMatchProbAtCoarse, coarseFactor):
@@ -643,7 +658,7 @@ class ScanMatcher:
                              int(res["cost"][iy, ix])) for iy, ix, it in lattice_peaks(res["cost"], res["heading"], top, sep)]
         return res
 
-    def refinePoses(self, poses, reading_or_ranges, stages=None, level="fine", window=None, likelihood=None, outside_cost=None):
+    def refinePoses(self, poses, reading_or_ranges, stages=None, level="fine", window=None, likelihood=None, outside_cost=None, rays=None):
         """The best pose near each of N free seed poses (include/slam2d.h, slam2d_refine_poses): a local correlative search about
         every ``poses[n] = (x, y, theta)`` in the covering level of ``scorePoses`` and ``searchPoses`` -- the same frame planning
         (the bounding box of the finite seeds, or ``window``), the same ``likelihood`` and the same ``outside_cost`` default --,
@@ -652,7 +667,13 @@ class ScanMatcher:
         ``default_stages`` of the level's step).  ``reading_or_ranges``: a reading dict, ``[beams]`` ranges for every seed, or
         ``[N, beams]``, a scan per seed.  One download.  Returns a dict of host arrays: ``poses`` [N, 3], ``cost`` (uint64, of
         the last stage's winner), ``score`` = -cost / cost_scale, ``start_cost`` (the seed's own) and ``offsets`` [N, stages, 3]
-        (each stage's signed steps in x, y, theta); ``self.last_cover`` keeps the level and its window."""
+        (each stage's signed steps in x, y, theta); ``self.last_cover`` keeps the level and its window.
+        ``rays``: None -- the endpoint cost alone, the path above bit for bit -- or a dict of ``stride``, ``phase`` (0), ``margin``
+        and ``through_cost`` (``refine_ray_options``: the defaults of ``Localiser``'s ``rays``): every candidate of every stage
+        pays ``through_cost`` for each cast beam -- b % stride == phase -- whose measured range lies more than ``margin`` samples
+        beyond a wall of the map (slam2d_refine_poses_rays), so a lattice that straddles a wall does not step to its wrong side
+        for nothing.  The squared distances come as in ``scoreRays``; the result gains ``through`` [N, stages], the through beams
+        of each stage's winner, and ``last_cover`` the filled-in ``rays``."""
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
         N, B = len(poses), self.og.numSamplesPerRev
         if N == 0:
@@ -660,31 +681,56 @@ class ScanMatcher:
         rng = ranges_of(reading_or_ranges, B, N)
         window = covering_window(poses, window)
         lv = self.covering_level(level, window[2], likelihood=likelihood)
+        rs = 0 if rng.ndim == 1 else B
+        if rays is None:
+            return self._refine("refinePoses", lv, window, poses, rng, stages, outside_cost,
+                                lambda eng, a, b, d_rng, radii, steps, cost, words:
+                                eng.refine_poses(lv, 0, a, b, N, 3, d_rng, rs, radii, steps, cost, d_words=words))
+        if outside_cost is None:
+            outside_cost = self.outside_cost_of(lv)
+        opt = refine_ray_options(rays, B, lv.step, self.og.wallThickness, outside_cost)
+        charge = (opt["stride"], opt["phase"], opt["margin"], opt["through_cost"])
+        lvd = lv if likelihood is not None else self._distance_twin(level, window[2])
         return self._refine("refinePoses", lv, window, poses, rng, stages, outside_cost,
-                            lambda eng, a, b, d_rng, radii, steps, cost, words:
-                            eng.refine_poses(lv, 0, a, b, N, 3, d_rng, 0 if rng.ndim == 1 else B, radii, steps, cost, d_words=words))
+                            lambda eng, a, b, d_rng, radii, steps, cost, words, d2, through:
+                            eng.refine_poses_rays(lv, 0, d2, a, b, N, 3, d_rng, rs, radii, steps, cost, *charge, d_words=words, d_through=through),
+                            rays=opt, lvd=lvd)
 
-    def _refine(self, name, lv, window, poses, source, stages, outside_cost, launch):
+    def _refine(self, name, lv, window, poses, source, stages, outside_cost, launch, rays=None, lvd=None):
         """The body of ``refinePoses`` and ``refinePoints`` in the covering level ``lv`` of ``window``: the field, the stages in
         turn -- ``launch(eng, d_in, d_out, d_source, radii, steps, outside_cost, d_words)``, ``source`` the scans or the point sets
-        --, one download, the decoded words."""
+        --, one download, the decoded words.  With ``rays`` (the filled-in options) the squared distances of ``lvd`` -- ``lv``
+        itself, or the distance twin on the same frame, as in ``scoreRays`` -- and a stage's [N] through counts are ``launch``'s
+        last two arguments, and the counts travel in the one download."""
         cx, cy, half = window
         N = len(poses)
         stages = check_stages(stages, lv.step)
         if outside_cost is None:
             outside_cost = self.outside_cost_of(lv)
-        with self._cover(lv, cx, cy) as (eng, _):
+        twin = rays is not None and lvd is not lv
+        with self._cover(lvd if twin else lv, cx, cy, dist2=rays is not None) as (eng, d2), _Exclusive(*((lv,) if twin else ())):
+            if twin:
+                self.build_cover(eng, lv, cx, cy)
+                same_frames(lv, lvd)
             d_pose = [eng.to_device(poses), torch.empty((N, 3), dtype=torch.float64, device=eng.device)]
             d_source = eng.to_device(source)
             words = torch.empty((len(stages), N, _lib.REFINE_STRIDE), dtype=torch.int64, device=eng.device)
+            through = None if rays is None else torch.empty((len(stages), N), dtype=torch.int32, device=eng.device)
             for i, (radii, steps) in enumerate(stages):
-                launch(eng, d_pose[i & 1], d_pose[1 - (i & 1)], d_source, radii, steps, outside_cost, words[i])
-            # one download: the poses, the stages' words and the build's fault word
-            best, w = self._download(eng, name, d_pose[len(stages) & 1], words)
+                more = () if rays is None else (d2, through[i])
+                launch(eng, d_pose[i & 1], d_pose[1 - (i & 1)], d_source, radii, steps, outside_cost, words[i], *more)
+            # one download: the poses, the stages' words, the through counts and the build's fault word
+            more = () if rays is None else (through.to(torch.int64),)
+            best, w, *thr = self._download(eng, name, d_pose[len(stages) & 1], words, *more)
             self.last_cover = dict(level=lv, window=(cx, cy, half), stages=stages)
+            if rays is not None:
+                self.last_cover.update(rays=rays, outside_cost=outside_cost)
         dec = [ParticleEngine.refine_host(w[i], radii, steps, lv.cost_scale) for i, (radii, steps) in enumerate(stages)]
-        return dict(poses=best.copy(), cost=dec[-1]["cost"], score=dec[-1]["score"], start_cost=dec[0]["start_cost"],
-                    offsets=np.stack([d["offsets"] for d in dec], axis=1))
+        res = dict(poses=best.copy(), cost=dec[-1]["cost"], score=dec[-1]["score"], start_cost=dec[0]["start_cost"],
+                   offsets=np.stack([d["offsets"] for d in dec], axis=1))
+        if rays is not None:
+            res["through"] = thr[0].T.copy()
+        return res
 
     def points_level(self, level, half, points, likelihood=None, shared=True):
         """The covering level of ``searchPoints`` / ``refinePoints``: that of ``searchPoses`` for the same window -- the same
